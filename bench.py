@@ -20,6 +20,18 @@ Launch: ``python bench.py --gpus N`` starts its own N ranks (one process per GPU
 GPU call in the parent) unless it already runs under ``python -m torch.distributed.run``
 (RANK/WORLD_SIZE set).  It never runs fewer ranks than asked for.
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps of the workload, writes the
+outputs of its last step if ``--dump-outputs DIR`` is given, and prints its line.  ``--full`` adds everything else the
+benchmark measures, each with runs of its own: at N=1 on C2 the config.extra lines (C3, C1, C1big, C4 / C5 shard 0 of
+8), the C4 and C5 shard sweeps, and the CPU baseline (``--no-extra`` / ``--no-cpu-baseline`` leave parts of it out).
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step, as DIR/<name>.npy in float32 / float64:
+the frame (image.npy, (H,W,3) float32) and its per-pixel closest-hit query counts (ray_counts.npy, (H,W), exact in
+float64) -- with ``--shard``, the shard's tile-major buffers (tiles.npy, tile_ray_counts.npy) -- and the step's ray
+total (rays_per_step.npy).  Beyond 64 MB in all, the same fixed, seeded sample of pixels (work items) is written of
+each array, their indices in sample_index.npy.  Inputs are fixed by the arguments (scene constants and seeds), so two
+builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0, including
   roofline     — the bound the counters support: VALU issue.  ``achieved`` = issue cycles per SIMD
                  per launch = (2 x plain + 4 x binary64 + 8 x transcendental wave-instructions per 64
@@ -29,7 +41,7 @@ Prints ONE JSON line on rank 0, including
                  (SQ_ACTIVE_INST_VALU x 2 / SIMDs).  ``logical_bytes`` keeps the SURVEY 8(d) bytes-per-ray
                  figure -- scene bytes a query CONSULTS, served from SGPRs / LDS, not a memory roofline --
                  and ``traffic`` is the FETCH_SIZE + WRITE_SIZE bytes per launch of the same workload.
-  cpu_baseline — the CPU oracle ("port") on this box's cores, on SURVEY 8(d)'s two samples.
+  cpu_baseline — (--full) the CPU oracle ("port") on this box's cores, on SURVEY 8(d)'s two samples.
 """
 import argparse
 import json
@@ -45,6 +57,8 @@ CLOCK_GHZ = 2.4        # ... max clock 2400 MHz
 # issue cycles per wave64 instruction on a SIMD (same guide): plain VALU 2, binary64 arithmetic 4 (half rate on this
 # part), transcendental 8
 CYC_VALU, CYC_F64, CYC_TRANS = 2, 4, 8
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240917  # ... and the seed of the pixel sample taken when the outputs are larger
 
 WORKLOADS = {
     "c2": dict(scene="cornell_box", size=1024, spp=1024, depth=50),
@@ -66,8 +80,13 @@ def parse(argv=None):
     ap.add_argument("--size", type=int, default=None, help="frame side in pixels (the WHOLE frame, for any N)")
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config.extra lines (C3, C1, C4 / C5 shard 0 of 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the config.extra lines, the C4 / C5 shard sweeps and the CPU baseline (N=1, C2)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the config.extra lines (C3, C1, C4 / C5 shard 0 of 8) and the shard sweeps")
     ap.add_argument("--shard", default=None, help="r/G: render shard r of a G-rank frame on this one GPU")
     ap.add_argument("--shard-sweep", type=int, default=0, metavar="G",
                     help="full frame, then each of the G shards, on this one GPU: predicted G-GPU speedup")
@@ -261,6 +280,7 @@ def run_workload(rtmi, torch, dist, w, args, rank, world, use_dist, steps, warmu
     xdev = "cuda" if on_device else "cpu"
 
     def step(ev=None):
+        """One frame; returns what its caller receives (rank 0 of N: the frame; other ranks: nothing)."""
         R.states.copy_(pristine)
         if ev:
             ev[0].record()
@@ -269,13 +289,15 @@ def run_workload(rtmi, torch, dist, w, args, rank, world, use_dist, steps, warmu
             ev[1].record()
         if shard:
             R.check()  # one shard of G: there is no frame to assemble on this GPU
+            return {"tiles": R.tiles, "tile_ray_counts": R.ray_counts}
         elif use_dist:
             R.check()  # an incomplete frame raises here, before it is handed on
             allt = gather_to_root(R.tiles if on_device else R.tiles.cpu(), 0)
             if rank == 0:
-                R.untile(allt if on_device else allt.cuda())
-        else:
-            R.untile()
+                return {"image": R.untile(allt if on_device else allt.cuda())[0]}
+            return None
+        img, cnt = R.untile()
+        return {"image": img, "ray_counts": cnt}
 
     for _ in range(warmup):
         step()
@@ -285,7 +307,7 @@ def run_workload(rtmi, torch, dist, w, args, rank, world, use_dist, steps, warmu
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        step(events[i])
+        outputs = step(events[i])
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -309,10 +331,35 @@ def run_workload(rtmi, torch, dist, w, args, rank, world, use_dist, steps, warmu
         per_rank_ms = [float(x[0]) for x in allk]
         n_seen = dist.get_world_size()
     n_simd = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count * 4
-    pixels_rank = int((rtmi.pixel_map(R.frame) >= 0).sum())
+    pixel_mask = rtmi.pixel_map(R.frame) >= 0  # work items that carry a pixel (the rest are padding)
+    pixels_rank = int(pixel_mask.sum())
     return dict(H=H, W=W, seed=seed, dt=dt, rays_rank=rays_rank, rays_all=rays_all, kern_ms=kern_ms, kern_ms_all=kerns,
                 per_rank_ms=per_rank_ms, n_seen=n_seen, bytes_per_ray=bytes_per_ray, n_simd=n_simd, shape=shape, mode=mode,
-                pixels_rank=pixels_rank, items=R.items, scene=scene)
+                pixels_rank=pixels_rank, pixel_mask=pixel_mask, items=R.items, scene=scene, outputs=outputs)
+
+
+def dump_outputs(path, outputs, lead, rays_per_step):
+    """--dump-outputs: the last timed step's outputs as <path>/<name>.npy -- float32 as they are, integers as float64
+    (exact) -- and the step's ray total.  The first ``lead`` dimensions of every array index the same pixels (work
+    items); beyond DUMP_BYTES in all, the same fixed, seeded sample of them is written of each, the indices (row-major
+    over those dimensions) in sample_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in outputs.items():
+        a = t.cpu().numpy()
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    rows = int(np.prod(next(iter(arrs.values())).shape[:lead]))
+    total = sum(a.nbytes for a in arrs.values())
+    budget = DUMP_BYTES - 4096  # (room for the .npy headers and rays_per_step)
+    if total > budget:
+        k = int(budget // (total / float(rows) + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=k, replace=False))
+        arrs = {name: a.reshape((rows,) + a.shape[lead:])[idx] for name, a in arrs.items()}
+        arrs["sample_index"] = idx.astype(np.float64)
+    arrs["rays_per_step"] = np.array([rays_per_step], dtype=np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def extra_line(tag, w, r, steps, shard=None):
@@ -446,6 +493,8 @@ def main():
     from rtmi import launch
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and not launch.under_launcher():
         # become the launcher: N children, one per GPU, before this process touches a GPU
         rc = launch.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:],
@@ -497,6 +546,12 @@ def main():
         if len(shard) != 2 or not 0 <= shard[0] < shard[1]:
             raise SystemExit("--shard wants r/G with 0 <= r < G")
     r = run_workload(rtmi, torch, dist, w, args, rank, world, use_dist, args.steps, args.warmup, shard=shard)
+    if args.dump_outputs and r["outputs"] is not None:
+        outs = r["outputs"]
+        if shard:  # tile-major buffers: only the work items that carry a pixel (padding items hold nothing)
+            keep = torch.from_numpy(r["pixel_mask"]).to(outs["tiles"].device)
+            outs = {k: v[keep] for k, v in outs.items()}
+        dump_outputs(args.dump_outputs, outs, 1 if shard else 2, r["rays_all"])
 
     if rank == 0:
         value = r["rays_all"] * args.steps / r["dt"] / 1e6
@@ -523,8 +578,8 @@ def main():
             "roofline": roofline(w, r["rays_rank"], r["kern_ms"], r["bytes_per_ray"], r["n_simd"],
                                  shard or ((rank, world) if world > 1 else None)),
         }
-    if world == 1 and not args.no_extra and w["name"] == "c2" and not shard:
-        # the other BASELINE configs one GPU carries, beside the headline: same contract, shorter runs.
+    if args.full and world == 1 and not args.no_extra and w["name"] == "c2" and not shard:
+        # (--full) the other BASELINE configs one GPU carries, beside the headline: same contract, shorter runs.
         # configs[2] (mesh + BVH); configs[0] (spheres) and its 1024x1024 shape; configs[3] / configs[4] as the
         # shard one GPU of eight renders, at their full sample counts
         extras = []
@@ -547,7 +602,7 @@ def main():
             out["config"]["shard_sweep"] = sweep_digest(sw)
             out["config"]["shard_sweep_c5"] = sweep_digest(sw5)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

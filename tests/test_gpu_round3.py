@@ -668,6 +668,45 @@ def test_bench_shard_and_sweep_paths():
     assert line["n_gpus"] == 1 and "shard 1 only" in line["config"]["workload"] and line["value"] > 0
 
 
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain bench.py run times --steps steps and carries nothing of what --full adds; --dump-outputs writes what the
+    last step returned -- the Python binding's render of the same workload, bit for bit -- and, for a frame whose outputs
+    pass 64 MB, the same seeded sample of pixels of each array."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import common
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def bench(out, *args):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(out)] + list(args), capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+
+    line = bench(tmp_path / "c1", "--workload", "c1")
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mrays/s"
+    assert "cpu_baseline" not in line and "extra" not in line["config"] and "shard_sweep" not in line["config"]
+    img, cnt = np.load(str(tmp_path / "c1" / "image.npy")), np.load(str(tmp_path / "c1" / "ray_counts.npy"))
+    assert img.dtype == np.float32 and img.shape == (256, 256, 3) and cnt.dtype == np.float64 and cnt.shape == (256, 256)
+    want, rays, _, total, _ = common.gpu_render("spheres", 256, 256, 16, 8)
+    assert np.array_equal(img, want) and np.array_equal(cnt, rays.astype(np.float64))
+    assert np.load(str(tmp_path / "c1" / "rays_per_step.npy")).tolist() == [float(total)] == [line["config"]["rays_per_step"]]
+
+    # 2048 x 2048: 80 MB of outputs, so a sample of 64 MB at most
+    bench(tmp_path / "big", "--scene", "spheres", "--size", "2048", "--spp", "1", "--depth", "2")
+    files = sorted(os.listdir(str(tmp_path / "big")))
+    assert files == ["image.npy", "ray_counts.npy", "rays_per_step.npy", "sample_index.npy"], files
+    assert sum(os.path.getsize(str(tmp_path / "big" / f)) for f in files) <= 64 << 20
+    idx = np.load(str(tmp_path / "big" / "sample_index.npy")).astype(np.int64)
+    assert len(idx) > 2 << 20 and (np.diff(idx) > 0).all() and idx[-1] < 2048 * 2048
+    want, rays, _, _, _ = common.gpu_render("spheres", 2048, 2048, 1, 2)
+    assert np.array_equal(np.load(str(tmp_path / "big" / "image.npy")), want.reshape(-1, 3)[idx])
+    assert np.array_equal(np.load(str(tmp_path / "big" / "ray_counts.npy")), rays.reshape(-1)[idx].astype(np.float64))
+
+
 def test_render_mode_reports_the_schedule_of_the_baseline_configs():
     """rtmi_render_mode: what rtmi_render_ex decides before it launches anything, on BASELINE's five configurations (their
     frame shapes; nothing is rendered): C2 and the C4 / C5 shards are planned chains after a first pass of the frame's own

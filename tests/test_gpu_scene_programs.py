@@ -1,8 +1,9 @@
-"""The reference's scene programs, compiled UNCHANGED from /root/reference/scenes/*.cu against
-ray-tracing-cuda_amd/api/ (build: __graft_entry__.build() -> make -C ray-tracing-cuda_amd/api),
+"""The reference's scene programs, compiled UNCHANGED from the reference checkout's scenes/*.cu against
+ray-tracing-cuda_amd/api/ (build: __graft_entry__.build() -> make -C oracle ref, into oracle/_ref/scenes/),
 run on the GPU through Main / DistributedMain, and compared with the ORACLE's render of the same
-worlds (and, as a second check, with the Python binding).  The binaries are built in the development container (the
-reference checkout does not exist on the GPU box) and travel with the repository snapshot.
+worlds (and, as a second check, with the Python binding).  The binaries are built where the reference checkout
+exists and travel with the repository tree under oracle/_ref/; the repository's own scene programs (tests/scenes/*.cu)
+are built by make -C ray-tracing-cuda_amd/api into ray-tracing-cuda_amd/build/scenes/.
 
 Scene constants are computed on the device by the scene's own InitWorld kernel here
 (glm::rotateY -> cosf/sinf, tan in the Camera constructor) and on the host in
@@ -21,10 +22,16 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "ray-tracing-cuda_amd", "build", "scenes")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "scenes")
+REF_SCENES = ("cornell_box", "spheres", "bunny", "birthday")
+
+
+def scene_exe(name):
+    return os.path.join(REF_BIN if name in REF_SCENES else BIN, name)
 
 
 def run_scene(name, tmp_path, h, w, spp, depth=10, extra_env=None):
-    exe = os.path.join(BIN, name)
+    exe = scene_exe(name)
     if not os.path.exists(exe):
         pytest.skip("%s not built (needs the reference checkout at build time)" % exe)
     env = dict(os.environ, RT_HEIGHT=str(h), RT_WIDTH=str(w), RT_SPP=str(spp), RT_MAX_DEPTH=str(depth),
@@ -87,7 +94,7 @@ def file_rccl(tmp_path_factory):
 
 def run_ranks(name, tmp_path, stub, n, h, w, spp, depth=10, extra_env=None, per_rank_setup=None):
     """`n` processes of scene program `name` on this one GPU, their RCCL calls answered by the file-backed stub."""
-    exe = os.path.join(BIN, name)
+    exe = scene_exe(name)
     if not os.path.exists(exe):
         pytest.skip("%s not built" % exe)
     base = tmp_path / ("%s_x%d_%s" % (name, n, "_".join(sorted((extra_env or {}).values())) or "tiles"))
@@ -351,7 +358,7 @@ def test_two_ranks_rendezvous_through_the_id_file(tmp_path):
     ("Duplicate GPU detected") -- which both ranks can only report if the hand-shake worked; with two
     GPUs the job completes and rank 0's frame equals the single-rank frame."""
     import torch
-    exe = os.path.join(BIN, "spheres")
+    exe = scene_exe("spheres")
     if not os.path.exists(exe):
         pytest.skip("%s not built" % exe)
     h, w, spp = 32, 48, 2

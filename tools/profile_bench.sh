@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the evidence bench.py's numbers are checked against (run on the GPU box):
-#   1. rocprofv3 --kernel-trace --stats of the default bench.py command -> per-kernel durations
+#   1. rocprofv3 --kernel-trace --stats of bench.py --full -> per-kernel durations
 #      (C2 headline + the C3 line of config.extra);
 #   2. separate --pmc passes (SQ instruction mix three times -- the third counts the binary64 instructions --, FETCH_SIZE,
 #      WRITE_SIZE) on ONE launch of
@@ -24,7 +24,7 @@ SQ2="SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY
 # (a gpurun call is at most 20 minutes: PROF_SKIP_TRACE=1 / PROF_NO_SUMMARY=1 split the collection over two calls whose
 # outputs merge under gpurun_out/<tag>/; tools/summarize_profile.py then runs on the merged directory, anywhere)
 if [ -z "${PROF_SKIP_TRACE:-}" ]; then
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1 || exit 1
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1 || exit 1
   echo "trace done"
 fi
 for WL in $WLS; do

@@ -1,9 +1,9 @@
 #!/bin/bash
 # Experiment (GPU box): can DistributedMain's RCCL path run with two ranks on ONE GPU?  (RCCL may
-# refuse duplicate devices.)  Runs build/scenes/spheres as ranks 0 and 1 of a 2-rank job, both in
+# refuse duplicate devices.)  Runs oracle/_ref/scenes/spheres as ranks 0 and 1 of a 2-rank job, both in
 # pixel-tile mode and in the reference's sample-split mode, and compares with the 1-rank frame.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-EXE=$ROOT/ray-tracing-cuda_amd/build/scenes/spheres
+EXE=$ROOT/oracle/_ref/scenes/spheres
 OUT=$ROOT/gpurun_out/two_ranks; rm -rf $OUT; mkdir -p $OUT/one $OUT/r0 $OUT/r1 $OUT/s0 $OUT/s1
 export RT_HEIGHT=64 RT_WIDTH=96 RT_SPP=4 HSA_ENABLE_IPC_MODE_LEGACY=0 NCCL_DEBUG=WARN
 (cd $OUT/one && RT_DUMP=$OUT/one/frame.bin timeout -k 5 120 $EXE > log.txt 2>&1) || { echo "1-rank run failed"; tail -3 $OUT/one/log.txt; exit 1; }
