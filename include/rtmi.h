@@ -319,6 +319,54 @@ int rtmi_render_mode(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render
 int rtmi_render_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream);
 
+/* ------------------------------------------------------------------ query --
+ * Batched closest-hit queries on a committed scene: HitableList::Hit (hitable_list.cu:7-25) for rays the
+ * caller made, answered by the trace kernels' own closest-hit engine, bit for bit as a render would.
+ * Added without a version change: a caller detects it by the symbol rtmi_intersect. */
+enum {
+  RTMI_HIT_NONE = 0,
+  RTMI_HIT_SPHERE = 1,
+  RTMI_HIT_TRIANGLE = 2,
+  RTMI_HIT_PARALLELOGRAM = 3,
+  RTMI_HIT_PARALLELEPIPED = 4,
+  RTMI_HIT_MESH = 5,
+  RTMI_HIT_SKY = 6
+};
+typedef struct rtmi_hit {      /* 48 bytes, 16-byte aligned */
+  float t;                     /* (float)record.t as Trace uses it (ray_tracing.cu:32); +INFINITY: no hit */
+  float u, v;                  /* record.u / record.v where the reference sets them, else 0 (Sky, Face<false>) */
+  float normal[3];             /* record.normal (face-oriented for triangles, utils.cu:80); 0 for Sky / no hit */
+  int32_t material;            /* material handle; -1: Sky, no hit */
+  int32_t kind;                /* RTMI_HIT_* */
+  int32_t entry;               /* recording index of the hitable: the n-th successful rtmi_add_* call on the scene,
+                                  0-based, every nesting level counted; -1: no hit */
+  int32_t element;             /* MESH: index of the face in the array given to rtmi_add_bvh; PARALLELEPIPED: its face
+                                  0..5 in the order AddCorner appends them; PARALLELOGRAM: 0/1 = which triangle; else 0 */
+  int32_t reserved[2];         /* 0 */
+} rtmi_hit;
+
+/* n rays: origins and directions float[n][3] (device).  Answers world->Hit(Ray(o, d), 1e-3, INFINITY, &rec) for
+ * each (hitable_list.cu:7-25; Ray normalises d, ray.cu:8-10, so t is along the unit direction), then reports a hit
+ * only if t <= t_max[i] (d_t_max nullable = no limit).
+ *   - t_max is a FILTER on the closest hit over [1e-3, +inf), not a bound passed into the traversal: the reference's
+ *     box tests are not exact in t_to, so Hit(ray, 1e-3, t_max) on a mesh can differ from the filtered answer in
+ *     degenerate cases.  The filtered answer is the one that is exact against the reference.
+ *   - A ray with a non-finite origin or direction, or a direction that does not normalise to a finite non-zero
+ *     vector (a zero direction among them), gets kind RTMI_HIT_NONE; the answers of the other rays do not change.
+ *     The kernel decides this: the host never reads the ray arrays.
+ *   - d_abandoned (nullable, device, one unsigned long long) is incremented by any abandoned mesh search, as the
+ *     render's counter word [2] is; an answer is only exact while it stays 0.
+ * Asynchronous on `stream`; the call shares no device state with renders or with other queries on the same scene.
+ * RTMI_ERR_INVALID before any HIP call for a null or uncommitted scene, n < 0, or null arrays with n > 0; then also
+ * when the current device is not the one the scene was committed on.  n == 0 launches nothing. */
+int rtmi_intersect(const rtmi_scene *s, int64_t n, const float *d_origins, const float *d_dirs,
+                   const float *d_t_max, rtmi_hit *d_hits, unsigned long long *d_abandoned, void *stream);
+/* The diagnostic build (librtmi_check1.so, -DRTMI_CHECK_MARGINS) exports one more entry, declared here only in words
+ * because no other build has it:  rtmi_intersect_check_counts(s, n, d_origins, d_dirs, d_t_max, d_hits, d_abandoned,
+ * unsigned long long *d_check, stream) -- rtmi_intersect with every query answered a second time without any cull,
+ * padded bound or distance slack (meshes: the reference's own tree walk); d_check (nullable, device, two words)
+ * += {queries re-done, disagreements}. */
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

@@ -451,6 +451,13 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   }
   d.cam = s->cam;
   s->dev = d;
+  QueryDev q{};  // (rtmi_intersect only)
+  if ((rc = upload(s, s->q_sphere_entry, &q.sphere_entry))) return rc;
+  if ((rc = upload(s, s->q_pair_entry, &q.pair_entry))) return rc;
+  if ((rc = upload(s, s->q_bvh_entry, &q.bvh_entry))) return rc;
+  if ((rc = upload(s, s->q_face_input, &q.face_input))) return rc;
+  q.sky_entry = s->q_sky_entry;
+  s->qdev = q;
   void *c = nullptr;
   // (behind the counters: the two kernel-argument blocks of a render without caller-owned scratch -- probe pass, real pass)
   HIP_TRY(hipMalloc(&c, RTMI_COUNTER_WORDS * sizeof(unsigned long long) + 2 * render_params_bytes()));
@@ -795,6 +802,48 @@ int rtmi_render_mode(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_rende
   out[7] = d.local_tiles;
   return RTMI_OK;
 }
+
+// ------------------------------------------------------------------ closest-hit queries
+static int intersect(const rtmi_scene *sp, int64_t n, const float *d_o, const float *d_d, const float *d_t_max,
+                     rtmi_hit *d_hits, unsigned long long *d_abandoned, unsigned long long *d_check, void *stream) {
+  static_assert(sizeof(rtmi_hit) == 12 * sizeof(int32_t), "rtmi_hit is 48 bytes");
+  // (argument checks first, without a HIP call: the host never reads the rays)
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
+  if (n > 0 && (!d_o || !d_d || !d_hits)) return fail(RTMI_ERR_INVALID, "null ray or hit array");
+  const Scene *s = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  if (n == 0) return RTMI_OK;
+  int n_cu = 0;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_cus.find(dev);
+    if (it == g_cus.end()) {
+      hipDeviceProp_t prop;
+      HIP_TRY(hipGetDeviceProperties(&prop, dev));
+      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
+    }
+    n_cu = it->second;
+  }
+  HIP_TRY(launch_query(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_o, d_d, d_t_max,
+                       reinterpret_cast<int32_t *>(d_hits), d_abandoned, d_check, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_intersect(const rtmi_scene *s, int64_t n, const float *d_origins, const float *d_dirs, const float *d_t_max,
+                   rtmi_hit *d_hits, unsigned long long *d_abandoned, void *stream) {
+  return intersect(s, n, d_origins, d_dirs, d_t_max, d_hits, d_abandoned, nullptr, stream);
+}
+#ifdef RTMI_CHECK_MARGINS
+int rtmi_intersect_check_counts(const rtmi_scene *s, int64_t n, const float *d_origins, const float *d_dirs,
+                                const float *d_t_max, rtmi_hit *d_hits, unsigned long long *d_abandoned,
+                                unsigned long long *d_check, void *stream) {
+  return intersect(s, n, d_origins, d_dirs, d_t_max, d_hits, d_abandoned, d_check, stream);
+}
+#endif
 
 int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream) {

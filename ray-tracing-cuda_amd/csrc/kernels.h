@@ -95,6 +95,14 @@ hipError_t launch_chain_plan(const uint32_t *d_order, const uint32_t *d_cost, in
 hipError_t launch_untile(const FrameDev &fr, const float *d_tiles, float *d_image, hipStream_t stream);
 hipError_t launch_untile_u32(const FrameDev &fr, const uint32_t *d_tiles, uint32_t *d_image, hipStream_t stream);
 hipError_t launch_post(float *d_img, int64_t n, int spp, hipStream_t stream);
+// Batched closest-hit queries (rtmi_intersect; kernels.hip: query_kernel).  d_hits: n x 12 words (rtmi_hit);
+// d_abandoned, d_t_max, d_check nullable (d_check: -DRTMI_CHECK_MARGINS builds only, {re-done, disagreements}).
+uint32_t pick_query_variant(uint32_t features);
+hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
+                        const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
+                        unsigned long long *d_check, hipStream_t stream);
+// the launch of a batch of n rays: workgroups (as many as fit on n_cu compute units, at most one per 256 rays), lanes each
+hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

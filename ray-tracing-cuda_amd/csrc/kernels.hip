@@ -117,6 +117,7 @@ __global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev f
 #include "mesh_search.h"
 #include "closest_hit.h"
 #include "render_body.h"
+#include "query_body.h"
 
 // The trace kernel proper, and the same code under a second name for the scheduler's 2-spp
 // cost probe (so per-kernel profiles keep the two apart).
@@ -560,8 +561,9 @@ static bool plain_list_scan() {
   return v;
 }
 
+// id_stack = false (query kernels): no stack of material ids, whatever fr.max_depth says.
 static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, size_t *lds_bytes,
-                          bool mats_in_lds = true) {
+                          bool mats_in_lds = true, bool id_stack = true) {
   LaunchCfg lc{};
   lc.threads = threads;
   lc.tile_order = nullptr;
@@ -572,6 +574,7 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   const size_t levels = (size_t)(fr.max_depth > 0 ? fr.max_depth : 1);
   // image-textured variants: one 32-bit word per level (material id, or the sampled texel)
   size_t stack = (variant & F_TEX) ? levels * threads * 4 : (lc.wide_ids == 2 ? (levels + 1) / 2 : levels) * threads * (lc.wide_ids == 1 ? 2 : 1);
+  if (!id_stack) stack = 0;
   size_t noff = (off + stack + 15) & ~(size_t)15;
   lc.nodes_off = (int32_t)noff;
   lc.lds_nodes = (variant & F_BVH) ? (sc.n_nodes < kLdsNodes ? sc.n_nodes : kLdsNodes) : 0;
@@ -599,7 +602,7 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   // of the fourth workgroup stays in global memory -- measured on spheres 1024^2: 7.6 -> 8.5 Grays/s.
   if (groups && mats_in_lds && lc.lds_mats > 0 && *lds_bytes * (size_t)(1024 / threads) > 160 * 1024) {
     size_t without = 0;
-    const LaunchCfg alt = make_cfg(variant, sc, fr, threads, &without, false);
+    const LaunchCfg alt = make_cfg(variant, sc, fr, threads, &without, false, id_stack);
     if (without * (size_t)(1024 / threads) <= 160 * 1024) {
       *lds_bytes = without;
       return alt;
@@ -753,6 +756,114 @@ hipError_t launch_post(float *d_img, int64_t n, int spp, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(post_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, d_img, n, spp);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ closest-hit queries (rtmi_intersect)
+// query_body.h around the render's closest_hit<F>.  Instantiated with F_TEX always (closest_hit tracks the winner's
+// u, v bitwise only then) and without F_DEFOCUS (no camera is involved): the render variants so mapped.
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void query_kernel(QueryParams qp) {
+  query_body<F>(qp);
+}
+
+#define RTMI_FOR_EACH_QUERY_VARIANT(X)               \
+  X(F_TEX)                                           \
+  X(F_TRIS | F_TEX)                                  \
+  X(F_SPHERE | F_TEX)                                \
+  X(F_TRIS | F_SPHERE | F_TEX)                       \
+  X(F_SPHERE | F_SGROUP | F_TEX)                     \
+  X(F_TRIS | F_SPHERE | F_SGROUP | F_TEX)            \
+  X(F_TRIS | F_BVH | F_TEX)                          \
+  X(F_ALL & ~F_DEFOCUS)
+
+uint32_t pick_query_variant(uint32_t features) {
+  features = (features & ~(uint32_t)F_DEFOCUS) | F_TEX;
+#define X(V) \
+  if ((features & ~(uint32_t)(V)) == 0) return (V);
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return F_ALL & ~F_DEFOCUS;
+}
+
+constexpr int kQueryThreads = 256;
+
+static LaunchCfg query_cfg(uint32_t variant, const SceneDev &sc, size_t *lds) {
+  FrameDev fr{};  // (make_cfg reads max_depth only, for the id stack the queries do without)
+  LaunchCfg lc = make_cfg(variant, sc, fr, kQueryThreads, lds, false, false);  // (nothing is shaded: no material table)
+  *lds = ((*lds + 15) & ~(size_t)15) + kQueryLdsExtra;
+  return lc;
+}
+
+template <uint32_t F>
+static hipError_t query_attrs_t(size_t lds) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(query_kernel<F>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  // query_body.h hands the mesh search and the list scans LDS by byte offset, as render_body.h does: right only while
+  // the kernel declares no static LDS
+  static const hipError_t lds_ok = [] {
+    hipFuncAttributes a{};
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(query_kernel<F>));
+    if (e != hipSuccess) return e;
+    return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
+  }();
+  return lds_ok;
+}
+
+template <uint32_t F>
+static hipError_t query_shape_t(const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads) {
+  size_t lds = 0;
+  (void)query_cfg(F, sc, &lds);
+  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
+  hipError_t e = query_attrs_t<F>(lds);
+  if (e != hipSuccess) return e;
+  int nb = 0;
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, query_kernel<F>, kQueryThreads, lds);
+  if (e != hipSuccess) return e;
+  if (nb < 1) nb = 1;
+  const int64_t want = (n + kQueryThreads - 1) / kQueryThreads, cap = (int64_t)n_cu * nb;
+  *blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
+  *threads = kQueryThreads;
+  return hipSuccess;
+}
+
+template <uint32_t F>
+static hipError_t launch_query_t(const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
+                                 const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
+                                 unsigned long long *d_check, hipStream_t stream) {
+  int blocks = 0, threads = 0;
+  hipError_t e = query_shape_t<F>(sc, n_cu, n, &blocks, &threads);
+  if (e != hipSuccess) return e;
+  size_t lds = 0;
+  QueryParams qp;
+  qp.sc = sc, qp.qd = qd;
+  qp.lc = query_cfg(F, sc, &lds);
+  qp.n = n, qp.origins = d_o, qp.dirs = d_d, qp.t_max = d_t_max, qp.hits = d_hits;
+  qp.abandoned = d_abandoned, qp.check = d_check;
+  qp.dummy_off = (int32_t)(lds - kQueryLdsExtra);
+  hipLaunchKernelGGL(query_kernel<F>, dim3(blocks), dim3(threads), lds, stream, qp);
+  return hipGetLastError();
+}
+
+hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
+                        const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
+                        unsigned long long *d_check, hipStream_t stream) {
+#define X(V) \
+  if (variant == (uint32_t)(V)) \
+    return launch_query_t<(V)>(sc, qd, n_cu, n, d_o, d_d, d_t_max, d_hits, d_abandoned, d_check, stream);
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads) {
+#define X(V) \
+  if (variant == (uint32_t)(V)) return query_shape_t<(V)>(sc, n_cu, n, blocks, threads);
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return hipErrorInvalidValue;
 }
 
 }  // namespace rtmi

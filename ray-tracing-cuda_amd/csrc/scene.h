@@ -81,8 +81,12 @@ struct Scene {
   std::vector<int32_t> face_of_orig;  // (used by -DRTMI_CHECK_MARGINS builds only) reference face order -> physical
   std::vector<MatRec> mat_recs;
   std::vector<TexRec> tex_recs;
+  // rtmi_intersect only (QueryDev): flattened records -> recording order
+  std::vector<int32_t> q_sphere_entry, q_pair_entry, q_bvh_entry, q_face_input;
+  int32_t q_sky_entry = -1;
   std::vector<void *> dev_allocs;
   SceneDev dev{};
+  QueryDev qdev{};
   unsigned long long *d_counters = nullptr;  // [0] work queue head, [1] total rays, [2] abandoned mesh searches
   int device = -1;
   int64_t bytes_per_ray = 0;

@@ -161,6 +161,7 @@ struct FacePts {
   V3 p[3];
   float uv[6];
   int orig;
+  int input;  // index in the array given to rtmi_add_bvh (rtmi_intersect's `element`)
   uint32_t code;
   int leaf;  // ordinal of the reference leaf in visiting order
   int kexp;  // slack exponent of the face (face_slack_exponent): the search boxes above it are widened by 2^kexp
@@ -558,6 +559,7 @@ std::string Scene::flatten() {
   sliver_faces = 0;
   runs.clear(), spheres.clear(), tris.clear(), bvh_recs.clear(), face_of_orig.clear(), nodes.clear(), qnodes.clear(), faces.clear(), leaf_paths.clear(), tops.clear(),
       face_uv.clear(), mat_recs.clear(), tex_recs.clear();
+  q_sphere_entry.clear(), q_pair_entry.clear(), q_bvh_entry.clear(), q_face_input.clear(), q_sky_entry = -1;
   features = 0;
   n_pgrams = n_triangles = n_spheres = 0;
   sub_depth = 0;
@@ -602,8 +604,15 @@ std::string Scene::flatten() {
 
   bytes_per_ray = 32;  // material / hit-record share per query
   for (const HostObj &ob : world) {
+    const int32_t entry = (int32_t)(&ob - world.data());  // one HostObj per rtmi_add_* call, in call order
+    // (rtmi_intersect: the entry and kind of every pair of `tris` records pushed for this hitable)
+    auto name_pairs = [&](int32_t kind) {
+      for (int32_t face = 0; (size_t)(q_pair_entry.size() / 2) < tris.size() / 2; face++)
+        q_pair_entry.push_back(entry), q_pair_entry.push_back(kind | face << 8);
+    };
     switch (ob.kind) {
       case OBJ_SKY:
+        if (q_sky_entry < 0) q_sky_entry = entry;
         runs.push_back(Run{RUN_SKY, 0, 1, 0});
         break;
       case OBJ_SPHERE: {
@@ -614,6 +623,7 @@ std::string Scene::flatten() {
         r.radius = ob.radius;
         r.r2 = ob.radius * ob.radius;
         spheres.push_back(r);
+        q_sphere_entry.push_back(entry);
         push_run(RUN_SPHERE, (int)spheres.size() - 1);
         features |= F_SPHERE;
         bytes_per_ray += 28;
@@ -625,6 +635,7 @@ std::string Scene::flatten() {
         tris.push_back(HotTri{});  // inert second record: the world-list loop walks pairs
         push_pair(*this, ob.p, 3, 0);
         push_run(RUN_TRIS, (int)tris.size() - 2);
+        name_pairs(QHIT_TRIANGLE);
         features |= F_TRIS;
         n_triangles++;
         bytes_per_ray += 40;
@@ -634,6 +645,7 @@ std::string Scene::flatten() {
         if (!check_mat(ob.mat)) return "parallelogram without a valid material";
         push_pgram(*this, ob.p[0], ob.p[1], ob.p[2], ob.mat);
         push_run(RUN_TRIS, (int)tris.size() - 2);
+        name_pairs(QHIT_PARALLELOGRAM);
         features |= F_TRIS;
         n_pgrams++;
         bytes_per_ray += 40;
@@ -647,6 +659,7 @@ std::string Scene::flatten() {
           n_pgrams++;
           bytes_per_ray += 40;
         }
+        name_pairs(QHIT_PARALLELEPIPED);  // face = 0..5, AddCorner order
         features |= F_TRIS;
         break;
       }
@@ -662,6 +675,7 @@ std::string Scene::flatten() {
                             hb.faces[(size_t)i * 9 + j * 3 + 2]);
           for (int j = 0; j < 6; j++) fp[i].uv[j] = has_uv ? hb.uvs[(size_t)i * 6 + j] : 0.f;
           fp[i].kexp = face_slack_exponent(fp[i].p);
+          fp[i].input = i;
           if (fp[i].kexp > 0) sliver_faces++;  // thinner than 1.8 degrees: its nodes' boxes are widened for it
         }
         int leaf_max = hb.leaf_max > 0 ? hb.leaf_max : 2048;
@@ -738,6 +752,7 @@ std::string Scene::flatten() {
           f.code = fp[i].code;
           f.leaf = fp[i].leaf;
           faces.push_back(f);
+          q_face_input.push_back(fp[i].input);
           if (has_uv)  // texture coordinates stay in the reference's order, addressed by `orig`
             for (int j = 0; j < 6; j++) face_uv[(size_t)(face_base + fp[i].orig) * 6 + j] = fp[i].uv[j];
         }
@@ -754,6 +769,7 @@ std::string Scene::flatten() {
         if (br.root >= 0) {
           build_top_entries(qnodes, br.sub_root, tops);  // row = index of the record
           bvh_recs.push_back(br);
+          q_bvh_entry.push_back(entry);
           push_run(RUN_BVH, (int)bvh_recs.size() - 1);
           features |= F_BVH;
         }

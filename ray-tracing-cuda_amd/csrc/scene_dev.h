@@ -262,6 +262,18 @@ struct SceneDev {
   CameraDev cam;
 };
 
+// What only rtmi_intersect reads (query_body.h): the flattened records back to recording order, so that a hit can
+// name its hitable.  Kept apart from SceneDev, whose layout the trace kernels' argument block fixes.
+enum : int32_t { QHIT_NONE = 0, QHIT_SPHERE = 1, QHIT_TRIANGLE = 2, QHIT_PARALLELOGRAM = 3, QHIT_PARALLELEPIPED = 4,
+                 QHIT_MESH = 5, QHIT_SKY = 6 };  // == RTMI_HIT_* of include/rtmi.h
+struct QueryDev {
+  const int32_t *sphere_entry;  // per SphereRec: its entry (index of the rtmi_add_* call)
+  const int32_t *pair_entry;    // per pair of HotTri records: {entry, kind | face << 8} (face: 0..5 of a parallelepiped)
+  const int32_t *bvh_entry;     // per BvhRec: its entry
+  const int32_t *face_input;    // per FaceRec: the face's index in the array given to rtmi_add_bvh
+  int32_t sky_entry;            // the first Sky of the flattened list (the only one that can win: all answer t = 1e9), -1: none
+};
+
 // Feature bits selecting a kernel specialisation.
 enum : uint32_t {
   F_SPHERE = 1u,   // double-precision t

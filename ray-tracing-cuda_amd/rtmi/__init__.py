@@ -5,6 +5,7 @@ for the scene recorder / RNG / render entry points and PyTorch tensors for devic
 memory, streams and ``torch.distributed``.  There is no CPU rendering path: every
 compute call raises ``RtmiError`` when librtmi.so or a GPU is missing.
 """
+import collections
 import ctypes as C
 import os
 
@@ -18,6 +19,16 @@ LIB_PATH = os.environ.get("RTMI_LIB_PATH") or os.path.join(_ROOT, "lib", "librtm
 TILE = 8
 STATE_WORDS = 6
 MAX_DEPTH = 64
+
+# rtmi_hit.kind (include/rtmi.h)
+RTMI_HIT_NONE = 0
+RTMI_HIT_SPHERE = 1
+RTMI_HIT_TRIANGLE = 2
+RTMI_HIT_PARALLELOGRAM = 3
+RTMI_HIT_PARALLELEPIPED = 4
+RTMI_HIT_MESH = 5
+RTMI_HIT_SKY = 6
+HIT_WORDS = 12  # sizeof(rtmi_hit) / 4
 
 
 class RtmiError(RuntimeError):
@@ -122,6 +133,8 @@ SYMBOLS = [
     ("rtmi_selftest_arithmetic", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("rtmi_set_launch", C.c_int, [C.c_int, C.c_int]),
     ("rtmi_set_schedule", C.c_int, [C.c_int]),
+    ("rtmi_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
 ]
 
 
@@ -174,6 +187,19 @@ def pixel_map(frame):
 
 def get_workload(rank, world_size, spp):
     return lib().rtmi_get_workload(rank, world_size, spp)
+
+
+class Hits(collections.namedtuple("Hits", "t uv normal material kind entry element")):
+    """What ``SceneBuilder.intersect`` returns: views into one (N, 12) int32 buffer of rtmi_hit records (``raw``) --
+    t (N,) float32 (+inf: no hit), uv (N, 2) float32, normal (N, 3) float32, material / kind / entry / element (N,)
+    int32.  ``check()`` waits for the query and raises when it abandoned a mesh search (its answers are then not to
+    be used)."""
+
+    def check(self):
+        n = int(self.abandoned.item())  # (a device-to-host copy: waits for the query)
+        if n:
+            raise RtmiError("rtmi_intersect abandoned %d mesh search(es): the answers are incomplete" % n)
+        return self
 
 
 class SceneBuilder:
@@ -298,7 +324,73 @@ class SceneBuilder:
 
     def commit(self):
         _check(self.L.rtmi_scene_commit(self.h), "rtmi_scene_commit")
+        self.device = None
+        try:
+            import torch
+            if torch.cuda.is_available():
+                self.device = torch.device("cuda", torch.cuda.current_device())
+        except ImportError:
+            pass
         return self
+
+    def intersect(self, origins, directions, t_max=None, out=None):
+        """Closest hit of each ray on the committed scene (rtmi_intersect), enqueued on torch's current stream.
+
+        ``origins`` / ``directions``: CUDA float32 (N, 3) tensors on the scene's device (directions need not be unit
+        length: Ray normalises them, and t is along the unit direction); ``t_max`` (N,) float32 or None: a hit is
+        reported only where t <= t_max.  ``out``: an optional (N, 12) int32 CUDA tensor to write into.  Returns
+        ``Hits`` (views into that buffer); call ``.check()`` on it before trusting the answers of a mesh scene."""
+        import torch
+        n = _check_rays(origins, "origins")
+        if _check_rays(directions, "directions") != n:
+            raise RtmiError("origins and directions differ in length")
+        if origins.device != directions.device:
+            raise RtmiError("origins and directions are on different devices")
+        dev = origins.device
+        if t_max is not None:
+            if not (isinstance(t_max, torch.Tensor) and t_max.is_cuda and t_max.dtype == torch.float32 and
+                    t_max.shape == (n,) and t_max.device == dev):
+                raise RtmiError("t_max must be a CUDA float32 tensor of shape (N,) on the rays' device")
+            t_max = t_max.contiguous()
+        if out is None:
+            out = torch.empty((n, HIT_WORDS), dtype=torch.int32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and
+                  out.shape == (n, HIT_WORDS) and out.is_contiguous() and out.device == dev):
+            raise RtmiError("out must be a contiguous CUDA int32 tensor of shape (N, 12) on the rays' device")
+        if self.h.value is None or getattr(self, "device", None) is None:
+            raise RtmiError("scene not committed")
+        if dev != self.device:
+            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        origins, directions = origins.contiguous(), directions.contiguous()
+        abandoned = torch.zeros((1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _check(self.L.rtmi_intersect(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                         C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(abandoned.data_ptr()), stream),
+                   "rtmi_intersect")
+        f = out.view(torch.float32)
+        hits = Hits(f[:, 0], f[:, 1:3], f[:, 3:6], out[:, 6], out[:, 7], out[:, 8], out[:, 9])
+        hits.raw, hits.abandoned = out, abandoned
+        hits._rays = (origins, directions, t_max)  # (kept alive while the query may still read them)
+        return hits
+
+
+def _check_rays(a, what):
+    """Length of a (N, 3) CUDA float32 tensor; raises before any GPU work otherwise."""
+    try:
+        import torch
+    except ImportError:
+        raise RtmiError("%s: torch is needed for rtmi_intersect" % what)
+    if not isinstance(a, torch.Tensor):
+        raise RtmiError("%s must be a torch tensor" % what)
+    if not a.is_cuda:
+        raise RtmiError("%s is on the CPU: rtmi_intersect has no CPU path (move it to the scene's GPU)" % what)
+    if a.dtype != torch.float32:
+        raise RtmiError("%s must be float32, not %s" % (what, a.dtype))
+    if a.dim() != 2 or a.shape[1] != 3:
+        raise RtmiError("%s must have shape (N, 3), not %s" % (what, tuple(a.shape)))
+    return int(a.shape[0])
 
 
 class Renderer:
