@@ -367,6 +367,37 @@ int rtmi_intersect(const rtmi_scene *s, int64_t n, const float *d_origins, const
  * padded bound or distance slack (meshes: the reference's own tree walk); d_check (nullable, device, two words)
  * += {queries re-done, disagreements}. */
 
+/* Any-hit visibility queries (shadow rays, ambient occlusion): one byte per ray, stopping at the first hit that
+ * decides it.  Added without a version change: a caller detects it by the symbol rtmi_occluded.
+ *
+ * d_occluded[i] = 1 exactly when rtmi_intersect with the same ray and the same t_max reports kind != RTMI_HIT_NONE,
+ * i.e. world->Hit(Ray(o, d), 1e-3, INFINITY, &rec) has a hit and (float)rec.t <= t_max[i] (d_t_max nullable = no
+ * limit); else 0.  So:
+ *   - Sky counts: it answers at t = 1e9, so a world with Sky occludes every ray whose t_max >= 1e9.
+ *   - A NaN t_max means clear; t_max < 1e-3 (0, negative) is clear too.
+ *   - A bad ray (non-finite origin or direction, or a direction that does not normalise) answers 0 and changes no
+ *     other answer, as for rtmi_intersect.
+ * Unlike rtmi_intersect, t_max bounds the traversal: every cull prunes by it and a ray stops at its first
+ * acceptance.  That is exact except on meshes (quirk g8): the reference's AABB::Hit asks for a crossing of the box's
+ * SURFACE inside [t_from, t_to], so a ray that starts inside a box and leaves it beyond t_max does not enter it under
+ * the bound, where the unbounded walk does and may find a face nearer than t_max.  A mesh whose search finds faces
+ * within t_max that the bounded replay refuses therefore leaves the ray undecided, and such a ray (if nothing else
+ * occludes it) is answered again by the unbounded closest-hit engine, then the filter.  (Rays that start inside the
+ * meshes' bounds with a t_max of at least 1/20 of their extent, where that is the common case, take the unbounded walk
+ * from the start, still stopping at the first hit that decides them.)
+ *   - d_counts (nullable, device, two unsigned long long): [0] += abandoned mesh searches (as rtmi_intersect's
+ *     d_abandoned; an answer is only exact while it stays 0), [1] += rays answered by that exact fallback.
+ * Asynchronous on `stream`; the call shares no device state with renders or with other queries on the same scene.
+ * RTMI_ERR_INVALID before any HIP call for a null or uncommitted scene, n < 0, or null arrays with n > 0; then also
+ * when the current device is not the one the scene was committed on.  n == 0 launches nothing. */
+int rtmi_occluded(const rtmi_scene *s, int64_t n, const float *d_origins, const float *d_dirs, const float *d_t_max,
+                  uint8_t *d_occluded, unsigned long long *d_counts, void *stream);
+/* The diagnostic build (librtmi_check1.so) also exports, declared here only in words:
+ * rtmi_occluded_check_counts(s, n, d_origins, d_dirs, d_t_max, d_occluded, d_counts, unsigned long long *d_check,
+ * stream) -- rtmi_occluded with every ray answered a second time by the unculled closest-hit engine from +inf (meshes:
+ * the reference's own tree walk), then the filter; d_check (nullable, device, two words) += {rays re-done,
+ * disagreements}. */
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

@@ -67,18 +67,31 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 // `live`: mesh variants are entered by ALL lanes of the wave (the mesh search borrows idle
 // lanes); a lane that is not tracing passes live = false and gets an unused result.  The other
 // variants are only entered by tracing lanes and pass true.
-template <uint32_t F>
+//
+// OCC (occlusion_body.h, rtmi_occluded): the same engine as a yes/no question "is anything accepted at t <= t_stop?".
+// The running bound starts at t_start instead of +inf (t_start = t_stop: the bounded pass; +inf: the exact fallback),
+// and a lane is decided once it has accepted something at or below t_stop: it takes no further part in this call, and
+// the wave leaves when none of its lanes is undecided.  In the bounded pass a mesh whose search lists faces that its
+// replay then refuses sets *uncertain (quirk g8: AABB::Hit asks for a crossing of the box's surface inside [t_from,
+// t_to], so a ray that starts inside a box and leaves it beyond t_stop does not enter it, where the unbounded walk
+// would).  With OCC false none of this is compiled in.
+template <uint32_t F, bool OCC = false>
 __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_nodes, int lds_nodes, const int *s_paths,
                                            int lds_paths, const float4 *s_pairs, int *ll, uint16_t *cands, int *wl,
                                            unsigned long long *overflow, V3 o, V3 d, bool live, bool count_work
 #ifdef RTMI_STATS
                                            , MeshStats &st
 #endif
+                                           , double t_start = INFINITY, double t_stop = INFINITY, bool *uncertain = nullptr
 ) {
   constexpr bool DT = (F & F_SPHERE) != 0;
   typedef typename TSel<DT>::type T;
   bool ok = false;
-  T t_to = (T)INFINITY;
+  T t_to = OCC ? (T)t_start : (T)INFINITY;
+  // (OCC) decided: something was accepted at or below t_stop, so the closest hit is there too.  (A macro, not a
+  // lambda: with OCC false it must fold away before anything else sees it, so that the render, probe and query
+  // kernels compile to what they were.)
+#define RTMI_DECIDED (OCC && ok && t_to <= (T)t_stop)
   uint32_t win = ID_NONE;
   int32_t aux = 0;
   int32_t work = 0;
@@ -111,6 +124,10 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   }
 
   for (int ri = 0; ri < sc.n_runs; ri++) {
+    if (OCC) {  // a decided lane only helps from here on; a wave without undecided lanes is done
+      live = live && !RTMI_DECIDED;
+      if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+    }
     const i32x4 rv = load_run(sc.runs, ri);
     Run run;
     run.kind = rv[0], run.first = rv[1], run.count = rv[2], run.pad = rv[3];
@@ -138,6 +155,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
       const int pair0 = run.first >> 1;
       const float lo0 = T_FROM_F * kTimeLo;
       for (int c0 = 0; c0 < run.count; c0 += 32) {
+        if (OCC && __builtin_amdgcn_ballot_w64(live && !RTMI_DECIDED) == 0ull) break;
         const int nc = run.count - c0 < 32 ? run.count - c0 : 32;
         const float hi0 = (float)t_to * kTimeHi + kTimeAbs;
         uint32_t mask = 0u;
@@ -178,6 +196,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
 #undef RTMI_CULL_PAIR
         mask = __brev(mask) >> (32 - nc);  // bit i = pair i of the chunk (1 <= nc <= 32)
         if (!live) mask = 0u;  // a lane without a ray of its own only helps
+        if (OCC && RTMI_DECIDED) mask = 0u;
         RTMI_STAT2(const unsigned long long tc1 = stat_now(); st.cyc[5] += tc1 - tc0;)
         RTMI_STAT(st.cull_bits += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(true)) * 0u; { unsigned pc = __builtin_popcount(mask); for (int off = 32; off > 0; off >>= 1) pc += __shfl_down(pc, off); st.cull_bits += __builtin_amdgcn_readfirstlane(pc); } st.cull_rays += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(true));)
 #ifndef RTMI_OWN_FIRST
@@ -221,6 +240,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             }
           }
         }
+        if (OCC && RTMI_DECIDED) mask = 0u;  // its remaining candidates cannot change a yes
 #endif
         {
           // ---- the (remaining) candidates of all 64 rays are worked off by all 64 lanes.  A ray comes near 2.2 pairs on
@@ -337,6 +357,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
       const HotTri *base = sc.tris + run.first;
       f32x16 A = load_hot_tri(base, 0);
       for (int i = 0; i < run.count; i++) {
+        if (OCC && __builtin_amdgcn_ballot_w64(!RTMI_DECIDED) == 0ull) break;
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): A has landed
         __builtin_amdgcn_sched_barrier(0);
         const f32x16 B = load_hot_tri(base, 2 * i + 1);
@@ -568,6 +589,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
     if ((F & F_SPHERE) && live && run.kind == RUN_SPHERE && !grouped_done) {
       f32x8 nxt = load_sphere(sc.spheres, run.first);
       for (int i = 0; i < run.count; i++) {
+        if (OCC && __builtin_amdgcn_ballot_w64(!RTMI_DECIDED) == 0ull) break;
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): see the triangle loop
         __builtin_amdgcn_sched_barrier(0);
         const f32x8 cur = nxt;
@@ -587,7 +609,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
           const float oc2 = dot3(oc, oc), r2f = (float)r2;
           const float disc_f = bf * bf - 4.0f * saf * (oc2 - r2f);
           const float mag = bf * bf + 4.0f * saf * (oc2 + r2f);
-          if (!__any(!(disc_f < -kSphDiscRel * mag))) continue;
+          if (!__any(!(disc_f < -kSphDiscRel * mag) && !RTMI_DECIDED)) continue;  // (OCC: a decided lane needs nothing)
         }
         double b = (double)bf;
         float lc = len3(oc);
@@ -637,6 +659,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
       const V3 inv_d = mk(safe_inverse(d.x), safe_inverse(d.y), safe_inverse(d.z));
       int *rr = wl + lane * kMeshRayWords;
       for (int i = 0; i < run.count; i++) {
+        if (OCC && __builtin_amdgcn_ballot_w64(live && !RTMI_DECIDED) == 0ull) break;
         BvhRec br;
         {
           const i32x16 bw = load_bvh_rec(sc.bvhs, run.first + i);  // wave-uniform: one scalar load, root bounds included
@@ -669,7 +692,8 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
         bool have_prev = false;
         uint32_t prev_code = 0u, entered = 0u;
         uint32_t lo_code = 0u;
-        bool need = live;
+        bool need = live && !RTMI_DECIDED;
+        bool listed = false;  // (OCC) the search listed a face of this mesh
 #ifndef RTMI_MESH_PRETEST
 #define RTMI_MESH_PRETEST 1
 #endif
@@ -739,6 +763,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
           int nleaf = 0;
 #pragma unroll
           for (int j = 0; j < kHitSlots; j++) nleaf += (uint32_t)hs[j].x != kCodeNone ? 1 : 0;
+          if (OCC) listed = listed || nleaf > 0;
           const int depth_r = br.ref_depth;
           const int log_d = depth_r < 8 ? 3 : depth_r < 16 ? 4 : 5;  // a leaf's row: its path code + the crossing times, 8, 16 or 32 words
           // (rows of this round: `leaves` holds 64 of them, `times` the rest of the stack's words)
@@ -860,10 +885,13 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             }
           }
           need = need && cut != kCodeNone;  // leaves were deferred: search again from `cut` on
+          if (OCC) need = need && !(bhit && bt_to <= (T)t_stop);  // decided: the deferred leaves cannot change a yes
           lo_code = cut;
           RTMI_STAT(st.cyc[3] += stat_now() - ts1;)
         }
-        if (bhit && (F & F_TEX)) {
+        // (OCC, bounded pass) listed but refused: the unbounded walk may still enter those leaves' boxes
+        if (OCC && uncertain != nullptr && listed && !bhit && t_start != (double)INFINITY) *uncertain = true;
+        if (!OCC && bhit && (F & F_TEX)) {
           // barycentrics of the winner (the same binary32 operations as in the search)
           const FaceRec f = sc.faces[bface];
           float t = 0.f;
@@ -881,6 +909,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
       }
     }
   }
+#undef RTMI_DECIDED
   Hit h;
   h.ok = ok;
   h.t = (float)t_to;

@@ -103,6 +103,14 @@ hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd
                         unsigned long long *d_check, hipStream_t stream);
 // the launch of a batch of n rays: workgroups (as many as fit on n_cu compute units, at most one per 256 rays), lanes each
 hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads);
+// Batched any-hit visibility queries (rtmi_occluded; kernels.hip: occlusion_kernel), on the query variants.
+// d_occluded: n bytes; d_t_max, d_counts ({abandoned, fallback rays}), d_check nullable (as launch_query).  Rays whose
+// origin lies inside [near_lo, near_hi] (the padded union of the meshes' root bounds) and whose t_max is not below
+// near_short start the walk from +inf.
+hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
+                            float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
+                            const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
+                            unsigned long long *d_check, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

@@ -118,6 +118,7 @@ __global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev f
 #include "closest_hit.h"
 #include "render_body.h"
 #include "query_body.h"
+#include "occlusion_body.h"
 
 // The trace kernel proper, and the same code under a second name for the scheduler's 2-spp
 // cost probe (so per-kernel profiles keep the two apart).
@@ -861,6 +862,79 @@ hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd
 hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads) {
 #define X(V) \
   if (variant == (uint32_t)(V)) return query_shape_t<(V)>(sc, n_cu, n, blocks, threads);
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+
+// ------------------------------------------------------------------ any-hit visibility queries (rtmi_occluded)
+// occlusion_body.h around closest_hit<F, true>: one instantiation per query variant, with the query kernels' staging,
+// LDS layout (plus its own stand-in words) and launch sizing.
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlusion_kernel(OcclusionParams p) {
+  occlusion_body<F>(p);
+}
+
+static LaunchCfg occlusion_cfg(uint32_t variant, const SceneDev &sc, size_t *lds) {
+  FrameDev fr{};
+  LaunchCfg lc = make_cfg(variant, sc, fr, kQueryThreads, lds, false, false);
+  *lds = ((*lds + 15) & ~(size_t)15) + kOcclusionLdsExtra;
+  return lc;
+}
+
+template <uint32_t F>
+static hipError_t occlusion_attrs_t(size_t lds) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(occlusion_kernel<F>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  // LDS regions by byte offset of the dynamic array: right only while the kernel declares no static LDS
+  static const hipError_t lds_ok = [] {
+    hipFuncAttributes a{};
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(occlusion_kernel<F>));
+    if (e != hipSuccess) return e;
+    return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
+  }();
+  return lds_ok;
+}
+
+template <uint32_t F>
+static hipError_t launch_occlusion_t(const SceneDev &sc, const float near_lo[3], const float near_hi[3],
+                                     float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
+                                     const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
+                                     unsigned long long *d_check, hipStream_t stream) {
+  size_t lds = 0;
+  OcclusionParams p;
+  p.sc = sc;
+  p.lc = occlusion_cfg(F, sc, &lds);
+  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
+  hipError_t e = occlusion_attrs_t<F>(lds);
+  if (e != hipSuccess) return e;
+  int nb = 0;
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, occlusion_kernel<F>, kQueryThreads, lds);
+  if (e != hipSuccess) return e;
+  if (nb < 1) nb = 1;
+  const int64_t want = (n + kQueryThreads - 1) / kQueryThreads, cap = (int64_t)n_cu * nb;
+  const int blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
+  p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
+  p.counts = d_counts, p.check = d_check;
+  p.dummy_off = (int32_t)(lds - kOcclusionLdsExtra);
+  for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
+  p.near_short = near_short;
+  hipLaunchKernelGGL(occlusion_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
+                            float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
+                            const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
+                            unsigned long long *d_check, hipStream_t stream) {
+#define X(V) \
+  if (variant == (uint32_t)(V)) \
+    return launch_occlusion_t<(V)>(sc, near_lo, near_hi, near_short, n_cu, n, d_o, d_d, d_t_max, d_occluded, \
+                                   d_counts, d_check, stream);
   RTMI_FOR_EACH_QUERY_VARIANT(X)
 #undef X
   return hipErrorInvalidValue;

@@ -103,7 +103,8 @@ __device__ __forceinline__ void query_body(const QueryParams &qp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SceneDev &sc = qp.sc;
   const LaunchCfg &lc = qp.lc;
-  // ---- staging: as render_body.h's prologue (materials are not read: nothing is shaded)
+  // ---- staging: as render_body.h's prologue (materials are not read: nothing is shaded).  occlusion_body.h has the
+  // same staging as a function (query_stage): a change here is a change there.
   const BvhNode *s_nodes = reinterpret_cast<const BvhNode *>(smem + lc.nodes_off);
   int *wl = nullptr;
   if (F & F_BVH)

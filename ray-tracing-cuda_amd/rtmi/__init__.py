@@ -135,6 +135,8 @@ SYMBOLS = [
     ("rtmi_set_schedule", C.c_int, [C.c_int]),
     ("rtmi_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
+    ("rtmi_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
 ]
 
 
@@ -200,6 +202,28 @@ class Hits(collections.namedtuple("Hits", "t uv normal material kind entry eleme
         if n:
             raise RtmiError("rtmi_intersect abandoned %d mesh search(es): the answers are incomplete" % n)
         return self
+
+
+class Occlusion:
+    """What ``SceneBuilder.occluded`` returns: ``mask`` (N,) torch.bool, a view of the (N,) uint8 output ``raw`` (1:
+    occluded).  ``check()`` waits for the query and raises when it abandoned a mesh search (the answers are then not
+    to be used); ``fallback_rays()`` is how many rays the exact unbounded fallback answered (rtmi_occluded's
+    d_counts[1])."""
+
+    def __init__(self, raw, counts, rays):
+        import torch
+        self.raw, self.counts = raw, counts
+        self.mask = raw.view(torch.bool)
+        self._rays = rays  # (kept alive while the query may still read them)
+
+    def check(self):
+        n = int(self.counts[0].item())  # (a device-to-host copy: waits for the query)
+        if n:
+            raise RtmiError("rtmi_occluded abandoned %d mesh search(es): the answers are incomplete" % n)
+        return self
+
+    def fallback_rays(self):
+        return int(self.counts[1].item())
 
 
 class SceneBuilder:
@@ -374,6 +398,45 @@ class SceneBuilder:
         hits.raw, hits.abandoned = out, abandoned
         hits._rays = (origins, directions, t_max)  # (kept alive while the query may still read them)
         return hits
+
+    def occluded(self, origins, directions, t_max=None, out=None):
+        """Is anything in the way of each ray within t_max (rtmi_occluded), enqueued on torch's current stream.
+
+        The answer for ray i is exactly ``intersect(...).kind[i] != RTMI_HIT_NONE`` with the same t_max (Sky counts,
+        at t = 1e9; a NaN t_max is clear), found with t_max as a traversal bound and an early stop.  ``origins`` /
+        ``directions`` / ``t_max`` as for ``intersect``; ``out``: an optional (N,) uint8 or bool CUDA tensor to
+        write into.  Returns ``Occlusion``; call ``.check()`` on it before trusting the answers of a mesh scene."""
+        import torch
+        n = _check_rays(origins, "origins")
+        if _check_rays(directions, "directions") != n:
+            raise RtmiError("origins and directions differ in length")
+        if origins.device != directions.device:
+            raise RtmiError("origins and directions are on different devices")
+        dev = origins.device
+        if t_max is not None:
+            if not (isinstance(t_max, torch.Tensor) and t_max.is_cuda and t_max.dtype == torch.float32 and
+                    t_max.shape == (n,) and t_max.device == dev):
+                raise RtmiError("t_max must be a CUDA float32 tensor of shape (N,) on the rays' device")
+            t_max = t_max.contiguous()
+        if out is None:
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint8, torch.bool) and
+                  out.shape == (n,) and out.is_contiguous() and out.device == dev):
+            raise RtmiError("out must be a contiguous CUDA uint8 or bool tensor of shape (N,) on the rays' device")
+        if self.h.value is None or getattr(self, "device", None) is None:
+            raise RtmiError("scene not committed")
+        if dev != self.device:
+            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        origins, directions = origins.contiguous(), directions.contiguous()
+        raw = out.view(torch.uint8)
+        counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _check(self.L.rtmi_occluded(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                        C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
+                                        C.c_void_p(raw.data_ptr()), C.c_void_p(counts.data_ptr()), stream),
+                   "rtmi_occluded")
+        return Occlusion(raw, counts, (origins, directions, t_max))
 
 
 def _check_rays(a, what):
