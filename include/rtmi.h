@@ -190,7 +190,8 @@ int rtmi_rng_get_state(const rtmi_frame *f, const void *d_states, int64_t q, uin
 int rtmi_render(const rtmi_scene *s, const rtmi_frame *f, void *d_states, float *d_tiles,
                 uint32_t *d_ray_counts, void *stream);
 /* Did the render complete?  Waits for `stream`, then returns RTMI_OK, or RTMI_ERR_INTERNAL when the render
- * abandoned a mesh search (the frame is then incomplete and must not be used).  `d_scratch`: the
+ * abandoned a mesh search, over both launches of a resumed frame (the frame is then incomplete and must not be
+ * used).  `d_scratch`: the
  * rtmi_render_opts.d_scratch that call was given, or NULL for a call without one (the most recent such call on
  * this scene).  out_rays (nullable) receives the call's total of closest-hit queries.  The reference has no
  * counterpart: its CHECKs abort (utils.cu:164-166). */
@@ -200,7 +201,9 @@ int rtmi_last_ray_total(const rtmi_scene *s, uint64_t *out_rays, void *stream);
 /* Diagnostic: the raw device counter words of a render ([0] work-queue head, [1] closest-hit queries,
  * [2] abandoned mesh searches, [3] head-queue cursor; a -DRTMI_STATS build of the kernels adds wave-level
  * step counts of the mesh search from word 4 on; a -DRTMI_CHECK_MARGINS build counts, in [33] / [34], the
- * sampled queries it re-did without the cull and the disagreements it found). */
+ * sampled queries it re-did without the cull and the disagreements it found).  [2], [33] and [34] count over
+ * both launches of a resumed frame (a first pass the frame keeps, then the rest); the other words are the last
+ * launch's, whose [1] is still the whole frame's total because a resumed pixel carries its count on. */
 #define RTMI_COUNTER_WORDS 40
 int rtmi_debug_counters(const rtmi_scene *s, unsigned long long out[RTMI_COUNTER_WORDS], void *stream);
 int rtmi_debug_counters_ex(const rtmi_scene *s, const void *d_scratch, unsigned long long out[RTMI_COUNTER_WORDS],

@@ -998,6 +998,13 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
     if (first_prio) probe_plan.prio_tab = plan.prio_tab;
     HIP_TRY(launch_render(variant, s->dev, probe, first_states, d_tiles, first_rays, counters, probe_plan, true, blocks,
                           threads, tune, params, st));
+#ifdef RTMI_CHECK_MARGINS
+    // Test hook of the check build: RTMI_CHECK_PLANT_ABANDONED=1 (read once) counts one abandoned mesh search after every
+    // first pass the frame keeps.  No world makes the search abandon one (mesh_search.h), and a test has to see that
+    // rtmi_render_status still reports it after the second launch (tests/test_gpu_first_pass_status.py).
+    static const bool plant_abandoned = env_int("RTMI_CHECK_PLANT_ABANDONED", 0) != 0;
+    if (plant_abandoned && resume) HIP_TRY(launch_add_one(counters + 2, st));
+#endif
     if (first_prio) HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
     if (resume) {
       // The scheduler's kernels read the first pass's ray counts and MARK the head's pixels in them (bit 31), and the
@@ -1037,7 +1044,24 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
       }
     }
   }
-  HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
+  // The counter words (render_body.h, mesh_search.h; rtmi_debug_counters) before the launch that finishes the frame:
+  //   [0]       work-queue cursor                                   zeroed (per launch)
+  //   [1]       closest-hit queries                                 zeroed (a resumed pixel re-adds its whole count)
+  //   [2]       abandoned mesh searches (rtmi_render_status)        kept after a first pass the frame keeps
+  //   [3]       head-queue cursor                                   zeroed (per launch)
+  //   [4..32]   -DRTMI_STATS wave step counts and cycles            zeroed (per launch)
+  //   [33] [34] -DRTMI_CHECK_MARGINS queries re-done, disagreements kept after a first pass the frame keeps
+  //   [35] [36] planned chains: SIMD arrival, take-over cursor      zeroed (per launch)
+  //   [37..39]  unused                                              zeroed
+  // So a resumed frame reports in [2], [33] and [34] over both launches.  Otherwise every word is zeroed: a discarded
+  // probe's samples are not in the image.
+  if (mode.resume) {
+    HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(counters + 3, 0, 30 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(counters + 35, 0, (RTMI_COUNTER_WORDS - 35) * sizeof(unsigned long long), st));
+  } else {
+    HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
+  }
   HIP_TRY(launch_render(variant, s->dev, first, reinterpret_cast<uint32_t *>(d_states), d_tiles, ray_buf, counters,
                         plan, false, blocks, threads, tune, params + render_params_bytes(), st));
   return RTMI_OK;

@@ -114,6 +114,9 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif
+#ifdef RTMI_CHECK_MARGINS
+hipError_t launch_add_one(unsigned long long *d_word, hipStream_t stream);  // *d_word += 1 (check builds' test hook)
+#endif
 // d_bad[4]: see arithmetic_selftest in kernels.hip.
 hipError_t launch_arithmetic_selftest(unsigned long long *d_bad, hipStream_t stream);
 

@@ -541,6 +541,13 @@ hipError_t launch_arithmetic_selftest(unsigned long long *d_bad, hipStream_t str
   hipLaunchKernelGGL(arithmetic_selftest, dim3(4096), dim3(256), 0, stream, d_bad, -1.f, 1.f, 0.f, 1.f);
   return hipGetLastError();
 }
+#ifdef RTMI_CHECK_MARGINS
+__global__ void add_one_kernel(unsigned long long *word) { atomicAdd(word, 1ull); }
+hipError_t launch_add_one(unsigned long long *d_word, hipStream_t stream) {
+  hipLaunchKernelGGL(add_one_kernel, dim3(1), dim3(1), 0, stream, d_word);
+  return hipGetLastError();
+}
+#endif
 
 // ------------------------------------------------------------------ launchers
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
