@@ -49,13 +49,17 @@ typedef enum rtmi_status {
   RTMI_ERR_INVALID = -1,    /* bad argument / scene not committed / handle out of range */
   RTMI_ERR_NO_DEVICE = -2,  /* HIP runtime or device unavailable */
   RTMI_ERR_HIP = -3,        /* a HIP call failed; see rtmi_last_error() */
-  RTMI_ERR_CAPACITY = -4,   /* HitableList::kMaxHitables (1024) exceeded, hitable_list.cuh:10 */
+  RTMI_ERR_CAPACITY = -4,   /* HitableList::kMaxHitables (1024) exceeded, hitable_list.cuh:10; or a scene of more than */
+                            /* RTMI_MAX_MATERIALS materials committed */
   RTMI_ERR_DEPTH = -5,      /* max_depth outside [0, RTMI_MAX_DEPTH] */
   RTMI_ERR_INTERNAL = -6    /* an internal invariant of the kernels did not hold; the output is not to be used */
 } rtmi_status;
 
 #define RTMI_MAX_DEPTH 64      /* TRACE_DEPTH_LIMIT is 10 in ray_tracing.cu:10; BASELINE configs use 8/10/50 */
 #define RTMI_MAX_HITABLES 1024 /* hitable_list.cuh:10 */
+/* Materials of one scene (the reference has no limit).  World-list triangles and parallelograms carry their material
+ * in a 24-bit field, so rtmi_scene_commit refuses a scene with more materials with RTMI_ERR_CAPACITY. */
+#define RTMI_MAX_MATERIALS (1 << 24)
 
 typedef struct rtmi_scene rtmi_scene; /* opaque; replaces the device-resident HitableList + Camera pair */
 

@@ -383,6 +383,9 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
   Scene *s = S(sp);
   if (s->list_counts.size() != 1) return fail(RTMI_ERR_INVALID, "a nested list is still open (rtmi_list_end missing)");
+  static_assert(RTMI_MAX_MATERIALS == kMaxMats, "rtmi.h and scene_dev.h disagree on the material limit");
+  if (s->mats.size() > (size_t)RTMI_MAX_MATERIALS)
+    return fail(RTMI_ERR_CAPACITY, "more than RTMI_MAX_MATERIALS (2^24) materials: a triangle's material field has 24 bits");
   if (rtmi_device_count() <= 0) return fail(RTMI_ERR_NO_DEVICE, "no HIP device: librtmi has no CPU fallback");
   free_device(s);
   std::string err = s->flatten();

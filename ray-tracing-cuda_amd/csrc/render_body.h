@@ -7,7 +7,8 @@
 // The id stack is laid out [depth][thread] so the lanes of a wave touch consecutive
 // bytes; entries are 4 bits when there are at most 16 materials (two levels per byte, lc.wide_ids == 2:
 // half the LDS, which is what lets a sixth wave per SIMD of the list kernel in at depth 50), uint8 when
-// every material id fits a byte, else uint16 (lc.wide_ids == 1).
+// every material id fits a byte, else uint16 (lc.wide_ids == 1).  A scene of more than 65536 materials is rendered by
+// the image-textured variants (scene.hip: flatten), whose 32-bit layer words hold any material id.
 struct LaunchCfg {
   int32_t lds_mats;    // materials staged in LDS (0: read them from global memory)
   int32_t wide_ids;    // 0: uint8 stack entries, 1: uint16, 2: 4-bit (two levels per byte)

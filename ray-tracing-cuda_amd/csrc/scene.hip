@@ -590,6 +590,9 @@ std::string Scene::flatten() {
     }
     mat_recs.push_back(r);
   }
+  // The id stack of the untextured variants holds at most 16-bit material ids (render_body.h).  A scene with more
+  // materials renders with the image-textured variants, whose layer word is 32 bits: the id of any material.
+  if (mats.size() > (size_t)kMaxStackMats) features |= F_TEX;
 
   // Run::count is in records for spheres / BVHs and in record PAIRS for RUN_TRIS.
   auto push_run = [&](int kind, int first) {
@@ -601,6 +604,7 @@ std::string Scene::flatten() {
     }
   };
   auto check_mat = [&](int m) { return m >= 0 && m < (int)mats.size(); };
+  if (mats.size() > (size_t)kMaxMats) return "more than 2^24 materials (TriNrm::mat_flags)";
 
   bytes_per_ray = 32;  // material / hit-record share per query
   for (const HostObj &ob : world) {
@@ -905,12 +909,15 @@ std::string Scene::check_margins() const {
         return "margin budget: a sphere group's bounds do not cover what its members' pre-tests can accept";
   }
   for (size_t b = 0; b < bvh_recs.size(); b++) {
+    // this mesh's search tree: its nodes lie in [sub_root, next mesh's sub_root) (flatten appends them root first)
+    const size_t n_lo = (size_t)bvh_recs[b].sub_root;
+    const size_t n_hi = b + 1 < bvh_recs.size() ? (size_t)bvh_recs[b + 1].sub_root : qnodes.size();
     for (int i = 0; i < kTopEntries; i++) {
       const BvhNode &t = tops[b * kTopEntries + (size_t)i];
       if (t.left == -1) continue;
       // the entry stands for child `t.left` of some node of this mesh's search tree: find the parent's box for it
       bool found = false;
-      for (size_t n = 0; n < qnodes.size() && !found; n++)
+      for (size_t n = n_lo; n < n_hi && !found; n++)
         for (int c = 0; c < 4 && !found; c++)
           if (qnodes[n].child[c] == t.left) {
             found = true;

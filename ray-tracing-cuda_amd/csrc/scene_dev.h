@@ -98,6 +98,8 @@ struct alignas(16) TriNrm {
   float n[3];
   int32_t mat_flags;
 };
+constexpr int kMaxStackMats = 1 << 16;  // materials whose ids the uint16 id stack holds (render_body.h, LaunchCfg::wide_ids)
+constexpr int kMaxMats = 1 << 24;  // materials of a scene: TriNrm::mat_flags holds 24 bits of one (== RTMI_MAX_MATERIALS)
 constexpr int kCullMinPairs = 4;  // shorter lists are scanned plainly: the cull and the hand-over through LDS cost more than they save
 // (ray, pair) / (ray, group) / (ray, sphere) tasks of the shared candidate tests that one wave holds in LDS at a time.
 // The capacity decides how many workgroups a CU's LDS holds, so it is per variant: the plain list kernel (six waves per

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("RTMI_LIB_PATH") or os.path.join(_ROOT, "lib", "librtm
 TILE = 8
 STATE_WORDS = 6
 MAX_DEPTH = 64
+MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
 
 # rtmi_hit.kind (include/rtmi.h)
 RTMI_HIT_NONE = 0

@@ -91,6 +91,16 @@ def _f3(v):
     return np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1))
 
 
+def default_threads():
+    """Render threads of the oracle: OMP_NUM_THREADS where it is set, else the CPUs this process may run on, at most
+    16 (a shared machine's os.cpu_count() can be many times what one command is given)."""
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    return max(1, min(16, n))
+
+
 def rng_init(seed, n, first=0):
     """(n, 6) uint32 array of compact XORWOW states {d, v0..v4} for pixels first..first+n."""
     st = np.zeros((n, 6), dtype=np.uint32)
@@ -240,7 +250,7 @@ class OracleBuilder:
             pixel_ids = np.ascontiguousarray(pixel_ids, dtype=np.int32)
             ids_p, n_ids = pixel_ids.ctypes.data_as(C.POINTER(C.c_int32)), pixel_ids.size
         if threads is None:
-            threads = os.cpu_count() or 1
+            threads = default_threads()
         total = self.L.orc_render(self.h, height, width, spp, max_depth, 1 if post else 0,
                                   states.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(rgb),
                                   rays.ctypes.data_as(C.POINTER(C.c_uint32)), ids_p, n_ids, threads)
