@@ -405,6 +405,42 @@ int rtmi_occluded(const rtmi_scene *s, int64_t n, const float *d_origins, const 
  * the reference's own tree walk), then the filter; d_check (nullable, device, two words) += {rays re-done,
  * disagreements}. */
 
+/* ------------------------------------------------------------------ trace --
+ * Path-traced radiance of rays the caller made: Trace(world, Ray(o, d), &state, max_depth) (ray_tracing.cu:12-54),
+ * the loop a render runs for every sample, bit for bit as a render runs it -- for panoramic, fisheye or per-texel
+ * cameras, light probes, or a re-render of chosen rays with chosen RNG states.  Added without a version change: a
+ * caller detects it by the symbol rtmi_trace.
+ *
+ * d_radiance[i] = Trace(world, Ray(o_i, d_i), &state_i, max_depth), raw: the unprocessed estimate a render keeps for
+ * one sample before post-processing (no division, clamp or sqrt).
+ *   - Directions: Ray(o, d) normalises d once, as for rtmi_intersect.  A camera ray of RayAt (which normalises too)
+ *     is therefore reproduced by handing in the normalised direction.
+ *   - n rays: origins and directions float[n][3], d_radiance float[n][3] (device).  n <= 2^31 - 1.
+ *   - max_depth in [0, RTMI_MAX_DEPTH], else RTMI_ERR_DEPTH.
+ *   - d_states: RTMI_STATE_WORDS planes of uint32[n] (the struct-of-arrays layout of rtmi_states_bytes, with n as the
+ *     stride; rtmi_rng_init_n seeds them).  Each state is advanced in place by exactly the draws Trace makes (the
+ *     Scatter of Lambertian, Metal and Dielectric), in the reference's order; no camera draws are made.
+ *   - d_ray_counts (nullable, uint32[n]): each ray's closest-hit queries (Trace's ray_count), at most max_depth + 1.
+ *   - A ray with a non-finite origin or direction, or a direction that does not normalise, is left out as in
+ *     rtmi_intersect: radiance 0, count 0, state untouched; no other answer changes.
+ *   - d_work (required, device, RTMI_TRACE_WORK_WORDS unsigned long long words, 8-byte aligned): the call's own
+ *     device state, reset on `stream` before the launch.  After the call [0] holds the abandoned mesh searches (the
+ *     answers are exact only while it is 0, as with rtmi_intersect's d_abandoned) and [1] the closest-hit queries of
+ *     all rays.  The rest is the kernel's: its work cursor, and the kernel's argument block (read by scalar loads,
+ *     which is why d_work is larger than the counters) -- so the call shares no device state with renders or with
+ *     other queries on the scene.  A d_work must not be reused before the call that holds it has finished.
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call for a null or uncommitted scene, n < 0, n above
+ * 2^31 - 1, or a null array with n > 0 (d_ray_counts excepted); then also when the current device is not the one
+ * the scene was committed on.  n == 0 launches nothing and leaves d_work as it is. */
+#define RTMI_TRACE_WORK_WORDS 256
+int rtmi_trace(const rtmi_scene *s, int64_t n, const float *d_origins, const float *d_dirs, int max_depth,
+               void *d_states, float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream);
+/* curand_init(seed, first + i, 0, &state_i) for i in [0, n), into RTMI_STATE_WORDS planes of uint32[n] (the layout
+ * rtmi_trace reads): n trace states seeded on the device.  The device's jump tables cover subsequences below 2^40,
+ * so first + n > 2^40 is RTMI_ERR_INVALID, as are n < 0, n above 2^31 - 1 and null d_states with n > 0.
+ * Asynchronous on `stream`; n == 0 launches nothing. */
+int rtmi_rng_init_n(uint64_t seed, uint64_t first, int64_t n, void *d_states, void *stream);
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

@@ -546,6 +546,22 @@ int rtmi_rng_init(uint64_t seed, const rtmi_frame *f, void *d_states, void *stre
   HIP_TRY(launch_rng_init(seed, d, jump, reinterpret_cast<uint32_t *>(d_states), (hipStream_t)stream));
   return RTMI_OK;
 }
+int rtmi_rng_init_n(uint64_t seed, uint64_t first, int64_t n, void *d_states, void *stream) {
+  // the device jump tables cover subsequences below 2^40 (xorwow.h: kJumpBits)
+  // (and n below 2^31 as for rtmi_trace: one state per lane of a one-dimensional grid)
+  if (n < 0 || n > (int64_t)INT32_MAX || (n > 0 && !d_states) || first > (1ull << kJumpBits) ||
+      (uint64_t)n > (1ull << kJumpBits) - first)
+    return fail(RTMI_ERR_INVALID, "bad rng_init_n arguments (n < 0, n above 2^31 - 1, first + n above 2^40, or null states)");
+  if (n == 0) return RTMI_OK;
+  if (rtmi_device_count() <= 0) return fail(RTMI_ERR_NO_DEVICE, "no HIP device: librtmi has no CPU fallback");
+  uint32_t *jump = nullptr;
+  int rc = device_jump(&jump);
+  if (rc) return rc;
+  FrameDev d{};
+  d.items = n;
+  HIP_TRY(launch_rng_init(seed, d, jump, reinterpret_cast<uint32_t *>(d_states), (hipStream_t)stream, (int64_t)first));
+  return RTMI_OK;
+}
 int rtmi_rng_host_state(uint64_t seed, uint64_t subsequence, uint32_t state[RTMI_STATE_WORDS]) {
   if (!state) return fail(RTMI_ERR_INVALID, "null state");
   Rng r = host_rng_init(seed, subsequence);
@@ -904,6 +920,42 @@ int rtmi_occluded_check_counts(const rtmi_scene *s, int64_t n, const float *d_or
   return occluded(s, n, d_origins, d_dirs, d_t_max, d_occluded, d_counts, d_check, stream);
 }
 #endif
+
+// ------------------------------------------------------------------ radiance of caller rays
+int rtmi_trace(const rtmi_scene *sp, int64_t n, const float *d_origins, const float *d_dirs, int max_depth,
+               void *d_states, float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
+  // (argument checks first, without a HIP call: the host never reads the rays)
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 rays");
+  if (n > 0 && (!d_origins || !d_dirs || !d_states || !d_radiance || !d_work))
+    return fail(RTMI_ERR_INVALID, "null ray, state, radiance or work array");
+  const Scene *s = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if (max_depth < 0 || max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  if (n == 0) return RTMI_OK;
+  int n_cu = 0;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_cus.find(dev);
+    if (it == g_cus.end()) {
+      hipDeviceProp_t prop;
+      HIP_TRY(hipGetDeviceProperties(&prop, dev));
+      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
+    }
+    n_cu = it->second;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the counter words (abandoned searches, queries, queue cursor) start from zero; the argument block behind them is
+  // written by launch_trace
+  HIP_TRY(hipMemsetAsync(d_work, 0, kTraceParamsOffset, st));
+  HIP_TRY(launch_trace(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, n, max_depth, d_origins, d_dirs,
+                       reinterpret_cast<uint32_t *>(d_states), d_radiance, d_ray_counts, d_work, st));
+  return RTMI_OK;
+}
 
 int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream) {

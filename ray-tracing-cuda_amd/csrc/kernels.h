@@ -12,8 +12,9 @@ namespace rtmi {
 
 int64_t frame_pixel_of(const FrameDev &fr, int rank, int64_t q);
 
+// first >= 0: fr.items states of subsequences first, first + 1, ... (rtmi_rng_init_n) instead of the frame's pixels
 hipError_t launch_rng_init(uint64_t seed, const FrameDev &fr, const uint32_t *d_jump, uint32_t *d_states,
-                           hipStream_t stream);
+                           hipStream_t stream, int64_t first = -1);
 
 // Kernel specialisation covering a feature set, its occupancy, and its launch.
 uint32_t pick_variant(uint32_t features);
@@ -111,6 +112,15 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
                             float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream);
+// Radiance of caller rays (rtmi_trace; kernels.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
+// words, zeroed in stream order before the call -- [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's
+// cursor, and from byte kTraceParamsOffset the kernel's argument block (written in stream order just before the launch).
+constexpr size_t kTraceParamsOffset = 256;  // (a 128-byte line of its own, away from the counter words)
+// tex_layers: the scene's features hold F_TEX (image textures, or more materials than the 16-bit id stack holds); without
+// it the F_TEX kernel keeps the untextured id stack.
+hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
+                        const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
+                        uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

@@ -68,15 +68,16 @@ __host__ __device__ __forceinline__ int64_t frame_pixel_of_rank(const FrameDev &
 int64_t frame_pixel_of(const FrameDev &fr, int rank, int64_t q) { return frame_pixel_of_rank(fr, rank, q); }
 
 // ------------------------------------------------------------------ RNG init
-// state(q) = seed scramble, then v <- A^(idx * 2^67) v, idx = global pixel index.
+// state(q) = seed scramble, then v <- A^(idx * 2^67) v, idx = global pixel index -- or, first >= 0 (rtmi_rng_init_n:
+// fr.items states, no frame), idx = first + q.
 // The jump matrix for bit k is wave-uniform -> scalar loads; lanes whose bit is
 // clear keep their vector.
-__global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev fr,
+__global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev fr, int64_t first,
                                                         const uint32_t *__restrict__ jump,
                                                         uint32_t *__restrict__ states) {
   int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= fr.items) return;
-  int64_t idx = frame_pixel_of_rank(fr, fr.rank, q);
+  int64_t idx = first >= 0 ? first + q : frame_pixel_of_rank(fr, fr.rank, q);
   uint64_t sub = idx < 0 ? 0 : (uint64_t)idx;
   Rng s = rng_seed(seed);
   uint32_t v0 = s.v0, v1 = s.v1, v2 = s.v2, v3 = s.v3, v4 = s.v4;
@@ -174,6 +175,25 @@ template <uint32_t F>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void probe_kernel(const RenderParams *p) {
   const RenderParams *kp = (const RenderParams *)(const RT_CONSTANT RenderParams *)(uintptr_t)p;
   render_body<F>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
+}
+// rtmi_trace: the same body in its caller-ray mode, its argument block read the render's way (constant address space)
+// from the call's own d_work, behind the kernel's counter words (launch_trace).
+struct TraceParams {
+  RenderParams rp;
+  const float *origins, *dirs;
+  int32_t tex_layers;  // 0: the scene samples no image texture, its layers are material ids (render_body.h)
+};
+static_assert(kTraceParamsOffset + sizeof(TraceParams) <= (size_t)RTMI_TRACE_WORK_WORDS * 8u,
+              "RTMI_TRACE_WORK_WORDS must hold the trace kernel's argument block");
+static_assert(kTraceParamsOffset % alignof(TraceParams) == 0, "the argument block is aligned in d_work");
+__global__ void trace_params_write_kernel(TraceParams p, TraceParams *dst) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
+}
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void trace_kernel(const TraceParams *p) {
+  const TraceParams *kp = (const TraceParams *)(const RT_CONSTANT TraceParams *)(uintptr_t)p;
+  render_body<F, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
+                       kp->origins, kp->dirs, kp->tex_layers != 0);
 }
 
 // ------------------------------------------------------------------ untile / post
@@ -553,9 +573,9 @@ hipError_t launch_add_one(unsigned long long *d_word, hipStream_t stream) {
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 hipError_t launch_rng_init(uint64_t seed, const FrameDev &fr, const uint32_t *d_jump, uint32_t *d_states,
-                           hipStream_t stream) {
+                           hipStream_t stream, int64_t first) {
   if (fr.items == 0) return hipSuccess;
-  hipLaunchKernelGGL(rng_init_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, seed, fr, d_jump,
+  hipLaunchKernelGGL(rng_init_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, seed, fr, first, d_jump,
                      d_states);
   return hipGetLastError();
 }
@@ -570,8 +590,9 @@ static bool plain_list_scan() {
 }
 
 // id_stack = false (query kernels): no stack of material ids, whatever fr.max_depth says.
+// tex_layers = false (trace kernels of scenes without image textures): an F_TEX variant with the untextured id stack.
 static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, size_t *lds_bytes,
-                          bool mats_in_lds = true, bool id_stack = true) {
+                          bool mats_in_lds = true, bool id_stack = true, bool tex_layers = true) {
   LaunchCfg lc{};
   lc.threads = threads;
   lc.tile_order = nullptr;
@@ -581,7 +602,7 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   lc.stack_off = (int32_t)off;
   const size_t levels = (size_t)(fr.max_depth > 0 ? fr.max_depth : 1);
   // image-textured variants: one 32-bit word per level (material id, or the sampled texel)
-  size_t stack = (variant & F_TEX) ? levels * threads * 4 : (lc.wide_ids == 2 ? (levels + 1) / 2 : levels) * threads * (lc.wide_ids == 1 ? 2 : 1);
+  size_t stack = (variant & F_TEX) && tex_layers ? levels * threads * 4 : (lc.wide_ids == 2 ? (levels + 1) / 2 : levels) * threads * (lc.wide_ids == 1 ? 2 : 1);
   if (!id_stack) stack = 0;
   size_t noff = (off + stack + 15) & ~(size_t)15;
   lc.nodes_off = (int32_t)noff;
@@ -610,7 +631,7 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   // of the fourth workgroup stays in global memory -- measured on spheres 1024^2: 7.6 -> 8.5 Grays/s.
   if (groups && mats_in_lds && lc.lds_mats > 0 && *lds_bytes * (size_t)(1024 / threads) > 160 * 1024) {
     size_t without = 0;
-    const LaunchCfg alt = make_cfg(variant, sc, fr, threads, &without, false, id_stack);
+    const LaunchCfg alt = make_cfg(variant, sc, fr, threads, &without, false, id_stack, tex_layers);
     if (without * (size_t)(1024 / threads) <= 160 * 1024) {
       *lds_bytes = without;
       return alt;
@@ -942,6 +963,76 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
   if (variant == (uint32_t)(V)) \
     return launch_occlusion_t<(V)>(sc, near_lo, near_hi, near_short, n_cu, n, d_o, d_d, d_t_max, d_occluded, \
                                    d_counts, d_check, stream);
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------ radiance of caller rays (rtmi_trace)
+// render_body.h in its caller-ray mode on the query variants (F_TEX always: the layer stack is one 32-bit word per level,
+// the material id or the sampled texel).  A persistent grid sized by occupancy; the lanes refill from the call's own
+// queue cursor (d_work[2]) as their paths end, a batch per wave per atomic.
+template <uint32_t F>
+static int trace_occupancy_t(const SceneDev &sc, const FrameDev &fr, int threads, bool tex_layers, size_t *lds) {
+  (void)make_cfg(F, sc, fr, threads, lds, true, true, tex_layers);
+  if (*lds > 160 * 1024) return 0;
+  if (*lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(trace_kernel<F>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
+    return 0;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<F>, threads, *lds) != hipSuccess) nb = 0;
+  return nb;
+}
+
+template <uint32_t F>
+static hipError_t launch_trace_t(const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth, const float *d_o,
+                                 const float *d_d, uint32_t *d_states, float *d_radiance, uint32_t *d_ray_counts,
+                                 unsigned long long *d_work, hipStream_t stream) {
+  FrameDev fr{};
+  fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
+  fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
+  fr.items = n;
+  // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
+  // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
+  int threads = 0, per_cu = 0;
+  for (int t = 256; t >= 64; t /= 2) {
+    size_t lds_t = 0;
+    const int nb = trace_occupancy_t<F>(sc, fr, t, tex_layers, &lds_t);
+    if (t * nb > threads * per_cu) threads = t, per_cu = nb;
+  }
+  if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
+  size_t lds = 0;
+  LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
+  lc.lane_stride = 1;
+  lc.fetch_batch = 64;  // (the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
+  lc.rate_scale = 1.f;
+  {  // render_body.h reads LDS by byte offset (lds_byte, the id stack): right only while the kernel declares no static LDS
+    static const hipError_t lds_ok = [] {
+      hipFuncAttributes a{};
+      hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(trace_kernel<F>));
+      if (e != hipSuccess) return e;
+      return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
+    }();
+    if (lds_ok != hipSuccess) return lds_ok;
+  }
+  const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
+  const int blocks = (int)(want < cap ? want : cap);
+  TraceParams tp;
+  tp.rp.sc = sc, tp.rp.fr = fr, tp.rp.lc = lc;
+  tp.rp.states = d_states, tp.rp.out = d_radiance, tp.rp.ray_counts = d_ray_counts, tp.rp.counters = d_work;
+  tp.origins = d_o, tp.dirs = d_d, tp.tex_layers = tex_layers ? 1 : 0;
+  TraceParams *dp = reinterpret_cast<TraceParams *>(reinterpret_cast<char *>(d_work) + kTraceParamsOffset);
+  hipLaunchKernelGGL(trace_params_write_kernel, dim3(1), dim3(64), 0, stream, tp, dp);
+  hipLaunchKernelGGL(trace_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const TraceParams *)dp);
+  return hipGetLastError();
+}
+
+hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
+                        const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
+                        uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
+#define X(V) \
+  if (variant == (uint32_t)(V)) \
+    return launch_trace_t<(V)>(sc, tex_layers, n_cu, n, max_depth, d_o, d_d, d_states, d_radiance, d_ray_counts, d_work, stream);
   RTMI_FOR_EACH_QUERY_VARIANT(X)
 #undef X
   return hipErrorInvalidValue;

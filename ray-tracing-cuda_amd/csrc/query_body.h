@@ -94,10 +94,6 @@ __device__ __forceinline__ QueryHit resolve_hit(const SceneDev &sc, const QueryD
   return r;
 }
 
-__device__ __forceinline__ bool finite3(V3 v) {
-  return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
-}
-
 template <uint32_t F>
 __device__ __forceinline__ void query_body(const QueryParams &qp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -1,5 +1,9 @@
 // The persistent per-pixel trace loop.  Included by kernels.hip inside namespace rtmi, after closest_hit.h
 // (not a stand-alone header).
+//
+// render_body<F, RAYS>: RAYS = false is the render (render_kernel, probe_kernel); RAYS = true is rtmi_trace
+// (trace_kernel): work item q is the caller's ray q instead of a pixel, traced once from the ray it is given -- no
+// camera, no jitter -- with the same bounce, shading, layer stack and fold, one copy of them for both.
 #pragma once
 
 // ================================================================== trace kernel
@@ -120,11 +124,22 @@ __device__ __forceinline__ void wave_priority_leave(uint32_t *tab) {
     __hip_atomic_store(tab + row * 16u + (hw & 15u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <uint32_t F>
+__device__ __forceinline__ bool finite3(V3 v) {
+  return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
+}
+
+// RAYS (rtmi_trace): fr.items rays, fr.spp = 1, fr.k_begin = 0, fr.k_end = 1, fr.post = 0; ray_o / ray_d float[items][3];
+// counters is the call's d_work: [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's cursor (a
+// render's counters hold the cursor in [0] and the abandoned searches in [2]).  The list queue serves every variant.
+// tex_layers (RAYS only): false keeps the untextured id stack in an F_TEX variant -- for scenes without image textures,
+// whose layers are material ids (launch_trace: a quarter or less of the 32-bit layer words' LDS).
+template <uint32_t F, bool RAYS = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
-                                            unsigned long long *__restrict__ counters) {
+                                            unsigned long long *__restrict__ counters,
+                                            const float *__restrict__ ray_o = nullptr,
+                                            const float *__restrict__ ray_d = nullptr, bool tex_layers = true) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   MatRec *s_mats = reinterpret_cast<MatRec *>(smem);
   // id stack: byte offset of entry [level][thread] in LDS, kept as 32-bit arithmetic (pointer
@@ -216,6 +231,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // (round 2 kept 64 x 3 floats of private memory per lane for this: 8.2 TB of scratch traffic per launch of a C5
   // shard, 43 % of the waves' time spent waiting.)  Image-textured scenes: a layer is one 32-bit word in LDS,
   // [level][thread] -- the material id, or bit 31 + the sampled texel's three bytes (trace_helpers.h: tex_fetch).
+  const bool tex32 = (F & F_TEX) && (!RAYS || tex_layers);  // the layer stack holds 32-bit words (else material ids)
   auto tex_layer_offset = [&](int level) -> uint32_t {
     return (uint32_t)lc.stack_off + (((uint32_t)level * n_threads + threadIdx.x) << 2);
   };
@@ -250,13 +266,27 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   auto take_item = [&](int64_t item) -> bool {  // false: ragged-tile padding (or nothing to sample), written as black
     q32 = (int32_t)item;
     const int64_t q = item;
-    int64_t idx = frame_pixel_of_rank(fr, fr.rank, q);
+    if constexpr (RAYS) {  // the caller's ray q, left out as rtmi_intersect leaves it out (query_body.h)
+      const V3 ro = mk(ray_o[q * 3 + 0], ray_o[q * 3 + 1], ray_o[q * 3 + 2]);
+      const V3 rd = mk(ray_d[q * 3 + 0], ray_d[q * 3 + 1], ray_d[q * 3 + 2]);
+      bool live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
+      V3 nd = splat(0.f);
+      if (live) nd = unit3_rn(rd);  // Ray's constructor (ray.cu:8-10)
+      live = live && finite3(nd) && (nd.x != 0.f || nd.y != 0.f || nd.z != 0.f);
+      if (!live) {  // radiance 0, count 0, state untouched
+        out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
+        if (ray_counts) ray_counts[q] = 0;
+        return false;
+      }
+      o = ro, d = nd;  // (the lane holds no path while it takes an item: o, d carry the ray to the path's start)
+    }
+    int64_t idx = RAYS ? 0 : frame_pixel_of_rank(fr, fr.rank, q);
     if (idx < 0 || fr.spp <= 0) {
       out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
       if (ray_counts) ray_counts[q] = 0;
       return false;
     }
-    pij = ((uint32_t)(idx / fr.width) << 16) | (uint32_t)(idx % fr.width);
+    if (!RAYS) pij = ((uint32_t)(idx / fr.width) << 16) | (uint32_t)(idx % fr.width);
     rng.d = states[0 * n_items + q];
     rng.v0 = states[1 * n_items + q];
     rng.v1 = states[2 * n_items + q];
@@ -290,7 +320,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // lane_stride lanes, so that every SIMD gets a wave and a wave's shared candidate tests serve 16 rays with 64 lanes
   // instead of 64 rays on a quarter of the SIMDs.  The idle lanes never fetch; they work in closest_hit.
   if (!(F & F_BVH) && lc.lane_stride > 1 && (threadIdx.x & (uint32_t)(lc.lane_stride - 1)) != 0u) done = true;
-  if (!(F & F_BVH) && lc.chain_next != nullptr) {  // planned chains: this wave's chain and its first tile
+  if (!RAYS && !(F & F_BVH) && lc.chain_next != nullptr) {  // planned chains: this wave's chain and its first tile
     const int chain = wave_chain_id(lc.prio_tab, counters + 35, lc.plan_simds, lc.plan_rounds);
     const int32_t t = chain >= 0 ? lc.chain_first[chain] : -1;
     heavy = t < 0;
@@ -346,9 +376,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       states[5 * n_items + q] = rng.v4;
       has_px = false;
     }
-    const bool wave_heavy = (F & F_BVH) && lc.exclusive &&
+    const bool wave_heavy = !RAYS && (F & F_BVH) && lc.exclusive &&
                             __builtin_amdgcn_ballot_w64(has_px && heavy && (active || k < fr.k_end)) != 0ull;
-    if ((F & F_BVH) && classes) {
+    if (!RAYS && (F & F_BVH) && classes) {
       const bool wants = !active && !done && !has_px;
       if (__builtin_amdgcn_ballot_w64(wants) != 0ull) {
         if (head_open)
@@ -396,7 +426,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
       }
-    } else if (!(F & F_BVH) && lc.chain_next != nullptr) {  // (wave-uniform) planned chains
+    } else if (!RAYS && !(F & F_BVH) && lc.chain_next != nullptr) {  // (wave-uniform) planned chains
       const uint32_t me = ((blockIdx.x * n_threads + threadIdx.x) >> 6) + 1u;  // this wave's mark in `claims`
       if (!active && !has_px && !heavy) {  // (`heavy` in this mode: the lane has walked its chain to the end)
         for (;;) {
@@ -428,9 +458,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           if (__builtin_amdgcn_ballot_w64(has_px) != 0ull) break;  // (a tile of padding only: look further)
         }
       }
-    } else if (!(F & F_BVH)) {
-      // The queue of a list frame, drawn by the WAVE: one atomic takes the next `batch` items for all its lanes, which
-      // help themselves from that pool as they finish their pixels.  Every atomic on the queue's cursor is a round
+    } else if (RAYS || !(F & F_BVH)) {
+      // The queue of a list frame (and of rtmi_trace's rays, every variant), drawn by the WAVE: one atomic takes the
+      // next `batch` items for all its lanes, which help themselves from that pool as they finish their pixels.  Every atomic on the queue's cursor is a round
       // trip to the one L2 channel that owns its line, and they are served there one after the other (5.5 ns each,
       // measured): with one per pixel a first pass of two samples over a million pixels was 3.8 ms of atomics around
       // 0.55 ms of rendering.  `batch` shrinks with what is left of the queue (at most half a wave's fair share of it),
@@ -449,7 +479,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
             batch = batch < 1u ? 1u : batch > (uint32_t)lc.fetch_batch ? (uint32_t)lc.fetch_batch : batch;
             const uint32_t asked = (uint32_t)__popcll(wm);  // (never less than the lanes that are waiting right now)
             batch = batch < asked ? asked : batch;
-            if ((threadIdx.x & 63u) == 0u) nq = atomicAdd(&counters[0], (unsigned long long)batch);
+            if ((threadIdx.x & 63u) == 0u) nq = atomicAdd(&counters[RAYS ? 2 : 0], (unsigned long long)batch);
             nq = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(nq >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((int)nq);
             if (nq < (unsigned long long)n_items) {
@@ -495,7 +525,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       }
     }
     if (!active && !done) {
-      if (has_px) {
+      if (RAYS && has_px) {  // the caller's ray, as take_item left it in o, d: no camera draws
+        k++;
+        depth = 0;
+        active = true;
+      } else if (has_px) {
         // ray_tracing.cu:68-74 + camera.cu:57-70
         float r1 = rng_01(rng);
         float r2 = rng_01(rng);
@@ -558,7 +592,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && ll != nullptr && sc.n_pairs >= kCullMinPairs) ||
                               ((F & F_SGROUP) && cands != nullptr);  // wave-uniform
     if (all_lanes_in)  // every lane goes in, with or without a ray of its own: see closest_hit
-      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + 2, o, d, active,
+      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (RAYS ? 0 : 2), o, d, active,
                          (F & F_BVH) && lc.visit_counts != nullptr
 #ifdef RTMI_STATS
                          , st
@@ -572,7 +606,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     // disagreement.  counters[33] += rays re-done, counters[34] += disagreements (rtmi_debug_counters).
     // Mesh variants: the second answer walks the reference's own tree (closest_hit.h: bvh_reference_walk), thousands
     // of triangle tests per ray -- for small frames (tools/gpu_check_margins.py).
-    if (all_lanes_in && (check_tick++ % RTMI_CHECK_EVERY) == 0u) {
+    if (!RAYS && all_lanes_in && (check_tick++ % RTMI_CHECK_EVERY) == 0u) {  // (rtmi_trace: d_work has no words 33, 34)
       const Hit h2 = closest_hit<F>(sc, s_nodes, 0, s_paths, 0, nullptr, nullptr, nullptr, nullptr, nullptr, o, d, active, false
 #ifdef RTMI_STATS
                                     , st
@@ -728,7 +762,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               if (scattered) nd = unit3_rn(nd);  // Ray's constructor
             }
             if (scattered) {
-              if (F & F_TEX) {
+              if (tex32) {
                 *reinterpret_cast<uint32_t *>(smem + tex_layer_offset(depth)) = layer;
               } else if (nibble_ids) {
                 const uint32_t at = ids_offset(depth >> 1);  // this lane's own byte: no other lane writes it
@@ -754,7 +788,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         // attenuation * result, deepest layer first.  The addition only matters for a product of -0,
         // which needs a colour with its sign bit set (sc.unsigned_colours).
         int i = depth - 1;
-        if (!(F & F_TEX) && fast_fold) {
+        if (!tex32 && fast_fold) {
           // common case (byte ids, material table in LDS, no signed colours) without the per-layer
           // uniform branches: four layers at a time, ids first, then colours, then the products.
           // The id bytes are read at a RUNNING byte offset that steps down a row at a time, as an LDS address proper
@@ -804,7 +838,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         }
         for (; i >= 0; i--) {
           V3 a;
-          if (F & F_TEX) {
+          if (tex32) {
             const uint32_t lw = *reinterpret_cast<const uint32_t *>(smem + tex_layer_offset(i));
             if (lw >> 31) {
               a = texel_rgb(lw);  // the same byte / 255 the sample would have returned
@@ -843,7 +877,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     if ((threadIdx.x & 63) == 0 && ray_total) atomicAdd(&counters[1], ray_total);
   }
 #ifdef RTMI_STATS
-  if ((threadIdx.x & 63) == 0) {
+  if (!RAYS && (threadIdx.x & 63) == 0) {  // (rtmi_trace: d_work has no statistics words)
     const unsigned v[13] = {wave_queries, st.searches, st.node_steps, st.face_steps, st.nodes_popped, st.blocks_popped,
                             st.insert_rounds, st.steps_hist[0], st.steps_hist[1], st.steps_hist[2], st.steps_hist[3],
                             st.steps_hist[4], st.steps_hist[5]};

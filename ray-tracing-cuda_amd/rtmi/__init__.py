@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("RTMI_LIB_PATH") or os.path.join(_ROOT, "lib", "librtm
 TILE = 8
 STATE_WORDS = 6
 MAX_DEPTH = 64
+TRACE_WORK_WORDS = 256  # RTMI_TRACE_WORK_WORDS: the device words of one rtmi_trace call
 MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
 
 # rtmi_hit.kind (include/rtmi.h)
@@ -138,6 +139,9 @@ SYMBOLS = [
                                  C.c_void_p]),
     ("rtmi_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
+    ("rtmi_trace", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p]),
+    ("rtmi_rng_init_n", C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -225,6 +229,44 @@ class Occlusion:
 
     def fallback_rays(self):
         return int(self.counts[1].item())
+
+
+class Trace:
+    """What ``SceneBuilder.trace`` returns: ``rgb`` (N, 3) float32, each ray's raw radiance estimate (no
+    post-processing); ``rays`` (N,) int32 closest-hit queries per ray, or None when they were not asked for; ``work``
+    the call's (RTMI_TRACE_WORK_WORDS,) int64 device words.  ``check()`` waits for the call and raises when it abandoned
+    a mesh search (the answers are then not to be used); ``total_rays()`` is the queries of all rays."""
+
+    def __init__(self, rgb, rays, work, keep):
+        self.rgb, self.rays, self.work = rgb, rays, work
+        self._keep = keep  # (kept alive while the call may still read them)
+
+    def check(self):
+        n = int(self.work[0].item())  # (a device-to-host copy: waits for the call)
+        if n:
+            raise RtmiError("rtmi_trace abandoned %d mesh search(es): the answers are incomplete" % n)
+        return self
+
+    def total_rays(self):
+        return int(self.work[1].item())
+
+
+def rng_states(seed, n, first=0, device=None):
+    """(6, n) int32 CUDA tensor of RNG states: curand_init(seed, first + i, 0) for ray i (rtmi_rng_init_n), in the
+    layout ``SceneBuilder.trace`` reads.  ``device``: a CUDA device (default: torch's current one)."""
+    import torch
+    n, first = int(n), int(first)
+    if n < 0 or first < 0 or first + n > 1 << 40:
+        raise RtmiError("rng_states: n and first must be >= 0 with first + n <= 2^40")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RtmiError("rng_states: the states live on a GPU (device %s)" % dev)
+    out = torch.empty((STATE_WORDS, n), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib().rtmi_rng_init_n(C.c_uint64(int(seed) & (2**64 - 1)), C.c_uint64(first), n,
+                                     C.c_void_p(out.data_ptr()), stream), "rtmi_rng_init_n")
+    return out
 
 
 class SceneBuilder:
@@ -438,6 +480,48 @@ class SceneBuilder:
                                         C.c_void_p(raw.data_ptr()), C.c_void_p(counts.data_ptr()), stream),
                    "rtmi_occluded")
         return Occlusion(raw, counts, (origins, directions, t_max))
+
+    def trace(self, origins, directions, states, max_depth, count_rays=False, out=None):
+        """Path-traced radiance of each ray (rtmi_trace): Trace(world, Ray(o, d), &state, max_depth) as a render runs
+        it for one sample, enqueued on torch's current stream.
+
+        ``origins`` / ``directions`` as for ``intersect``; ``states``: a contiguous (6, N) int32 CUDA tensor of RNG
+        states (``rng_states``), advanced in place by the draws each path makes; ``max_depth`` in [0, 64];
+        ``count_rays``: also return each ray's closest-hit queries; ``out``: an optional (N, 3) float32 CUDA tensor to
+        write the radiance into.  Returns ``Trace``; call ``.check()`` on it before trusting the answers of a mesh
+        scene."""
+        import torch
+        n = _check_rays(origins, "origins")
+        if _check_rays(directions, "directions") != n:
+            raise RtmiError("origins and directions differ in length")
+        if origins.device != directions.device:
+            raise RtmiError("origins and directions are on different devices")
+        dev = origins.device
+        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.int32 and
+                states.shape == (STATE_WORDS, n) and states.is_contiguous() and states.device == dev):
+            raise RtmiError("states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
+        max_depth = int(max_depth)
+        if not 0 <= max_depth <= MAX_DEPTH:
+            raise RtmiError("max_depth %d outside [0, %d]" % (max_depth, MAX_DEPTH))
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and
+                  out.shape == (n, 3) and out.is_contiguous() and out.device == dev):
+            raise RtmiError("out must be a contiguous CUDA float32 tensor of shape (N, 3) on the rays' device")
+        if self.h.value is None or getattr(self, "device", None) is None:
+            raise RtmiError("scene not committed")
+        if dev != self.device:
+            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        origins, directions = origins.contiguous(), directions.contiguous()
+        rays = torch.empty((n,), dtype=torch.int32, device=dev) if count_rays else None
+        work = torch.zeros((TRACE_WORK_WORDS,), dtype=torch.int64, device=dev)  # (n == 0 leaves it untouched)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _check(self.L.rtmi_trace(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                     max_depth, C.c_void_p(states.data_ptr()), C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(rays.data_ptr()) if rays is not None else None,
+                                     C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
+        return Trace(out, rays, work, (origins, directions, states))
 
 
 def _check_rays(a, what):
