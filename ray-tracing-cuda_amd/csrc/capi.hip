@@ -129,6 +129,18 @@ static int device_jump(uint32_t **out) {
   *out = it->second;
   return RTMI_OK;
 }
+// compute units of device dev, cached per device (hipGetDeviceProperties is slow)
+static int device_cus(int dev, int *n_cu) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_cus.find(dev);
+  if (it == g_cus.end()) {
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    it = g_cus.emplace(dev, prop.multiProcessorCount).first;
+  }
+  *n_cu = it->second;
+  return RTMI_OK;
+}
 
 template <typename R>
 static int upload(Scene *s, const std::vector<R> &v, const R **out) {
@@ -600,29 +612,42 @@ int rtmi_rng_get_state(const rtmi_frame *f, const void *d_states, int64_t q, uin
 }
 
 // ------------------------------------------------------------------ render
-// Per-call scratch: [ counters: RTMI_COUNTER_WORDS x 8 B ][ probe RNG states ][ probe ray counts ][ tile costs ]
-// [ tile order ][ 32 words of scheduler meta ][ head list: kHeadCap words ][ probe work counts ][ quarter costs ]
-// [ quarters sorted ][ quarter order ][ 4 words ][ chain plan: per tile estimate of what follows, next tile, claim; per
-// chain its first tile (kMaxChains words) ] rounded up to 256 bytes, then [ wave-priority table: kPrioTabBytes ]
-// [ two kernel-argument blocks: probe pass, real pass ].  The counters come first so that rtmi_render_status can find
-// them from the scratch pointer alone.
+// Per-call scratch of a frame, the one description of it (rtmi_render_scratch_bytes, rtmi_render_ex).  The counters come
+// first so that rtmi_render_status can find them from the scratch pointer alone; then what the scheduler's probe pass
+// leaves for the real pass, rounded up to 256 bytes; then the wave-priority table and the kernel-argument blocks.
 static constexpr size_t kCounterBytes = RTMI_COUNTER_WORDS * sizeof(unsigned long long);
 static constexpr int kMaxChains = 1 << 15;  // planned chains: one per wave of the grid (8 waves x 4 SIMDs x 1024 CUs)
-static size_t scratch_body_bytes(const FrameDev &d);
-static size_t scratch_bytes_of(const FrameDev &d) {
-  return scratch_body_bytes(d) + kPrioTabBytes + 2 * render_params_bytes();
-}
-static size_t scratch_body_bytes(const FrameDev &d) {
+struct ScratchLayout {  // byte offsets of the regions (sizes: scratch_layout), and the whole
+  size_t states, rays, cost, order;   // the probe's RNG states and ray counts; tile costs, tile order
+  size_t meta, head, work;            // scheduler meta (launch_tile_order), the head list right behind it; probe work counts
+  size_t qcost, qsorted, qmap, qmax;  // quarter tiles: costs, sorted, order; their maximum
+  size_t fut, next, claims, first;    // chain plan: per tile what follows, next tile, claim; per chain its first tile
+  size_t prio_tab, params, total;     // wave-priority table, the two kernel-argument blocks (probe pass, real pass)
+};
+static ScratchLayout scratch_layout(const FrameDev &d) {
   const size_t n = (size_t)d.items, nt = (size_t)d.local_tiles;
-  return (kCounterBytes + n * RTMI_STATE_WORDS * 4 + n * 4 + nt * 4 * 2 + 128 + (size_t)kHeadCap * 4 +
-         n * 4 + nt * 4 * 15 + 16 + (size_t)kMaxChains * 4 + 255) & ~(size_t)255;  // + the probe's work counts, the quarter-tile costs, their sorted
-                                                     // list, the order, the chain plan; then the wave-priority table and
-                                                     // the two kernel-argument blocks (scratch_bytes_of)
+  ScratchLayout l;
+  size_t at = kCounterBytes;
+  auto region = [&at](size_t bytes) { const size_t o = at; at += bytes; return o; };
+  l.states = region(n * RTMI_STATE_WORDS * 4);
+  l.rays = region(n * 4);
+  l.cost = region(nt * 4), l.order = region(nt * 4);
+  l.meta = region(32 * 4);  // (8-byte aligned: with n = 64 nt, 320 + 1800 nt bytes in)
+  l.head = region((size_t)kHeadCap * 4);
+  l.work = region(n * 4);
+  l.qcost = region(nt * 16), l.qsorted = region(nt * 16), l.qmap = region(nt * 16), l.qmax = region(16);
+  l.fut = region(nt * 4), l.next = region(nt * 4), l.claims = region(nt * 4);
+  l.first = region((size_t)kMaxChains * 4);
+  at = (at + 255) & ~(size_t)255;
+  l.prio_tab = region(kPrioTabBytes);
+  l.params = region(2 * render_params_bytes());
+  l.total = at;
+  return l;
 }
 size_t rtmi_render_scratch_bytes(const rtmi_frame *f) {
   FrameDev d;
   if (!make_frame(f, &d)) return 0;
-  return scratch_bytes_of(d);
+  return scratch_layout(d).total;
 }
 
 int rtmi_render(const rtmi_scene *sp, const rtmi_frame *f, void *d_states, float *d_tiles, uint32_t *d_ray_counts,
@@ -676,16 +701,7 @@ static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &t
   HIP_TRY(hipGetDevice(&dev));
   if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
   int n_cu = 0;
-  {  // compute-unit count, cached per device (hipGetDeviceProperties is slow)
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_cus.find(dev);
-    if (it == g_cus.end()) {
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, dev));
-      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
-    }
-    n_cu = it->second;
-  }
+  if (int rc = device_cus(dev, &n_cu)) return rc;
   const uint32_t variant = pick_variant(s->features);
   int threads = tune.threads > 0 ? tune.threads : 256;
   if (threads > 256 && !(variant & F_BVH)) threads = 256;  // only the mesh kernels are built for larger workgroups
@@ -822,31 +838,35 @@ int rtmi_render_mode(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_rende
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ batches of caller rays
+// What rtmi_intersect, rtmi_occluded and rtmi_trace check before they launch, in this order: the arguments first, without
+// a HIP call (the host never reads the rays), then the scene's device.  max_depth (rtmi_trace's, else null): n is at most
+// 2^31 - 1 and the depth in [0, RTMI_MAX_DEPTH] too.  *n_cu: the device's compute units, 0 when n == 0 (nothing to do).
+static int batch_prologue(const rtmi_scene *sp, int64_t n, bool arrays, const char *null_arrays, const int *max_depth,
+                          const Scene **out, int *n_cu) {
+  *n_cu = 0;
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
+  if (max_depth && n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 rays");
+  if (n > 0 && !arrays) return fail(RTMI_ERR_INVALID, null_arrays);
+  const Scene *s = *out = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if (max_depth && (*max_depth < 0 || *max_depth > RTMI_MAX_DEPTH))
+    return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  return n == 0 ? RTMI_OK : device_cus(dev, n_cu);
+}
+
 // ------------------------------------------------------------------ closest-hit queries
 static int intersect(const rtmi_scene *sp, int64_t n, const float *d_o, const float *d_d, const float *d_t_max,
                      rtmi_hit *d_hits, unsigned long long *d_abandoned, unsigned long long *d_check, void *stream) {
   static_assert(sizeof(rtmi_hit) == 12 * sizeof(int32_t), "rtmi_hit is 48 bytes");
-  // (argument checks first, without a HIP call: the host never reads the rays)
-  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
-  if (n > 0 && (!d_o || !d_d || !d_hits)) return fail(RTMI_ERR_INVALID, "null ray or hit array");
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
-  if (n == 0) return RTMI_OK;
-  int n_cu = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_cus.find(dev);
-    if (it == g_cus.end()) {
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, dev));
-      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
-    }
-    n_cu = it->second;
-  }
+  const Scene *s;
+  int n_cu;
+  const int rc = batch_prologue(sp, n, d_o && d_d && d_hits, "null ray or hit array", nullptr, &s, &n_cu);
+  if (rc || n == 0) return rc;
   HIP_TRY(launch_query(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_o, d_d, d_t_max,
                        reinterpret_cast<int32_t *>(d_hits), d_abandoned, d_check, (hipStream_t)stream));
   return RTMI_OK;
@@ -865,34 +885,12 @@ int rtmi_intersect_check_counts(const rtmi_scene *s, int64_t n, const float *d_o
 #endif
 
 // ------------------------------------------------------------------ any-hit visibility queries
-static int occluded(const rtmi_scene *sp, int64_t n, const float *d_o, const float *d_d, const float *d_t_max,
-                    uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check, void *stream) {
-  // (argument checks first, without a HIP call: the host never reads the rays)
-  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
-  if (n > 0 && (!d_o || !d_d || !d_occluded)) return fail(RTMI_ERR_INVALID, "null ray or output array");
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
-  if (n == 0) return RTMI_OK;
-  int n_cu = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_cus.find(dev);
-    if (it == g_cus.end()) {
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, dev));
-      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
-    }
-    n_cu = it->second;
-  }
-  // Longer rays that start inside a mesh's bounds run into quirk g8 for most of what the mesh occludes
-  // (occlusion_body.h): they walk from +inf instead.  The padding and the length (1/20 of the meshes' extent) only move
-  // rays between two exact ways of answering.
-  float near_short = 0.f;
-  float near_lo[3] = {INFINITY, INFINITY, INFINITY}, near_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+// Longer rays that start inside a mesh's bounds run into quirk g8 for most of what the mesh occludes (occlusion_body.h):
+// they walk from +inf instead.  The padding and the length (1/20 of the meshes' extent) only move rays between two exact
+// ways of answering.
+static void near_box(const Scene *s, float near_lo[3], float near_hi[3], float *near_short) {
+  *near_short = 0.f;
+  for (int k = 0; k < 3; k++) near_lo[k] = INFINITY, near_hi[k] = -INFINITY;
   for (const BvhRec &br : s->bvh_recs)
     for (int k = 0; k < 3; k++)
       near_lo[k] = fminf(near_lo[k], br.root_mn[k]), near_hi[k] = fmaxf(near_hi[k], br.root_mx[k]);
@@ -901,9 +899,19 @@ static int occluded(const rtmi_scene *sp, int64_t n, const float *d_o, const flo
     for (int k = 0; k < 3; k++)
       diag = fmaxf(diag, near_hi[k] - near_lo[k]), mag = fmaxf(mag, fmaxf(fabsf(near_lo[k]), fabsf(near_hi[k])));
     const float pad = 1e-2f * diag + 1e-4f * mag;
-    near_short = 0.05f * diag;
+    *near_short = 0.05f * diag;
     for (int k = 0; k < 3; k++) near_lo[k] -= pad, near_hi[k] += pad;
   }
+}
+
+static int occluded(const rtmi_scene *sp, int64_t n, const float *d_o, const float *d_d, const float *d_t_max,
+                    uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check, void *stream) {
+  const Scene *s;
+  int n_cu;
+  const int rc = batch_prologue(sp, n, d_o && d_d && d_occluded, "null ray or output array", nullptr, &s, &n_cu);
+  if (rc || n == 0) return rc;
+  float near_lo[3], near_hi[3], near_short;
+  near_box(s, near_lo, near_hi, &near_short);
   HIP_TRY(launch_occlusion(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, d_o, d_d,
                            d_t_max, d_occluded, d_counts, d_check, (hipStream_t)stream));
   return RTMI_OK;
@@ -924,30 +932,11 @@ int rtmi_occluded_check_counts(const rtmi_scene *s, int64_t n, const float *d_or
 // ------------------------------------------------------------------ radiance of caller rays
 int rtmi_trace(const rtmi_scene *sp, int64_t n, const float *d_origins, const float *d_dirs, int max_depth,
                void *d_states, float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
-  // (argument checks first, without a HIP call: the host never reads the rays)
-  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative ray count");
-  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 rays");
-  if (n > 0 && (!d_origins || !d_dirs || !d_states || !d_radiance || !d_work))
-    return fail(RTMI_ERR_INVALID, "null ray, state, radiance or work array");
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  if (max_depth < 0 || max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
-  if (n == 0) return RTMI_OK;
-  int n_cu = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_cus.find(dev);
-    if (it == g_cus.end()) {
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, dev));
-      it = g_cus.emplace(dev, prop.multiProcessorCount).first;
-    }
-    n_cu = it->second;
-  }
+  const Scene *s;
+  int n_cu;
+  const int rc = batch_prologue(sp, n, d_origins && d_dirs && d_states && d_radiance && d_work,
+                                "null ray, state, radiance or work array", &max_depth, &s, &n_cu);
+  if (rc || n == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the counter words (abandoned searches, queries, queue cursor) start from zero; the argument block behind them is
   // written by launch_trace
@@ -980,7 +969,8 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
   const int threads = ls.threads, blocks = ls.blocks;
   tune.lane_stride = ls.lane_stride;
   hipStream_t st = (hipStream_t)stream;
-  const size_t need = scratch_bytes_of(d);
+  const ScratchLayout sl = scratch_layout(d);
+  const size_t need = sl.total;
   if (user_scratch && user_scratch_bytes < need)
     return fail(RTMI_ERR_INVALID, "rtmi_render_opts.scratch_bytes < rtmi_render_scratch_bytes(frame)");
   // Every piece of device state of this call -- queue cursors, ray total, abandoned-search flag, the scheduler's
@@ -989,7 +979,7 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
   // scene state) is used, which ties renders of this scene to one at a time.
   unsigned long long *counters = user_scratch ? reinterpret_cast<unsigned long long *>(user_scratch) : s->d_counters;
   // the kernels' argument blocks (kernels.hip: RenderParams): probe pass, real pass
-  char *params = user_scratch ? reinterpret_cast<char *>(user_scratch) + scratch_body_bytes(d) + kPrioTabBytes
+  char *params = user_scratch ? reinterpret_cast<char *>(user_scratch) + sl.params
                               : reinterpret_cast<char *>(s->d_counters) + kCounterBytes;
   // Longest-first tile order, first pass, plan, priorities: decide_mode
   SchedPlan plan;
@@ -1010,23 +1000,18 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
   }
   FrameDev first = d;               // the launch that finishes the frame: all of it, or what a first pass left
   uint32_t *ray_buf = d_ray_counts;  // (a resumed pixel reads its count back: scratch when the caller wants none)
+  auto region = [scratch](size_t off) { return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scratch) + off); };
   if (prio) {
-    plan.prio_tab = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scratch) + scratch_body_bytes(d));
+    plan.prio_tab = region(sl.prio_tab);
     HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
   }
   if (scheduled) {
     const size_t n = (size_t)d.items, nt = (size_t)d.local_tiles;
-    uint32_t *p_states = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scratch) + kCounterBytes);
-    uint32_t *p_rays = p_states + n * RTMI_STATE_WORDS;
-    uint32_t *p_cost = p_rays + n;
-    uint32_t *p_order = p_cost + nt;
-    uint32_t *p_meta = p_order + nt;  // 16 + 16 words (launch_tile_order); 450 * nt words in: 8-byte aligned
-    uint32_t *p_work = p_meta + 32 + kHeadCap;
-    uint32_t *p_qcost = p_work + n, *p_qsorted = p_qcost + 4 * nt, *p_qmap = p_qsorted + 4 * nt, *p_qmax = p_qmap + 4 * nt;
-    uint32_t *p_fut = p_qmax + 4;
-    int32_t *p_next = reinterpret_cast<int32_t *>(p_fut + nt);
-    uint32_t *p_claims = reinterpret_cast<uint32_t *>(p_next + nt);
-    int32_t *p_first = reinterpret_cast<int32_t *>(p_claims + nt);  // kMaxChains words
+    uint32_t *p_states = region(sl.states), *p_rays = region(sl.rays), *p_cost = region(sl.cost), *p_order = region(sl.order);
+    uint32_t *p_meta = region(sl.meta), *p_work = region(sl.work);
+    uint32_t *p_qcost = region(sl.qcost), *p_qsorted = region(sl.qsorted), *p_qmap = region(sl.qmap), *p_qmax = region(sl.qmax);
+    uint32_t *p_fut = region(sl.fut), *p_claims = region(sl.claims);
+    int32_t *p_next = reinterpret_cast<int32_t *>(region(sl.next)), *p_first = reinterpret_cast<int32_t *>(region(sl.first));
     // mesh frames (binary32 t): the probe also books the lane-steps of its mesh searches on the pixels they serve
     const bool by_cost = tune.cost_probe && (variant & F_BVH) && !(variant & F_SPHERE);
     // first pass: the frame's own samples [0, probe_spp) into the caller's buffers, or a discarded probe on copies
@@ -1073,7 +1058,7 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
     // sparse stride, or RTMI_HEAD_CLASSES=0 -- the outlier tiles at one pixel per that many lanes
     static const bool head_classes = env_int("RTMI_HEAD_CLASSES", 1) != 0;
     const bool by_pixels = head_classes && !(opts && opts->sparse_stride > 0);
-    uint32_t *p_head = (variant & F_BVH) && by_pixels ? p_meta + 32 : nullptr;
+    uint32_t *p_head = (variant & F_BVH) && by_pixels ? region(sl.head) : nullptr;
     HIP_TRY(launch_tile_order(p_rays, d.local_tiles, p_cost, p_meta, p_order, p_head, sparse_cap, blocks * (threads / 64),
                               tune.outlier_x10, tune.head_pct, st));
     // (the head's marks in p_rays are bit 31: quarter_cost_kernel masks them off)

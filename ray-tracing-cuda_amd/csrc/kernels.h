@@ -102,8 +102,6 @@ uint32_t pick_query_variant(uint32_t features);
 hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
                         const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
                         unsigned long long *d_check, hipStream_t stream);
-// the launch of a batch of n rays: workgroups (as many as fit on n_cu compute units, at most one per 256 rays), lanes each
-hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads);
 // Batched any-hit visibility queries (rtmi_occluded; kernels.hip: occlusion_kernel), on the query variants.
 // d_occluded: n bytes; d_t_max, d_counts ({abandoned, fallback rays}), d_check nullable (as launch_query).  Rays whose
 // origin lies inside [near_lo, near_hi] (the padded union of the meshes' root bounds) and whose t_max is not below

@@ -47,6 +47,7 @@
 #include "kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 #include "scene_dev.h"
 #include "vec.h"
 #include "xorwow.h"
@@ -640,89 +641,23 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   return lc;
 }
 
-template <uint32_t F>
-static hipError_t launch_render_t(const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
-                                  uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan,
-                                  bool probe, int blocks, int threads, const RenderTuning &tune, void *d_params,
-                                  hipStream_t stream) {
-  size_t lds = 0;
-  LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds);
-  lc.tile_order = plan.tile_order;
-  lc.visit_counts = plan.visit_counts;
-  lc.sparse_items = plan.sparse_items;
-  lc.head_list = plan.head_list;
-  lc.probe_marks = plan.probe_marks;
-  lc.sparse_stride = tune.sparse_stride;
-  lc.exclusive = tune.exclusive;
-  lc.probe_spp = plan.probe_spp;
-  lc.promote = tune.promote;
-  lc.lane_stride = tune.lane_stride > 0 ? tune.lane_stride : 1;
-  lc.prio_tab = plan.prio_tab;  // (a first pass has one when it is long enough to gain from priorities: capi.hip)
-  lc.tile_cost = plan.tile_cost;
-  lc.rate_scale = 1.f / (64.f * (float)(plan.probe_spp > 0 ? plan.probe_spp : 1));
-  lc.chain_next = (F & F_BVH) || lc.prio_tab == nullptr ? nullptr : plan.chain_next;
-  lc.chain_fut = plan.chain_fut, lc.chain_first = plan.chain_first, lc.claims = plan.claims;
-  lc.plan_simds = plan.plan_simds, lc.plan_rounds = plan.plan_rounds;
-  lc.prio_every = tune.prio_every > 0 ? tune.prio_every : 16;
-  {  // (render_body.h: the wave draws from the queue in batches; RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST: A/B measurements)
-    static const int batch_main = [] { const char *e = getenv("RTMI_FETCH_BATCH"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : v > 64 ? 64 : v; }();
-    static const int batch_first = [] { const char *e = getenv("RTMI_FETCH_BATCH_FIRST"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v > 64 ? 64 : v; }();
-    // a first pass of a few samples: whole tiles; longest-first order: 16 (measured 4 / 16 / 64 on frames of 2.3 ...
-    // 12.8 pixels per lane, NOTES.md); image order, or a first pass as long as a frame: the lanes that wait
-    // (a pooled item waits for a lane of its wave: the longer a pixel takes, the fewer -- from 4,096 samples on, none)
-    const int samples = fr.k_end - fr.k_begin > 0 ? fr.k_end - fr.k_begin : 1;
-    const int by_length = 4096 / samples < 1 ? 1 : 4096 / samples;
-    // image order (a frame too short to be scheduled, or a first pass as long as a frame): its last tiles weigh as much as
-    // any, so batches only where the atomics would otherwise be the frame -- cornell 1024^2 x 16 spp: 8.0 ms a pixel at
-    // a time, 5.2 ms four at a time; at 200 spp sixteen at a time cost 8 %
-    // (below 32 spp -- where list frames are not scheduled -- 256 / samples: at 24 spp two pixels per atomic left a 2048^2
-    // frame at the cursor's rate, 23.8 ms against 22.1 ms for 32 spp)
-    const int per_atomic = samples < 32 ? 256 / samples : 64 / samples;
-    const int image_batch = per_atomic < 1 ? 1 : per_atomic > 16 ? 16 : per_atomic;
-    lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_batch;
-  }
-  if (lds > 64 * 1024) {  // above the default dynamic-LDS limit: ask for it (160 KiB per CU on gfx950)
-    hipError_t e = hipFuncSetAttribute(probe ? reinterpret_cast<const void *>(probe_kernel<F>)
-                                             : reinterpret_cast<const void *>(render_kernel<F>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// Dynamic LDS of a launch of Kernel: above the default limit of 64 KiB it is asked for (160 KiB per CU on gfx950).  The
+// bodies address LDS by byte offsets of the dynamic array (render_body.h: lds_byte, the id stack; query_body.h and
+// occlusion_body.h: the staged regions): right only while the kernel declares no static LDS, in EVERY build flavour
+// (-DRTMI_STATS, -DRTMI_CHECK_MARGINS, A/B builds) -- asked of the code object once per kernel.
+template <auto Kernel>
+static hipError_t dynamic_lds(size_t lds) {
+  const void *k = reinterpret_cast<const void *>(Kernel);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  {  // render_body.h reads LDS by byte offset (lds_byte): right only while the kernels declare no static LDS, in EVERY
-     // build flavour (-DRTMI_STATS, -DRTMI_CHECK_MARGINS, A/B builds) -- asked of the code object once per variant
-    static const hipError_t lds_ok = [] {
-      hipFuncAttributes a{}, b{};
-      hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(render_kernel<F>));
-      if (e == hipSuccess) e = hipFuncGetAttributes(&b, reinterpret_cast<const void *>(probe_kernel<F>));
-      if (e != hipSuccess) return e;
-      return a.sharedSizeBytes == 0 && b.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
-    }();
-    if (lds_ok != hipSuccess) return lds_ok;
-  }
-  RenderParams rp;
-  rp.sc = sc, rp.fr = fr, rp.lc = lc;
-  rp.states = d_states, rp.out = d_out, rp.ray_counts = d_ray_counts, rp.counters = d_counters;
-  RenderParams *dp = reinterpret_cast<RenderParams *>(d_params);
-  hipLaunchKernelGGL(params_write_kernel, dim3(1), dim3(64), 0, stream, rp, dp);
-  if (probe) {
-    hipLaunchKernelGGL(probe_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
-  } else {
-    hipLaunchKernelGGL(render_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
-  }
-  return hipGetLastError();
-}
-
-template <uint32_t F>
-static int occupancy_t(const SceneDev &sc, const FrameDev &fr, int threads) {
-  int nb = 0;
-  size_t lds = 0;
-  (void)make_cfg(F, sc, fr, threads, &lds);
-  if (threads > RTMI_MAX_THREADS(F) || lds > 160 * 1024) return 0;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(render_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds) != hipSuccess)
-    return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel<F>, threads, lds) != hipSuccess) nb = 0;
-  return nb;
+  static const hipError_t no_static = [k] {
+    hipFuncAttributes a{};
+    const hipError_t e = hipFuncGetAttributes(&a, k);
+    return e != hipSuccess ? e : a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
+  }();
+  return no_static;
 }
 
 // The specialisations that are instantiated; a feature set outside them uses F_ALL.
@@ -745,24 +680,83 @@ uint32_t pick_variant(uint32_t features) {
   return F_ALL;
 }
 
-int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads) {
+// f(std::integral_constant<uint32_t, V>()) for the instantiated variant V that equals `variant`; `otherwise` for any other.
+template <class R, class Fn>
+static R with_variant(uint32_t variant, R otherwise, Fn &&f) {
 #define X(V) \
-  if (variant == (uint32_t)(V)) return occupancy_t<(V)>(sc, fr, threads);
+  if (variant == (uint32_t)(V)) return f(std::integral_constant<uint32_t, (V)>());
   RTMI_FOR_EACH_VARIANT(X)
 #undef X
-  return 0;
+  return otherwise;
+}
+
+int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads) {
+  return with_variant(variant, 0, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    int nb = 0;
+    size_t lds = 0;
+    (void)make_cfg(F, sc, fr, threads, &lds);
+    if (threads > RTMI_MAX_THREADS(F) || lds > 160 * 1024 || dynamic_lds<render_kernel<F>>(lds) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel<F>, threads, lds) != hipSuccess) nb = 0;
+    return nb;
+  });
 }
 
 hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
                          uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan, bool probe,
                          int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) \
-    return launch_render_t<(V)>(sc, fr, d_states, d_out, d_ray_counts, d_counters, plan, probe, blocks, threads, tune, \
-                                d_params, stream);
-  RTMI_FOR_EACH_VARIANT(X)
-#undef X
-  return hipErrorInvalidValue;
+  return with_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    size_t lds = 0;
+    LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds);
+    lc.tile_order = plan.tile_order;
+    lc.visit_counts = plan.visit_counts;
+    lc.sparse_items = plan.sparse_items;
+    lc.head_list = plan.head_list;
+    lc.probe_marks = plan.probe_marks;
+    lc.sparse_stride = tune.sparse_stride;
+    lc.exclusive = tune.exclusive;
+    lc.probe_spp = plan.probe_spp;
+    lc.promote = tune.promote;
+    lc.lane_stride = tune.lane_stride > 0 ? tune.lane_stride : 1;
+    lc.prio_tab = plan.prio_tab;  // (a first pass has one when it is long enough to gain from priorities: capi.hip)
+    lc.tile_cost = plan.tile_cost;
+    lc.rate_scale = 1.f / (64.f * (float)(plan.probe_spp > 0 ? plan.probe_spp : 1));
+    lc.chain_next = (F & F_BVH) || lc.prio_tab == nullptr ? nullptr : plan.chain_next;
+    lc.chain_fut = plan.chain_fut, lc.chain_first = plan.chain_first, lc.claims = plan.claims;
+    lc.plan_simds = plan.plan_simds, lc.plan_rounds = plan.plan_rounds;
+    lc.prio_every = tune.prio_every > 0 ? tune.prio_every : 16;
+    {  // (render_body.h: the wave draws from the queue in batches; RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST: A/B measurements)
+      static const int batch_main = [] { const char *e = getenv("RTMI_FETCH_BATCH"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : v > 64 ? 64 : v; }();
+      static const int batch_first = [] { const char *e = getenv("RTMI_FETCH_BATCH_FIRST"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v > 64 ? 64 : v; }();
+      // a first pass of a few samples: whole tiles; longest-first order: 16 (measured 4 / 16 / 64 on frames of 2.3 ...
+      // 12.8 pixels per lane, NOTES.md); image order, or a first pass as long as a frame: the lanes that wait
+      // (a pooled item waits for a lane of its wave: the longer a pixel takes, the fewer -- from 4,096 samples on, none)
+      const int samples = fr.k_end - fr.k_begin > 0 ? fr.k_end - fr.k_begin : 1;
+      const int by_length = 4096 / samples < 1 ? 1 : 4096 / samples;
+      // image order (a frame too short to be scheduled, or a first pass as long as a frame): its last tiles weigh as much as
+      // any, so batches only where the atomics would otherwise be the frame -- cornell 1024^2 x 16 spp: 8.0 ms a pixel at
+      // a time, 5.2 ms four at a time; at 200 spp sixteen at a time cost 8 %
+      // (below 32 spp -- where list frames are not scheduled -- 256 / samples: at 24 spp two pixels per atomic left a 2048^2
+      // frame at the cursor's rate, 23.8 ms against 22.1 ms for 32 spp)
+      const int per_atomic = samples < 32 ? 256 / samples : 64 / samples;
+      const int image_batch = per_atomic < 1 ? 1 : per_atomic > 16 ? 16 : per_atomic;
+      lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_batch;
+    }
+    const hipError_t e = probe ? dynamic_lds<probe_kernel<F>>(lds) : dynamic_lds<render_kernel<F>>(lds);
+    if (e != hipSuccess) return e;
+    RenderParams rp;
+    rp.sc = sc, rp.fr = fr, rp.lc = lc;
+    rp.states = d_states, rp.out = d_out, rp.ray_counts = d_ray_counts, rp.counters = d_counters;
+    RenderParams *dp = reinterpret_cast<RenderParams *>(d_params);
+    hipLaunchKernelGGL(params_write_kernel, dim3(1), dim3(64), 0, stream, rp, dp);
+    if (probe) {
+      hipLaunchKernelGGL(probe_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
+    } else {
+      hipLaunchKernelGGL(render_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
+    }
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_untile(const FrameDev &fr, const float *d_tiles, float *d_image, hipStream_t stream) {
@@ -814,228 +808,138 @@ uint32_t pick_query_variant(uint32_t features) {
   return F_ALL & ~F_DEFOCUS;
 }
 
+// with_variant over the query variants (rtmi_intersect, rtmi_occluded, rtmi_trace).
+template <class R, class Fn>
+static R with_query_variant(uint32_t variant, R otherwise, Fn &&f) {
+#define X(V) \
+  if (variant == (uint32_t)(V)) return f(std::integral_constant<uint32_t, (V)>());
+  RTMI_FOR_EACH_QUERY_VARIANT(X)
+#undef X
+  return otherwise;
+}
+
 constexpr int kQueryThreads = 256;
 
+// make_cfg's layout for the query and occlusion kernels (nothing is shaded: no material table, no id stack), and the
+// kQueryLdsExtra bytes of stand-in words behind it (QueryParams / OcclusionParams: dummy_off)
 static LaunchCfg query_cfg(uint32_t variant, const SceneDev &sc, size_t *lds) {
   FrameDev fr{};  // (make_cfg reads max_depth only, for the id stack the queries do without)
-  LaunchCfg lc = make_cfg(variant, sc, fr, kQueryThreads, lds, false, false);  // (nothing is shaded: no material table)
+  LaunchCfg lc = make_cfg(variant, sc, fr, kQueryThreads, lds, false, false);
   *lds = ((*lds + 15) & ~(size_t)15) + kQueryLdsExtra;
   return lc;
 }
 
-template <uint32_t F>
-static hipError_t query_attrs_t(size_t lds) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(query_kernel<F>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // query_body.h hands the mesh search and the list scans LDS by byte offset, as render_body.h does: right only while
-  // the kernel declares no static LDS
-  static const hipError_t lds_ok = [] {
-    hipFuncAttributes a{};
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(query_kernel<F>));
-    if (e != hipSuccess) return e;
-    return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
-  }();
-  return lds_ok;
-}
-
-template <uint32_t F>
-static hipError_t query_shape_t(const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads) {
-  size_t lds = 0;
-  (void)query_cfg(F, sc, &lds);
+// The grid of a batch of n rays on Kernel: as many workgroups as fit on n_cu compute units, at most one per
+// kQueryThreads rays.
+template <auto Kernel>
+static hipError_t query_blocks(size_t lds, int n_cu, int64_t n, int *blocks) {
   if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
-  hipError_t e = query_attrs_t<F>(lds);
+  hipError_t e = dynamic_lds<Kernel>(lds);
   if (e != hipSuccess) return e;
   int nb = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, query_kernel<F>, kQueryThreads, lds);
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, kQueryThreads, lds);
   if (e != hipSuccess) return e;
   if (nb < 1) nb = 1;
   const int64_t want = (n + kQueryThreads - 1) / kQueryThreads, cap = (int64_t)n_cu * nb;
   *blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
-  *threads = kQueryThreads;
   return hipSuccess;
-}
-
-template <uint32_t F>
-static hipError_t launch_query_t(const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
-                                 const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
-                                 unsigned long long *d_check, hipStream_t stream) {
-  int blocks = 0, threads = 0;
-  hipError_t e = query_shape_t<F>(sc, n_cu, n, &blocks, &threads);
-  if (e != hipSuccess) return e;
-  size_t lds = 0;
-  QueryParams qp;
-  qp.sc = sc, qp.qd = qd;
-  qp.lc = query_cfg(F, sc, &lds);
-  qp.n = n, qp.origins = d_o, qp.dirs = d_d, qp.t_max = d_t_max, qp.hits = d_hits;
-  qp.abandoned = d_abandoned, qp.check = d_check;
-  qp.dummy_off = (int32_t)(lds - kQueryLdsExtra);
-  hipLaunchKernelGGL(query_kernel<F>, dim3(blocks), dim3(threads), lds, stream, qp);
-  return hipGetLastError();
 }
 
 hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
                         const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
                         unsigned long long *d_check, hipStream_t stream) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) \
-    return launch_query_t<(V)>(sc, qd, n_cu, n, d_o, d_d, d_t_max, d_hits, d_abandoned, d_check, stream);
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return hipErrorInvalidValue;
+  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    size_t lds = 0;
+    QueryParams qp;
+    qp.sc = sc, qp.qd = qd;
+    qp.lc = query_cfg(F, sc, &lds);
+    int blocks = 0;
+    const hipError_t e = query_blocks<query_kernel<F>>(lds, n_cu, n, &blocks);
+    if (e != hipSuccess) return e;
+    qp.n = n, qp.origins = d_o, qp.dirs = d_d, qp.t_max = d_t_max, qp.hits = d_hits;
+    qp.abandoned = d_abandoned, qp.check = d_check;
+    qp.dummy_off = (int32_t)(lds - kQueryLdsExtra);
+    hipLaunchKernelGGL(query_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, qp);
+    return hipGetLastError();
+  });
 }
-
-hipError_t query_launch_shape(uint32_t variant, const SceneDev &sc, int n_cu, int64_t n, int *blocks, int *threads) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) return query_shape_t<(V)>(sc, n_cu, n, blocks, threads);
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return hipErrorInvalidValue;
-}
-
 
 // ------------------------------------------------------------------ any-hit visibility queries (rtmi_occluded)
 // occlusion_body.h around closest_hit<F, true>: one instantiation per query variant, with the query kernels' staging,
-// LDS layout (plus its own stand-in words) and launch sizing.
+// LDS layout (its stand-in words included) and launch sizing.
 template <uint32_t F>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlusion_kernel(OcclusionParams p) {
   occlusion_body<F>(p);
-}
-
-static LaunchCfg occlusion_cfg(uint32_t variant, const SceneDev &sc, size_t *lds) {
-  FrameDev fr{};
-  LaunchCfg lc = make_cfg(variant, sc, fr, kQueryThreads, lds, false, false);
-  *lds = ((*lds + 15) & ~(size_t)15) + kOcclusionLdsExtra;
-  return lc;
-}
-
-template <uint32_t F>
-static hipError_t occlusion_attrs_t(size_t lds) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(occlusion_kernel<F>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // LDS regions by byte offset of the dynamic array: right only while the kernel declares no static LDS
-  static const hipError_t lds_ok = [] {
-    hipFuncAttributes a{};
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(occlusion_kernel<F>));
-    if (e != hipSuccess) return e;
-    return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
-  }();
-  return lds_ok;
-}
-
-template <uint32_t F>
-static hipError_t launch_occlusion_t(const SceneDev &sc, const float near_lo[3], const float near_hi[3],
-                                     float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
-                                     const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
-                                     unsigned long long *d_check, hipStream_t stream) {
-  size_t lds = 0;
-  OcclusionParams p;
-  p.sc = sc;
-  p.lc = occlusion_cfg(F, sc, &lds);
-  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
-  hipError_t e = occlusion_attrs_t<F>(lds);
-  if (e != hipSuccess) return e;
-  int nb = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, occlusion_kernel<F>, kQueryThreads, lds);
-  if (e != hipSuccess) return e;
-  if (nb < 1) nb = 1;
-  const int64_t want = (n + kQueryThreads - 1) / kQueryThreads, cap = (int64_t)n_cu * nb;
-  const int blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
-  p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
-  p.counts = d_counts, p.check = d_check;
-  p.dummy_off = (int32_t)(lds - kOcclusionLdsExtra);
-  for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
-  p.near_short = near_short;
-  hipLaunchKernelGGL(occlusion_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p);
-  return hipGetLastError();
 }
 
 hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
                             float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) \
-    return launch_occlusion_t<(V)>(sc, near_lo, near_hi, near_short, n_cu, n, d_o, d_d, d_t_max, d_occluded, \
-                                   d_counts, d_check, stream);
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return hipErrorInvalidValue;
+  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    size_t lds = 0;
+    OcclusionParams p;
+    p.sc = sc;
+    p.lc = query_cfg(F, sc, &lds);
+    int blocks = 0;
+    const hipError_t e = query_blocks<occlusion_kernel<F>>(lds, n_cu, n, &blocks);
+    if (e != hipSuccess) return e;
+    p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
+    p.counts = d_counts, p.check = d_check;
+    p.dummy_off = (int32_t)(lds - kQueryLdsExtra);
+    for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
+    p.near_short = near_short;
+    hipLaunchKernelGGL(occlusion_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------ radiance of caller rays (rtmi_trace)
 // render_body.h in its caller-ray mode on the query variants (F_TEX always: the layer stack is one 32-bit word per level,
 // the material id or the sampled texel).  A persistent grid sized by occupancy; the lanes refill from the call's own
 // queue cursor (d_work[2]) as their paths end, a batch per wave per atomic.
-template <uint32_t F>
-static int trace_occupancy_t(const SceneDev &sc, const FrameDev &fr, int threads, bool tex_layers, size_t *lds) {
-  (void)make_cfg(F, sc, fr, threads, lds, true, true, tex_layers);
-  if (*lds > 160 * 1024) return 0;
-  if (*lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(trace_kernel<F>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
-    return 0;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<F>, threads, *lds) != hipSuccess) nb = 0;
-  return nb;
-}
-
-template <uint32_t F>
-static hipError_t launch_trace_t(const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth, const float *d_o,
-                                 const float *d_d, uint32_t *d_states, float *d_radiance, uint32_t *d_ray_counts,
-                                 unsigned long long *d_work, hipStream_t stream) {
-  FrameDev fr{};
-  fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
-  fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
-  fr.items = n;
-  // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
-  // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
-  int threads = 0, per_cu = 0;
-  for (int t = 256; t >= 64; t /= 2) {
-    size_t lds_t = 0;
-    const int nb = trace_occupancy_t<F>(sc, fr, t, tex_layers, &lds_t);
-    if (t * nb > threads * per_cu) threads = t, per_cu = nb;
-  }
-  if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
-  size_t lds = 0;
-  LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
-  lc.lane_stride = 1;
-  lc.fetch_batch = 64;  // (the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
-  lc.rate_scale = 1.f;
-  {  // render_body.h reads LDS by byte offset (lds_byte, the id stack): right only while the kernel declares no static LDS
-    static const hipError_t lds_ok = [] {
-      hipFuncAttributes a{};
-      hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(trace_kernel<F>));
-      if (e != hipSuccess) return e;
-      return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidConfiguration;
-    }();
-    if (lds_ok != hipSuccess) return lds_ok;
-  }
-  const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
-  const int blocks = (int)(want < cap ? want : cap);
-  TraceParams tp;
-  tp.rp.sc = sc, tp.rp.fr = fr, tp.rp.lc = lc;
-  tp.rp.states = d_states, tp.rp.out = d_radiance, tp.rp.ray_counts = d_ray_counts, tp.rp.counters = d_work;
-  tp.origins = d_o, tp.dirs = d_d, tp.tex_layers = tex_layers ? 1 : 0;
-  TraceParams *dp = reinterpret_cast<TraceParams *>(reinterpret_cast<char *>(d_work) + kTraceParamsOffset);
-  hipLaunchKernelGGL(trace_params_write_kernel, dim3(1), dim3(64), 0, stream, tp, dp);
-  hipLaunchKernelGGL(trace_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const TraceParams *)dp);
-  return hipGetLastError();
-}
-
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) \
-    return launch_trace_t<(V)>(sc, tex_layers, n_cu, n, max_depth, d_o, d_d, d_states, d_radiance, d_ray_counts, d_work, stream);
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return hipErrorInvalidValue;
+  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    FrameDev fr{};
+    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
+    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
+    fr.items = n;
+    // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
+    // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
+    int threads = 0, per_cu = 0;
+    for (int t = 256; t >= 64; t /= 2) {
+      size_t lds_t = 0;
+      (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
+      int nb = 0;
+      if (lds_t > 160 * 1024 || dynamic_lds<trace_kernel<F>>(lds_t) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<F>, t, lds_t) != hipSuccess)
+        nb = 0;
+      if (t * nb > threads * per_cu) threads = t, per_cu = nb;
+    }
+    if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
+    size_t lds = 0;
+    LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
+    lc.lane_stride = 1;
+    lc.fetch_batch = 64;  // (the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
+    lc.rate_scale = 1.f;
+    const hipError_t e = dynamic_lds<trace_kernel<F>>(lds);
+    if (e != hipSuccess) return e;
+    const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
+    const int blocks = (int)(want < cap ? want : cap);
+    TraceParams tp;
+    tp.rp.sc = sc, tp.rp.fr = fr, tp.rp.lc = lc;
+    tp.rp.states = d_states, tp.rp.out = d_radiance, tp.rp.ray_counts = d_ray_counts, tp.rp.counters = d_work;
+    tp.origins = d_o, tp.dirs = d_d, tp.tex_layers = tex_layers ? 1 : 0;
+    TraceParams *dp = reinterpret_cast<TraceParams *>(reinterpret_cast<char *>(d_work) + kTraceParamsOffset);
+    hipLaunchKernelGGL(trace_params_write_kernel, dim3(1), dim3(64), 0, stream, tp, dp);
+    hipLaunchKernelGGL(trace_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const TraceParams *)dp);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace rtmi

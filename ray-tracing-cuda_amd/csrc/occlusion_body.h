@@ -31,7 +31,6 @@ struct OcclusionParams {
   float near_lo[3], near_hi[3];  // padded union of the meshes' root bounds (empty without meshes) ...
   float near_short;              // ... and the t_max below which a ray from inside them still walks bounded
 };
-constexpr size_t kOcclusionLdsExtra = 16;  // bytes behind make_cfg's layout: the stand-in words
 
 // query_body.h's staging (render_body.h's prologue without the materials), as a function: the scene's pair corners,
 // top mesh nodes and leaf paths copied in, and this wave's regions of the dynamic LDS.  The caller waits at a barrier

@@ -19,7 +19,7 @@ struct QueryParams {
   unsigned long long *check;      // -DRTMI_CHECK_MARGINS: nullable, {re-done, disagreements}; else unused
   int32_t dummy_off;          // byte offset in dynamic LDS of a word that stands in for a null `abandoned`
 };
-constexpr size_t kQueryLdsExtra = 16;  // bytes behind make_cfg's layout: the stand-in word
+constexpr size_t kQueryLdsExtra = 16;  // bytes behind make_cfg's layout: the stand-in words (of the occlusion kernel too)
 
 // What Trace makes of the winner (render_body.h, after closest_hit), as a record: the oriented normal of a triangle
 // (utils.cu:80), the parallelogram's remapped u, v (parallelogram.cu:26-29,35-38), the sphere's normal and GetUV

@@ -408,30 +408,12 @@ class SceneBuilder:
         reported only where t <= t_max.  ``out``: an optional (N, 12) int32 CUDA tensor to write into.  Returns
         ``Hits`` (views into that buffer); call ``.check()`` on it before trusting the answers of a mesh scene."""
         import torch
-        n = _check_rays(origins, "origins")
-        if _check_rays(directions, "directions") != n:
-            raise RtmiError("origins and directions differ in length")
-        if origins.device != directions.device:
-            raise RtmiError("origins and directions are on different devices")
-        dev = origins.device
-        if t_max is not None:
-            if not (isinstance(t_max, torch.Tensor) and t_max.is_cuda and t_max.dtype == torch.float32 and
-                    t_max.shape == (n,) and t_max.device == dev):
-                raise RtmiError("t_max must be a CUDA float32 tensor of shape (N,) on the rays' device")
-            t_max = t_max.contiguous()
-        if out is None:
-            out = torch.empty((n, HIT_WORDS), dtype=torch.int32, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and
-                  out.shape == (n, HIT_WORDS) and out.is_contiguous() and out.device == dev):
-            raise RtmiError("out must be a contiguous CUDA int32 tensor of shape (N, 12) on the rays' device")
-        if self.h.value is None or getattr(self, "device", None) is None:
-            raise RtmiError("scene not committed")
-        if dev != self.device:
-            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        n, dev, t_max = _check_batch("rtmi_intersect", origins, directions, t_max)
+        out = _out_buffer(out, "int32 tensor of shape (N, 12)", (n, HIT_WORDS), dev, torch.int32)
+        stream = self._stream(dev)
         origins, directions = origins.contiguous(), directions.contiguous()
         abandoned = torch.zeros((1,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _check(self.L.rtmi_intersect(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                          C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
                                          C.c_void_p(out.data_ptr()), C.c_void_p(abandoned.data_ptr()), stream),
@@ -450,31 +432,13 @@ class SceneBuilder:
         ``directions`` / ``t_max`` as for ``intersect``; ``out``: an optional (N,) uint8 or bool CUDA tensor to
         write into.  Returns ``Occlusion``; call ``.check()`` on it before trusting the answers of a mesh scene."""
         import torch
-        n = _check_rays(origins, "origins")
-        if _check_rays(directions, "directions") != n:
-            raise RtmiError("origins and directions differ in length")
-        if origins.device != directions.device:
-            raise RtmiError("origins and directions are on different devices")
-        dev = origins.device
-        if t_max is not None:
-            if not (isinstance(t_max, torch.Tensor) and t_max.is_cuda and t_max.dtype == torch.float32 and
-                    t_max.shape == (n,) and t_max.device == dev):
-                raise RtmiError("t_max must be a CUDA float32 tensor of shape (N,) on the rays' device")
-            t_max = t_max.contiguous()
-        if out is None:
-            out = torch.empty((n,), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint8, torch.bool) and
-                  out.shape == (n,) and out.is_contiguous() and out.device == dev):
-            raise RtmiError("out must be a contiguous CUDA uint8 or bool tensor of shape (N,) on the rays' device")
-        if self.h.value is None or getattr(self, "device", None) is None:
-            raise RtmiError("scene not committed")
-        if dev != self.device:
-            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        n, dev, t_max = _check_batch("rtmi_occluded", origins, directions, t_max)
+        out = _out_buffer(out, "uint8 or bool tensor of shape (N,)", (n,), dev, torch.uint8, torch.bool)
+        stream = self._stream(dev)
         origins, directions = origins.contiguous(), directions.contiguous()
         raw = out.view(torch.uint8)
         counts = torch.zeros((2,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _check(self.L.rtmi_occluded(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                         C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
                                         C.c_void_p(raw.data_ptr()), C.c_void_p(counts.data_ptr()), stream),
@@ -491,54 +455,78 @@ class SceneBuilder:
         write the radiance into.  Returns ``Trace``; call ``.check()`` on it before trusting the answers of a mesh
         scene."""
         import torch
-        n = _check_rays(origins, "origins")
-        if _check_rays(directions, "directions") != n:
-            raise RtmiError("origins and directions differ in length")
-        if origins.device != directions.device:
-            raise RtmiError("origins and directions are on different devices")
-        dev = origins.device
-        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.int32 and
-                states.shape == (STATE_WORDS, n) and states.is_contiguous() and states.device == dev):
+        n, dev, _ = _check_batch("rtmi_trace", origins, directions)
+        if not _is_buffer(states, (STATE_WORDS, n), dev, torch.int32):
             raise RtmiError("states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
         max_depth = int(max_depth)
         if not 0 <= max_depth <= MAX_DEPTH:
             raise RtmiError("max_depth %d outside [0, %d]" % (max_depth, MAX_DEPTH))
-        if out is None:
-            out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and
-                  out.shape == (n, 3) and out.is_contiguous() and out.device == dev):
-            raise RtmiError("out must be a contiguous CUDA float32 tensor of shape (N, 3) on the rays' device")
-        if self.h.value is None or getattr(self, "device", None) is None:
-            raise RtmiError("scene not committed")
-        if dev != self.device:
-            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        out = _out_buffer(out, "float32 tensor of shape (N, 3)", (n, 3), dev, torch.float32)
+        stream = self._stream(dev)
         origins, directions = origins.contiguous(), directions.contiguous()
         rays = torch.empty((n,), dtype=torch.int32, device=dev) if count_rays else None
         work = torch.zeros((TRACE_WORK_WORDS,), dtype=torch.int64, device=dev)  # (n == 0 leaves it untouched)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _check(self.L.rtmi_trace(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                      max_depth, C.c_void_p(states.data_ptr()), C.c_void_p(out.data_ptr()),
                                      C.c_void_p(rays.data_ptr()) if rays is not None else None,
                                      C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
         return Trace(out, rays, work, (origins, directions, states))
 
+    def _stream(self, dev):
+        """torch's current stream on dev, the rays' device; raises unless the scene was committed there."""
+        if self.h.value is None or getattr(self, "device", None) is None:
+            raise RtmiError("scene not committed")
+        if dev != self.device:
+            raise RtmiError("the rays are on %s, the scene was committed on %s" % (dev, self.device))
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-def _check_rays(a, what):
-    """Length of a (N, 3) CUDA float32 tensor; raises before any GPU work otherwise."""
+
+def _check_batch(entry, origins, directions, t_max=None):
+    """(N, the rays' device, t_max made contiguous) of a batch for ``entry``; raises before any GPU work unless
+    origins and directions are (N, 3) CUDA float32 tensors on one device and t_max is None or (N,) float32 there."""
     try:
         import torch
     except ImportError:
-        raise RtmiError("%s: torch is needed for rtmi_intersect" % what)
-    if not isinstance(a, torch.Tensor):
-        raise RtmiError("%s must be a torch tensor" % what)
-    if not a.is_cuda:
-        raise RtmiError("%s is on the CPU: rtmi_intersect has no CPU path (move it to the scene's GPU)" % what)
-    if a.dtype != torch.float32:
-        raise RtmiError("%s must be float32, not %s" % (what, a.dtype))
-    if a.dim() != 2 or a.shape[1] != 3:
-        raise RtmiError("%s must have shape (N, 3), not %s" % (what, tuple(a.shape)))
-    return int(a.shape[0])
+        raise RtmiError("origins: torch is needed for %s" % entry)
+    for what, a in (("origins", origins), ("directions", directions)):
+        if not isinstance(a, torch.Tensor):
+            raise RtmiError("%s must be a torch tensor" % what)
+        if not a.is_cuda:
+            raise RtmiError("%s is on the CPU: %s has no CPU path (move it to the scene's GPU)" % (what, entry))
+        if a.dtype != torch.float32:
+            raise RtmiError("%s must be float32, not %s" % (what, a.dtype))
+        if a.dim() != 2 or a.shape[1] != 3:
+            raise RtmiError("%s must have shape (N, 3), not %s" % (what, tuple(a.shape)))
+    n = int(origins.shape[0])
+    if directions.shape[0] != n:
+        raise RtmiError("origins and directions differ in length")
+    if origins.device != directions.device:
+        raise RtmiError("origins and directions are on different devices")
+    dev = origins.device
+    if t_max is not None:
+        if not (isinstance(t_max, torch.Tensor) and t_max.is_cuda and t_max.dtype == torch.float32 and
+                t_max.shape == (n,) and t_max.device == dev):
+            raise RtmiError("t_max must be a CUDA float32 tensor of shape (N,) on the rays' device")
+        t_max = t_max.contiguous()
+    return n, dev, t_max
+
+
+def _is_buffer(t, shape, dev, *dtypes):
+    import torch
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.shape == shape and t.is_contiguous()
+            and t.device == dev)
+
+
+def _out_buffer(out, desc, shape, dev, *dtypes):
+    """A new tensor of the first of dtypes for out=None, else out itself, which must match (desc: its words in the error)."""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=dtypes[0], device=dev)
+    if not _is_buffer(out, shape, dev, *dtypes):
+        raise RtmiError("out must be a contiguous CUDA %s on the rays' device" % desc)
+    return out
 
 
 class Renderer:

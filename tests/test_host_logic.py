@@ -343,6 +343,19 @@ def test_render_opts_validation():
     assert total == body + (1 << 14) * 16 * 4 + 2 * params and params % 256 == 0 and 512 <= params <= 2048, (total, body, params)
 
 
+@pytest.mark.parametrize("frame, want", [
+    ((8, 8, 1), 1249536),                                     # small: one tile
+    ((1024, 1024, 64), 35915776),                             # tiled
+    ((2048, 2048, 4096, 64, True, 3, 8), 18581504),           # one shard of eight, deep
+    ((720, 1280, 20, 50), 31717632),                          # deep, partial tiles
+    ((17, 999, 2, 64, False, 6, 7), 1361664),                 # a shard with a padding tile
+])
+def test_render_scratch_bytes_are_pinned(frame, want):
+    """The size of the render's scratch (capi.hip: ScratchLayout), pinned: a change to the layout shows here."""
+    f = rtmi.make_frame(*frame)
+    assert rtmi.lib().rtmi_render_scratch_bytes(C.byref(f)) == want
+
+
 def test_no_cpu_fallback():
     """Without a GPU every compute entry point must fail loudly, never render on the CPU."""
     L = rtmi.lib()
