@@ -441,6 +441,74 @@ int rtmi_trace(const rtmi_scene *s, int64_t n, const float *d_origins, const flo
  * Asynchronous on `stream`; n == 0 launches nothing. */
 int rtmi_rng_init_n(uint64_t seed, uint64_t first, int64_t n, void *d_states, void *stream);
 
+/* ----------------------------------------------------------------- budget --
+ * A render whose sample count is per pixel, a per-pixel error statistic to decide it from, and the two small kernels
+ * that turn them into an adaptive render (plan a pass, render it, ... , resolve).  Added without a version change: a
+ * caller detects it by the symbol rtmi_render_budget.  Every entry is per shard (f->rank of f->world_size), on
+ * tile-major buffers of rtmi_frame_work_items(f) items, so rtmi_untile, rtmi_untile_u32 and rtmi_gather take them as
+ * they are.
+ *
+ * rtmi_render_budget: for every work item q of the shard that is a pixel (not ragged-tile padding), with
+ * b = min(d_budget[q], f->spp):
+ *   - renders b more samples of that pixel -- exactly the samples rtmi_render would render next from d_states (the
+ *     same jitter and lens draws, the same Trace, in the same order) -- and advances the state in place;
+ *   - d_sum[q][c] (float[items][3]): starting from the value it holds, adds each sample's radiance in sample order,
+ *     one binary32 addition per sample and channel (what rtmi_render with post_process = 0 does from zero);
+ *   - d_sq[q][c] (nullable, float[items][3]): likewise adds x * x of each sample's channel value x, the product and
+ *     the sum each rounded to binary32 on its own (no fused multiply-add);
+ *   - d_samples[q] += b;  d_ray_counts[q] (nullable) += the closest-hit queries of those samples.  Both are uint32 and
+ *     wrap modulo 2^32 over many calls.
+ *   - b == 0 and padding items: nothing of the item is read or written, its state included.
+ * All four buffers ACCUMULATE: the caller zeroes them once.  f->spp is the cap on ONE call's samples per pixel (it
+ * keeps spp x (max_depth + 1) <= RTMI_MAX_PIXEL_QUERIES meaningful without the host reading d_budget); f->post_process
+ * must be 0 (RTMI_ERR_INVALID): a uniform division has no meaning here, rtmi_resolve divides.  d_work (required,
+ * RTMI_BUDGET_WORK_WORDS unsigned long long words, 8-byte aligned) is the call's own device state exactly as
+ * rtmi_trace's: reset on `stream` before the launch; afterwards [0] holds the abandoned mesh searches (the results are
+ * exact only while it is 0) and [1] the closest-hit queries of THIS call; the rest is the kernel's (work cursor,
+ * argument block).  The call shares no device state with renders or queries on the scene; a d_work must not be reused
+ * before the call that holds it has finished.  Work is handed out from a plain queue in image order: a pixel is a
+ * serial chain, so a call lasts at least as long as its largest budget x that pixel's queries per sample.
+ * Asynchronous on `stream`.  Before any HIP call: RTMI_ERR_INVALID for a null scene, a bad frame, a null array
+ * (d_sq, d_ray_counts excepted), an uncommitted scene, post_process != 0; RTMI_ERR_DEPTH for max_depth outside
+ * [0, RTMI_MAX_DEPTH]; then RTMI_ERR_INVALID when the current device is not the scene's. */
+#define RTMI_BUDGET_WORK_WORDS RTMI_TRACE_WORK_WORDS
+int rtmi_render_budget(const rtmi_scene *s, const rtmi_frame *f, const uint32_t *d_budget, void *d_states,
+                       float *d_sum, float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts,
+                       unsigned long long *d_work, void *stream);
+
+typedef struct rtmi_adaptive_opts {
+  int32_t size;        /* sizeof(rtmi_adaptive_opts) of the caller: must match the library's */
+  int32_t min_samples; /* >= 2 */
+  int32_t max_samples; /* >= min_samples */
+  int32_t step;        /* >= 1: samples a pixel that has not converged gets per pass */
+  float tolerance;     /* > 0: relative standard error of the pixel mean at which it stops */
+  float floor;         /* >= 0: radiance below which the error is taken as absolute (dark pixels) */
+} rtmi_adaptive_opts;
+/* The next pass's budget of every work item, from what rtmi_render_budget accumulated.  With n = d_samples[q]:
+ *   padding -> 0;  n < min_samples -> min_samples - n;  n >= max_samples -> 0;  otherwise the pixel has converged iff
+ * for EVERY channel, with S = d_sum[q][c], Q = d_sq[q][c], nf = (float)n (round to nearest), T = tolerance, F = floor,
+ * in binary32 with every operation rounded on its own (no fused multiply-add), evaluated exactly as written:
+ *     a = nf * Q;  b = S * S;  c = a - b;  d = nf - 1.0f;  lhs = c / d;
+ *     e = T * T;   g = nf * nf;  h = F * F;  i = g * h;  j = b + i;  rhs = e * j;
+ *     lhs <= rhs          (false when either side is a NaN: such a pixel has not converged)
+ * i.e. "unbiased sample variance / n <= T^2 (mean^2 + F^2)" multiplied through by n^2.  Converged -> 0, else
+ * min(step, max_samples - n).  d_totals (two unsigned long long) is OVERWRITTEN on the stream: [0] = items with a
+ * budget > 0, [1] = the sum of the budgets; a pass is needed while [0] != 0.
+ * Raw second moments lose digits to cancellation when n is large and the variance small.  The rule is first met at the
+ * smallest n that satisfies it, where the sums are short; a pixel that has met it gets no more samples, so the loss
+ * cannot stop a pixel early that the exact statistic would have kept, only (harmlessly) make a stopped pixel look more
+ * converged had it gone on.
+ * Asynchronous on `stream`; RTMI_ERR_INVALID before any HIP call for a bad frame, a null array, null opts, a wrong
+ * size, min_samples < 2, max_samples < min_samples, step < 1, a tolerance that is not a finite number > 0, a floor
+ * that is not a finite number >= 0. */
+int rtmi_budget_plan(const rtmi_frame *f, const rtmi_adaptive_opts *o, const float *d_sum, const float *d_sq,
+                     const uint32_t *d_samples, uint32_t *d_budget, unsigned long long *d_totals, void *stream);
+/* d_tiles[q][c] = d_sum[q][c] / (float)d_samples[q] (0 where d_samples[q] == 0 and for padding), then with post_process
+ * != 0 sqrt(clamp(., 0, 1)) by the render's own expressions: for a uniform sample count the result is bit for bit
+ * rtmi_render's post-processed tile buffer.  Tile-major, float[items][3].  Asynchronous on `stream`. */
+int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samples, int post_process, float *d_tiles,
+                 void *stream);
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

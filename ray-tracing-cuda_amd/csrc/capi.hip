@@ -946,6 +946,68 @@ int rtmi_trace(const rtmi_scene *sp, int64_t n, const float *d_origins, const fl
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ per-pixel sample budgets
+// What the three entries below check of their frame, in the other entries' order: the arguments first, without a HIP call.
+static int budget_frame(const rtmi_frame *f, bool arrays, const char *null_arrays, FrameDev *d) {
+  if (!make_frame(f, d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
+  if (d->items > 0 && !arrays) return fail(RTMI_ERR_INVALID, null_arrays);
+  return RTMI_OK;
+}
+
+int rtmi_render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
+                       float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  FrameDev d;
+  int rc = budget_frame(f, d_budget && d_states && d_sum && d_samples && d_work,
+                        "null budget, state, sum, sample-count or work array", &d);
+  if (rc) return rc;
+  const Scene *s = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if (d.max_depth < 0 || d.max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
+  if (d.post) return fail(RTMI_ERR_INVALID, "post_process must be 0: per-pixel sample counts have no uniform division (rtmi_resolve)");
+  // (spp caps one call's samples per pixel: a call's closest-hit queries of a pixel stay below 2^31 as a render's do)
+  if ((int64_t)d.spp * (d.max_depth + 1) > (int64_t)RTMI_MAX_PIXEL_QUERIES)
+    return fail(RTMI_ERR_INVALID, "spp x (max_depth + 1) above 2^31 - 1 (RTMI_MAX_PIXEL_QUERIES): a pixel's closest-hit queries are counted in 31 bits");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  int n_cu = 0;
+  if ((rc = device_cus(dev, &n_cu))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the counter words start from zero; the argument block behind them is written by launch_budget
+  HIP_TRY(hipMemsetAsync(d_work, 0, kBudgetParamsOffset, st));
+  if (d.spp == 0) return RTMI_OK;  // (every budget is capped at 0: nothing to render)
+  HIP_TRY(launch_budget(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, d, d_budget,
+                        reinterpret_cast<uint32_t *>(d_states), d_sum, d_sq, d_samples, d_ray_counts, d_work, st));
+  return RTMI_OK;
+}
+
+int rtmi_budget_plan(const rtmi_frame *f, const rtmi_adaptive_opts *o, const float *d_sum, const float *d_sq,
+                     const uint32_t *d_samples, uint32_t *d_budget, unsigned long long *d_totals, void *stream) {
+  FrameDev d;
+  const int rc = budget_frame(f, d_sum && d_sq && d_samples && d_budget && d_totals,
+                              "null sum, second-moment, sample-count, budget or totals array", &d);
+  if (rc) return rc;
+  if (!o) return fail(RTMI_ERR_INVALID, "null rtmi_adaptive_opts");
+  if (o->size != (int32_t)sizeof(rtmi_adaptive_opts)) return fail(RTMI_ERR_INVALID, "rtmi_adaptive_opts.size does not match this library");
+  if (o->min_samples < 2 || o->max_samples < o->min_samples || o->step < 1 || !(o->tolerance > 0.f) ||
+      !std::isfinite(o->tolerance) || !(o->floor >= 0.f) || !std::isfinite(o->floor))
+    return fail(RTMI_ERR_INVALID, "rtmi_adaptive_opts field out of range (min_samples >= 2, max_samples >= min_samples, step >= 1, "
+                                  "finite tolerance > 0, finite floor >= 0)");
+  HIP_TRY(launch_budget_plan(d, o->min_samples, o->max_samples, o->step, o->tolerance, o->floor, d_sum, d_sq, d_samples,
+                             d_budget, d_totals, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samples, int post_process, float *d_tiles,
+                 void *stream) {
+  FrameDev d;
+  const int rc = budget_frame(f, d_sum && d_samples && d_tiles, "null sum, sample-count or tile array", &d);
+  if (rc) return rc;
+  HIP_TRY(launch_resolve(d, d_sum, d_samples, post_process, d_tiles, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
 int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream) {
   if (!sp || !d_states || !d_tiles) return fail(RTMI_ERR_INVALID, "null argument");

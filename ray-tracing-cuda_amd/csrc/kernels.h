@@ -119,6 +119,21 @@ constexpr size_t kTraceParamsOffset = 256;  // (a 128-byte line of its own, away
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
+// Per-pixel sample budgets (rtmi_render_budget; kernels.hip: budget_kernel), on the query variants with F_DEFOCUS added.
+// fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
+// d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).
+constexpr size_t kBudgetParamsOffset = kTraceParamsOffset;
+hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &fr,
+                         const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
+                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
+// The next pass's budget per work item by the stopping rule of include/rtmi.h; d_totals[2] = {items with a budget, sum of
+// budgets}, zeroed on the stream first.
+hipError_t launch_budget_plan(const FrameDev &fr, int min_samples, int max_samples, int step, float tolerance, float floor,
+                              const float *d_sum, const float *d_sq, const uint32_t *d_samples, uint32_t *d_budget,
+                              unsigned long long *d_totals, hipStream_t stream);
+// d_tiles = d_sum / d_samples per work item (0 where there are none), post != 0: then sqrt(clamp(., 0, 1)).
+hipError_t launch_resolve(const FrameDev &fr, const float *d_sum, const uint32_t *d_samples, int post, float *d_tiles,
+                          hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

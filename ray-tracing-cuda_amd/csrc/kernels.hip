@@ -197,6 +197,29 @@ __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void trace_
                        kp->origins, kp->dirs, kp->tex_layers != 0);
 }
 
+// rtmi_render_budget: the same body in its budget mode, its argument block read from the call's own d_work as the trace
+// kernel's is.  F always holds F_DEFOCUS (launch_budget): whether a sample draws a lens offset is decided by the
+// wave-uniform sc.cam.defocus at run time, so the eight query variants serve both cameras.
+struct BudgetParams {
+  RenderParams rp;
+  const uint32_t *budget;
+  float *sq;
+  uint32_t *samples;
+  int32_t tex_layers;  // as TraceParams::tex_layers
+};
+static_assert(kBudgetParamsOffset + sizeof(BudgetParams) <= (size_t)RTMI_BUDGET_WORK_WORDS * 8u,
+              "RTMI_BUDGET_WORK_WORDS must hold the budget kernel's argument block");
+static_assert(kBudgetParamsOffset % alignof(BudgetParams) == 0, "the argument block is aligned in d_work");
+__global__ void budget_params_write_kernel(BudgetParams p, BudgetParams *dst) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
+}
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void budget_kernel(const BudgetParams *p) {
+  const BudgetParams *kp = (const BudgetParams *)(const RT_CONSTANT BudgetParams *)(uintptr_t)p;
+  render_body<F, false, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
+                              nullptr, nullptr, kp->tex_layers != 0, kp->budget, kp->sq, kp->samples);
+}
+
 // ------------------------------------------------------------------ untile / post
 template <typename E, int C>
 __global__ __launch_bounds__(256) void untile_kernel(FrameDev fr, const E *__restrict__ tiles, E *__restrict__ image) {
@@ -940,6 +963,124 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
     hipLaunchKernelGGL(trace_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const TraceParams *)dp);
     return hipGetLastError();
   });
+}
+
+// ------------------------------------------------------------------ per-pixel sample budgets (rtmi_render_budget)
+// render_body.h in its budget mode on the query variants + F_DEFOCUS, launched as launch_trace launches: a persistent
+// grid sized by occupancy, the lanes refilling from the call's own queue cursor (d_work[2]) in image order.  A pixel is
+// a serial chain, so a call lasts at least as long as its largest budget x that pixel's rays per sample.
+hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
+                         const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
+                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
+  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value | F_DEFOCUS;
+    FrameDev fr = frame;
+    fr.post = 0, fr.k_begin = 0, fr.k_end = fr.spp;
+    const int64_t n = fr.items;
+    int threads = 0, per_cu = 0;  // (the workgroup size that keeps the most lanes resident: launch_trace)
+    for (int t = 256; t >= 64; t /= 2) {
+      size_t lds_t = 0;
+      (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
+      int nb = 0;
+      if (lds_t > 160 * 1024 || dynamic_lds<budget_kernel<F>>(lds_t) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, budget_kernel<F>, t, lds_t) != hipSuccess)
+        nb = 0;
+      if (t * nb > threads * per_cu) threads = t, per_cu = nb;
+    }
+    if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
+    size_t lds = 0;
+    LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
+    lc.lane_stride = 1;
+    // items per atomic: a pixel of a few samples is as short as a ray of rtmi_trace; longer ones as launch_render's image order
+    const int per_atomic = fr.spp < 32 ? 256 / (fr.spp > 0 ? fr.spp : 1) : 64 / fr.spp;
+    lc.fetch_batch = per_atomic < 1 ? 1 : per_atomic > 64 ? 64 : per_atomic;
+    lc.rate_scale = 1.f;
+    const hipError_t e = dynamic_lds<budget_kernel<F>>(lds);
+    if (e != hipSuccess) return e;
+    const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
+    const int blocks = (int)(want < cap ? want : cap);
+    BudgetParams bp;
+    bp.rp.sc = sc, bp.rp.fr = fr, bp.rp.lc = lc;
+    bp.rp.states = d_states, bp.rp.out = d_sum, bp.rp.ray_counts = d_ray_counts, bp.rp.counters = d_work;
+    bp.budget = d_budget, bp.sq = d_sq, bp.samples = d_samples, bp.tex_layers = tex_layers ? 1 : 0;
+    BudgetParams *dp = reinterpret_cast<BudgetParams *>(reinterpret_cast<char *>(d_work) + kBudgetParamsOffset);
+    hipLaunchKernelGGL(budget_params_write_kernel, dim3(1), dim3(64), 0, stream, bp, dp);
+    hipLaunchKernelGGL(budget_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const BudgetParams *)dp);
+    return hipGetLastError();
+  });
+}
+
+// The stopping rule of include/rtmi.h (rtmi_budget_plan), operation by operation in binary32 (the file is compiled
+// without contraction and with IEEE division; the intrinsics say so where it matters).  One lane per work item; the
+// totals by a wave reduction and one atomic pair per wave.
+__global__ __launch_bounds__(256) void budget_plan_kernel(FrameDev fr, uint32_t min_n, uint32_t max_n, uint32_t step, float tol,
+                                                           float flr, const float *__restrict__ sum,
+                                                           const float *__restrict__ sq, const uint32_t *__restrict__ samples,
+                                                           uint32_t *__restrict__ budget, unsigned long long *__restrict__ totals) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t b = 0u;
+  if (q < fr.items) {
+    if (frame_pixel_of_rank(fr, fr.rank, q) >= 0) {
+      const uint32_t n = samples[q];
+      if (n < min_n) {
+        b = min_n - n;
+      } else if (n < max_n) {
+        const float nf = (float)n;
+        const float tt = __fmul_rn(tol, tol), nnff = __fmul_rn(__fmul_rn(nf, nf), __fmul_rn(flr, flr));
+        bool converged = true;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const float S = sum[q * 3 + c], Q = sq[q * 3 + c];
+          const float ss = __fmul_rn(S, S);
+          const float lhs = __fdiv_rn(__fsub_rn(__fmul_rn(nf, Q), ss), __fsub_rn(nf, 1.0f));
+          const float rhs = __fmul_rn(tt, __fadd_rn(ss, nnff));
+          converged = converged && (lhs <= rhs);  // (a NaN on either side: not converged)
+        }
+        if (!converged) b = step < max_n - n ? step : max_n - n;
+      }
+    }
+    budget[q] = b;
+  }
+  unsigned long long live = b > 0u ? 1ull : 0ull, total = b;
+  for (int off = 32; off > 0; off >>= 1) live += __shfl_down(live, off), total += __shfl_down(total, off);
+  if ((threadIdx.x & 63) == 0 && total) {
+    atomicAdd(&totals[0], live);
+    atomicAdd(&totals[1], total);
+  }
+}
+hipError_t launch_budget_plan(const FrameDev &fr, int min_samples, int max_samples, int step, float tolerance, float floor,
+                              const float *d_sum, const float *d_sq, const uint32_t *d_samples, uint32_t *d_budget,
+                              unsigned long long *d_totals, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(d_totals, 0, 2 * sizeof(unsigned long long), stream);
+  if (e != hipSuccess || fr.items == 0) return e;
+  hipLaunchKernelGGL(budget_plan_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, fr, (uint32_t)min_samples,
+                     (uint32_t)max_samples, (uint32_t)step, tolerance, floor, d_sum, d_sq, d_samples, d_budget, d_totals);
+  return hipGetLastError();
+}
+
+// sum / n per pixel, then the render's own post-processing expressions (render_body.h: the write-back).
+__global__ __launch_bounds__(256) void resolve_kernel(FrameDev fr, const float *__restrict__ sum,
+                                                       const uint32_t *__restrict__ samples, int post,
+                                                       float *__restrict__ tiles) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= fr.items) return;
+  V3 c = splat(0.f);
+  const uint32_t n = frame_pixel_of_rank(fr, fr.rank, q) >= 0 ? samples[q] : 0u;
+  if (n > 0u) {
+    c = mk(sum[q * 3 + 0], sum[q * 3 + 1], sum[q * 3 + 2]) / (float)n;
+    if (post) {
+      c = mk(clamp1(c.x, 0.f, 1.f), clamp1(c.y, 0.f, 1.f), clamp1(c.z, 0.f, 1.f));
+      c = mk(sqrtf(c.x), sqrtf(c.y), sqrtf(c.z));
+    }
+  }
+  tiles[q * 3 + 0] = c.x, tiles[q * 3 + 1] = c.y, tiles[q * 3 + 2] = c.z;
+}
+hipError_t launch_resolve(const FrameDev &fr, const float *d_sum, const uint32_t *d_samples, int post, float *d_tiles,
+                          hipStream_t stream) {
+  if (fr.items == 0) return hipSuccess;
+  hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, fr, d_sum, d_samples, post,
+                     d_tiles);
+  return hipGetLastError();
 }
 
 }  // namespace rtmi

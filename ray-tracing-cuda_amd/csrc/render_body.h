@@ -1,9 +1,11 @@
 // The persistent per-pixel trace loop.  Included by kernels.hip inside namespace rtmi, after closest_hit.h
 // (not a stand-alone header).
 //
-// render_body<F, RAYS>: RAYS = false is the render (render_kernel, probe_kernel); RAYS = true is rtmi_trace
+// render_body<F, RAYS, BUDGET>: neither is the render (render_kernel, probe_kernel); RAYS is rtmi_trace
 // (trace_kernel): work item q is the caller's ray q instead of a pixel, traced once from the ray it is given -- no
-// camera, no jitter -- with the same bounce, shading, layer stack and fold, one copy of them for both.
+// camera, no jitter -- with the same bounce, shading, layer stack and fold, one copy of them for both.  BUDGET is
+// rtmi_render_budget (budget_kernel): a work item is a pixel as in the render, but how many samples it gets is its own
+// word of a budget map, and the sums, second moments, sample and ray counts it finds in the buffers are carried on.
 #pragma once
 
 // ================================================================== trace kernel
@@ -131,15 +133,22 @@ __device__ __forceinline__ bool finite3(V3 v) {
 // RAYS (rtmi_trace): fr.items rays, fr.spp = 1, fr.k_begin = 0, fr.k_end = 1, fr.post = 0; ray_o / ray_d float[items][3];
 // counters is the call's d_work: [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's cursor (a
 // render's counters hold the cursor in [0] and the abandoned searches in [2]).  The list queue serves every variant.
-// tex_layers (RAYS only): false keeps the untextured id stack in an F_TEX variant -- for scenes without image textures,
+// tex_layers (RAYS, BUDGET): false keeps the untextured id stack in an F_TEX variant -- for scenes without image textures,
 // whose layers are material ids (launch_trace: a quarter or less of the 32-bit layer words' LDS).
-template <uint32_t F, bool RAYS = false>
+// BUDGET (rtmi_render_budget): the frame's items, fr.k_begin = 0, fr.post = 0, fr.spp = fr.k_end = the cap on one call's
+// samples per pixel; budget uint32[items]; out (sums), sq (second moments, nullable), samples, ray_counts (nullable) all
+// ACCUMULATE; counters is the call's d_work, laid out and served as for RAYS (the list queue, every variant; tex_layers).
+template <uint32_t F, bool RAYS = false, bool BUDGET = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
                                             unsigned long long *__restrict__ counters,
                                             const float *__restrict__ ray_o = nullptr,
-                                            const float *__restrict__ ray_d = nullptr, bool tex_layers = true) {
+                                            const float *__restrict__ ray_d = nullptr, bool tex_layers = true,
+                                            const uint32_t *__restrict__ budget = nullptr,
+                                            float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr) {
+  static_assert(!(RAYS && BUDGET), "one work-item source at a time");
+  constexpr bool QUEUE = RAYS || BUDGET;  // the call owns its device state (d_work) and draws from the list queue
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   MatRec *s_mats = reinterpret_cast<MatRec *>(smem);
   // id stack: byte offset of entry [level][thread] in LDS, kept as 32-bit arithmetic (pointer
@@ -218,6 +227,12 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   bool has_px = false, done = false, active = false;
   bool heavy = false;  // a pixel of the queue's sparse head (see below)
   V3 color = splat(0.f);
+  V3 moment = splat(0.f);  // (BUDGET) the running sum of squares, per channel
+  int k_end_px = 0;        // (BUDGET) the lane's own last sample index: min(budget[q], fr.spp)
+  auto k_end = [&]() -> int {
+    if constexpr (BUDGET) return k_end_px;
+    else return fr.k_end;
+  };
   uint32_t rays = 0;
   Rng rng = {0, 0, 0, 0, 0, 0};
   // per-lane path state
@@ -231,7 +246,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // (round 2 kept 64 x 3 floats of private memory per lane for this: 8.2 TB of scratch traffic per launch of a C5
   // shard, 43 % of the waves' time spent waiting.)  Image-textured scenes: a layer is one 32-bit word in LDS,
   // [level][thread] -- the material id, or bit 31 + the sampled texel's three bytes (trace_helpers.h: tex_fetch).
-  const bool tex32 = (F & F_TEX) && (!RAYS || tex_layers);  // the layer stack holds 32-bit words (else material ids)
+  const bool tex32 = (F & F_TEX) && (!QUEUE || tex_layers);  // the layer stack holds 32-bit words (else material ids)
   auto tex_layer_offset = [&](int level) -> uint32_t {
     return (uint32_t)lc.stack_off + (((uint32_t)level * n_threads + threadIdx.x) << 2);
   };
@@ -281,7 +296,12 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       o = ro, d = nd;  // (the lane holds no path while it takes an item: o, d carry the ray to the path's start)
     }
     int64_t idx = RAYS ? 0 : frame_pixel_of_rank(fr, fr.rank, q);
-    if (idx < 0 || fr.spp <= 0) {
+    if constexpr (BUDGET) {  // padding, or nothing to sample: nothing of the item is read or written
+      if (idx < 0) return false;
+      const uint32_t b = budget[q];
+      k_end_px = (int)(b < (uint32_t)fr.spp ? b : (uint32_t)fr.spp);
+      if (k_end_px <= 0) return false;
+    } else if (idx < 0 || fr.spp <= 0) {
       out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
       if (ray_counts) ray_counts[q] = 0;
       return false;
@@ -300,6 +320,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     if (fr.k_begin > 0) {  // (wave-uniform) resume: the first pass left the pixel's raw sum and ray count in the buffers
       color = mk(out[q * 3 + 0], out[q * 3 + 1], out[q * 3 + 2]);
       rays = ray_counts[q] & 0x7fffffffu;  // (bit 31: the scheduler's head mark on a mesh frame)
+    }
+    if constexpr (BUDGET) {  // carry on from the sums the earlier calls left (rays: this call's, added at the write-back)
+      color = mk(out[q * 3 + 0], out[q * 3 + 1], out[q * 3 + 2]);
+      if (sq) moment = mk(sq[q * 3 + 0], sq[q * 3 + 1], sq[q * 3 + 2]);
     }
     has_px = true;
     return true;
@@ -320,7 +344,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // lane_stride lanes, so that every SIMD gets a wave and a wave's shared candidate tests serve 16 rays with 64 lanes
   // instead of 64 rays on a quarter of the SIMDs.  The idle lanes never fetch; they work in closest_hit.
   if (!(F & F_BVH) && lc.lane_stride > 1 && (threadIdx.x & (uint32_t)(lc.lane_stride - 1)) != 0u) done = true;
-  if (!RAYS && !(F & F_BVH) && lc.chain_next != nullptr) {  // planned chains: this wave's chain and its first tile
+  if (!QUEUE && !(F & F_BVH) && lc.chain_next != nullptr) {  // planned chains: this wave's chain and its first tile
     const int chain = wave_chain_id(lc.prio_tab, counters + 35, lc.plan_simds, lc.plan_rounds);
     const int32_t t = chain >= 0 ? lc.chain_first[chain] : -1;
     heavy = t < 0;
@@ -339,19 +363,19 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       // -- with the scheduler's probe behind the launch, its tile's rays per sample stand in as 64 samples' worth of
       // prior -- and, on a planned chain, what the probe said of the tiles still to come
       float left = 0.f;
-      if (has_px && (active || k < fr.k_end)) {
+      if (has_px && (active || k < k_end())) {
         float prior_rays = 8.f, prior_n = 1.f;
         if (lc.tile_cost != nullptr) prior_rays = 64.f * ((float)lc.tile_cost[q32 >> 6] * lc.rate_scale), prior_n = 64.f;
-        left = ((float)rays + prior_rays) * (float)(fr.k_end - k + 1) * __builtin_amdgcn_rcpf((float)k + prior_n);
+        left = ((float)rays + prior_rays) * (float)(k_end() - k + 1) * __builtin_amdgcn_rcpf((float)k + prior_n);
         if (!(F & F_BVH) && lc.chain_next != nullptr && !heavy) left += (float)lc.chain_fut[q32 >> 6];
       }
       wave_priority_update(lc.prio_tab, (uint32_t)fminf(left, 4.0e9f));
     }
     // -------------------------------------------------------- sample / pixel bookkeeping
-    if (!active && !done && has_px && k >= fr.k_end) {
+    if (!active && !done && has_px && k >= k_end()) {
       const int64_t q = (int64_t)q32;
       V3 c = color;
-      if (fr.post && fr.k_end >= fr.spp) {  // ray_tracing.cu:78-83 (a first pass leaves the raw sum)
+      if (!BUDGET && fr.post && fr.k_end >= fr.spp) {  // ray_tracing.cu:78-83 (a first pass leaves the raw sum)
         c = c / (float)fr.spp;
         c = mk(clamp1(c.x, 0.f, 1.f), clamp1(c.y, 0.f, 1.f), clamp1(c.z, 0.f, 1.f));
         c = mk(sqrtf(c.x), sqrtf(c.y), sqrtf(c.z));
@@ -359,7 +383,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       out[q * 3 + 0] = c.x;
       out[q * 3 + 1] = c.y;
       out[q * 3 + 2] = c.z;
-      if (ray_counts) ray_counts[q] = rays;
+      if constexpr (BUDGET) {
+        if (sq) sq[q * 3 + 0] = moment.x, sq[q * 3 + 1] = moment.y, sq[q * 3 + 2] = moment.z;
+        samples[q] += (uint32_t)k;
+        if (ray_counts) ray_counts[q] += rays;
+      } else if (ray_counts) ray_counts[q] = rays;
       if ((F & F_BVH) && lc.visit_counts != nullptr) lc.visit_counts[q] = work_px;
       // the lane's ray total in ONE register: 2^31 at a time goes to the global counter (a constant addend: the
       // compiler's wave-level combining of atomics needs no scan for it), the rest at the end of the kernel
@@ -376,9 +404,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       states[5 * n_items + q] = rng.v4;
       has_px = false;
     }
-    const bool wave_heavy = !RAYS && (F & F_BVH) && lc.exclusive &&
-                            __builtin_amdgcn_ballot_w64(has_px && heavy && (active || k < fr.k_end)) != 0ull;
-    if (!RAYS && (F & F_BVH) && classes) {
+    const bool wave_heavy = !QUEUE && (F & F_BVH) && lc.exclusive &&
+                            __builtin_amdgcn_ballot_w64(has_px && heavy && (active || k < k_end())) != 0ull;
+    if (!QUEUE && (F & F_BVH) && classes) {
       const bool wants = !active && !done && !has_px;
       if (__builtin_amdgcn_ballot_w64(wants) != 0ull) {
         if (head_open)
@@ -388,7 +416,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         // before each round
         for (int round = 0; round < 4; round++) {
           const int lvl = round == 0 ? 64 : round == 1 ? 32 : round == 2 ? 16 : 1;
-          const bool live_px = has_px && (active || k < fr.k_end);
+          const bool live_px = has_px && (active || k < k_end());
           int wave_cls = 1;
           if (lc.exclusive) {
             if (__builtin_amdgcn_ballot_w64(live_px && cls == 16) != 0ull) wave_cls = 16;
@@ -426,7 +454,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
       }
-    } else if (!RAYS && !(F & F_BVH) && lc.chain_next != nullptr) {  // (wave-uniform) planned chains
+    } else if (!QUEUE && !(F & F_BVH) && lc.chain_next != nullptr) {  // (wave-uniform) planned chains
       const uint32_t me = ((blockIdx.x * n_threads + threadIdx.x) >> 6) + 1u;  // this wave's mark in `claims`
       if (!active && !has_px && !heavy) {  // (`heavy` in this mode: the lane has walked its chain to the end)
         for (;;) {
@@ -458,8 +486,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           if (__builtin_amdgcn_ballot_w64(has_px) != 0ull) break;  // (a tile of padding only: look further)
         }
       }
-    } else if (RAYS || !(F & F_BVH)) {
-      // The queue of a list frame (and of rtmi_trace's rays, every variant), drawn by the WAVE: one atomic takes the
+    } else if (QUEUE || !(F & F_BVH)) {
+      // The queue of a list frame (and of rtmi_trace's rays and rtmi_render_budget's pixels, every variant), drawn by the WAVE: one atomic takes the
       // next `batch` items for all its lanes, which help themselves from that pool as they finish their pixels.  Every atomic on the queue's cursor is a round
       // trip to the one L2 channel that owns its line, and they are served there one after the other (5.5 ns each,
       // measured): with one per pixel a first pass of two samples over a million pixels was 3.8 ms of atomics around
@@ -479,7 +507,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
             batch = batch < 1u ? 1u : batch > (uint32_t)lc.fetch_batch ? (uint32_t)lc.fetch_batch : batch;
             const uint32_t asked = (uint32_t)__popcll(wm);  // (never less than the lanes that are waiting right now)
             batch = batch < asked ? asked : batch;
-            if ((threadIdx.x & 63u) == 0u) nq = atomicAdd(&counters[RAYS ? 2 : 0], (unsigned long long)batch);
+            if ((threadIdx.x & 63u) == 0u) nq = atomicAdd(&counters[QUEUE ? 2 : 0], (unsigned long long)batch);
             nq = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(nq >> 32)) << 32) |
                  (uint32_t)__builtin_amdgcn_readfirstlane((int)nq);
             if (nq < (unsigned long long)n_items) {
@@ -592,7 +620,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && ll != nullptr && sc.n_pairs >= kCullMinPairs) ||
                               ((F & F_SGROUP) && cands != nullptr);  // wave-uniform
     if (all_lanes_in)  // every lane goes in, with or without a ray of its own: see closest_hit
-      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (RAYS ? 0 : 2), o, d, active,
+      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (QUEUE ? 0 : 2), o, d, active,
                          (F & F_BVH) && lc.visit_counts != nullptr
 #ifdef RTMI_STATS
                          , st
@@ -606,7 +634,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     // disagreement.  counters[33] += rays re-done, counters[34] += disagreements (rtmi_debug_counters).
     // Mesh variants: the second answer walks the reference's own tree (closest_hit.h: bvh_reference_walk), thousands
     // of triangle tests per ray -- for small frames (tools/gpu_check_margins.py).
-    if (!RAYS && all_lanes_in && (check_tick++ % RTMI_CHECK_EVERY) == 0u) {  // (rtmi_trace: d_work has no words 33, 34)
+    if (!QUEUE && all_lanes_in && (check_tick++ % RTMI_CHECK_EVERY) == 0u) {  // (rtmi_trace, rtmi_render_budget: d_work has no words 33, 34)
       const Hit h2 = closest_hit<F>(sc, s_nodes, 0, s_paths, 0, nullptr, nullptr, nullptr, nullptr, nullptr, o, d, active, false
 #ifdef RTMI_STATS
                                     , st
@@ -864,6 +892,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
         color = color + result;
+        if constexpr (BUDGET)  // the product and the sum rounded separately, so that a binary32 restatement is exact
+          moment = mk(__fadd_rn(moment.x, __fmul_rn(result.x, result.x)), __fadd_rn(moment.y, __fmul_rn(result.y, result.y)),
+                      __fadd_rn(moment.z, __fmul_rn(result.z, result.z)));
         active = false;
       }
     }
@@ -877,7 +908,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     if ((threadIdx.x & 63) == 0 && ray_total) atomicAdd(&counters[1], ray_total);
   }
 #ifdef RTMI_STATS
-  if (!RAYS && (threadIdx.x & 63) == 0) {  // (rtmi_trace: d_work has no statistics words)
+  if (!QUEUE && (threadIdx.x & 63) == 0) {  // (rtmi_trace, rtmi_render_budget: d_work has no statistics words)
     const unsigned v[13] = {wave_queries, st.searches, st.node_steps, st.face_steps, st.nodes_popped, st.blocks_popped,
                             st.insert_rounds, st.steps_hist[0], st.steps_hist[1], st.steps_hist[2], st.steps_hist[3],
                             st.steps_hist[4], st.steps_hist[5]};

@@ -20,6 +20,7 @@ TILE = 8
 STATE_WORDS = 6
 MAX_DEPTH = 64
 TRACE_WORK_WORDS = 256  # RTMI_TRACE_WORK_WORDS: the device words of one rtmi_trace call
+BUDGET_WORK_WORDS = TRACE_WORK_WORDS  # RTMI_BUDGET_WORK_WORDS: the device words of one rtmi_render_budget call
 MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
 
 # rtmi_hit.kind (include/rtmi.h)
@@ -65,6 +66,16 @@ def render_opts(schedule=-1, blocks_per_cu=0, threads_per_block=0, sparse_stride
         o.d_scratch = scratch.data_ptr()
         o.scratch_bytes = scratch.numel() * scratch.element_size()
     return o
+
+
+class AdaptiveOpts(C.Structure):
+    """rtmi_adaptive_opts of include/rtmi.h (the stopping rule of rtmi_budget_plan)."""
+    _fields_ = [("size", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("step", C.c_int32),
+                ("tolerance", C.c_float), ("floor", C.c_float)]
+
+
+def adaptive_opts(min_spp, max_spp, step, tolerance, floor=0.01):
+    return AdaptiveOpts(C.sizeof(AdaptiveOpts), int(min_spp), int(max_spp), int(step), float(tolerance), float(floor))
 
 
 TRANSFORM_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p)
@@ -142,6 +153,11 @@ SYMBOLS = [
     ("rtmi_trace", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p]),
     ("rtmi_rng_init_n", C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("rtmi_render_budget", C.c_int, [C.c_void_p, _frp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_budget_plan", C.c_int, [_frp, C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    ("rtmi_resolve", C.c_int, [_frp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -249,6 +265,11 @@ class Trace:
 
     def total_rays(self):
         return int(self.work[1].item())
+
+
+class Adaptive(collections.namedtuple("Adaptive", "tiles samples passes total_samples")):
+    """What ``Renderer.render_adaptive`` returns: ``tiles`` (items, 3) float32, the resolved tile buffer; ``samples``
+    (items,) int32, the samples each work item got; ``passes`` rendered; ``total_samples`` over the shard."""
 
 
 def rng_states(seed, n, first=0, device=None):
@@ -579,11 +600,87 @@ class Renderer:
         return self
 
     def check(self):
-        """Wait for the last render and raise if it reported an incomplete frame (rtmi_render_status)."""
+        """Wait for the last render and raise if it reported an incomplete frame (rtmi_render_status); with budget
+        renders behind it (``render_budget``), also if any of them abandoned a mesh search."""
+        if getattr(self, "budget_abandoned", None) is not None:
+            n = int(self.budget_abandoned.item())  # (a device-to-host copy: waits for the calls)
+            if n:
+                raise RtmiError("rtmi_render_budget abandoned %d mesh search(es): the sums are incomplete" % n)
         with self.torch.cuda.device(self.device):
             _check(self.L.rtmi_render_status(self.scene.h, C.c_void_p(getattr(self, "_last_scratch", None)), None,
                                              self._stream()), "rtmi_render_status")
         return self
+
+    # -------------------------------------------------------------- per-pixel sample budgets
+    def _budget_buffers(self):
+        if getattr(self, "sum", None) is None:
+            torch, n, dev = self.torch, self.items, self.device
+            self.sum = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+            self.sq = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+            self.samples = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.budget_rays = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.d_work = torch.zeros((BUDGET_WORK_WORDS,), dtype=torch.int64, device=dev)
+            self.budget_abandoned = torch.zeros((), dtype=torch.int64, device=dev)  # d_work[0] over all calls
+            self.budget = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.totals = torch.zeros((2,), dtype=torch.int64, device=dev)
+
+    def render_budget(self, budget, count_rays=True):
+        """``budget[q]`` more samples (at most the frame's spp per call) of every pixel q of this shard
+        (rtmi_render_budget), enqueued on torch's current stream: continues each pixel's RNG stream in ``states`` and
+        adds to ``sum`` (radiance), ``sq`` (squares), ``samples`` and, with ``count_rays``, ``budget_rays`` -- zeroed
+        on first use and kept as attributes.  ``budget``: a contiguous (items,) int32 CUDA tensor.  The frame must
+        have been made with ``post=False``."""
+        torch = self.torch
+        if not _is_buffer(budget, (self.items,), self.device, torch.int32):
+            raise RtmiError("budget must be a contiguous CUDA int32 tensor of shape (items,) on the renderer's device")
+        self._budget_buffers()
+        with torch.cuda.device(self.device):
+            _check(self.L.rtmi_render_budget(self.scene.h, C.byref(self.frame), C.c_void_p(budget.data_ptr()),
+                                             C.c_void_p(self.states.data_ptr()), C.c_void_p(self.sum.data_ptr()),
+                                             C.c_void_p(self.sq.data_ptr()), C.c_void_p(self.samples.data_ptr()),
+                                             C.c_void_p(self.budget_rays.data_ptr()) if count_rays else None,
+                                             C.c_void_p(self.d_work.data_ptr()), self._stream()), "rtmi_render_budget")
+            self.budget_abandoned += self.d_work[0]  # (stream-ordered: the next call resets d_work)
+        return self
+
+    def plan(self, min_spp, max_spp, step, tolerance, floor=0.01):
+        """The next pass's budget from the sums so far (rtmi_budget_plan; the rule is in include/rtmi.h).  Returns
+        (budget tensor, pixels with a budget, sum of the budgets); reading the two totals waits for the stream."""
+        self._budget_buffers()
+        o = adaptive_opts(min_spp, max_spp, step, tolerance, floor)
+        with self.torch.cuda.device(self.device):
+            _check(self.L.rtmi_budget_plan(C.byref(self.frame), C.byref(o), C.c_void_p(self.sum.data_ptr()),
+                                           C.c_void_p(self.sq.data_ptr()), C.c_void_p(self.samples.data_ptr()),
+                                           C.c_void_p(self.budget.data_ptr()), C.c_void_p(self.totals.data_ptr()),
+                                           self._stream()), "rtmi_budget_plan")
+            active, total = self.totals.tolist()
+        return self.budget, active, total
+
+    def resolve(self, post=True):
+        """(items, 3) tile buffer: sum / samples per pixel, post-processed like a render's (rtmi_resolve)."""
+        self._budget_buffers()
+        out = self.torch.empty((self.items, 3), dtype=self.torch.float32, device=self.device)
+        with self.torch.cuda.device(self.device):
+            _check(self.L.rtmi_resolve(C.byref(self.frame), C.c_void_p(self.sum.data_ptr()),
+                                       C.c_void_p(self.samples.data_ptr()), 1 if post else 0, C.c_void_p(out.data_ptr()),
+                                       self._stream()), "rtmi_resolve")
+        return out
+
+    def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True):
+        """Plan / render passes until no pixel has a budget left: every pixel gets ``min_spp`` samples, then ``step``
+        more per pass until it meets the stopping rule or has ``max_spp``.  One host read of the plan's totals per
+        pass is the only synchronisation.  The frame's spp must be at least max(min_spp, step)."""
+        if self.frame.spp < max(int(min_spp), int(step)):
+            raise RtmiError("the frame's spp (%d) caps one pass: it must be at least max(min_spp, step)" % self.frame.spp)
+        passes = total = 0
+        while True:
+            budget, active, pass_total = self.plan(min_spp, max_spp, step, tolerance, floor)
+            if active == 0:
+                break
+            self.render_budget(budget)
+            passes, total = passes + 1, total + pass_total
+        self.check()
+        return Adaptive(self.resolve(post), self.samples, passes, total)
 
     def scratch_bytes(self):
         return int(self.L.rtmi_render_scratch_bytes(C.byref(self.frame)))
