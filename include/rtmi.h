@@ -509,6 +509,60 @@ int rtmi_budget_plan(const rtmi_frame *f, const rtmi_adaptive_opts *o, const flo
 int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samples, int post_process, float *d_tiles,
                  void *stream);
 
+/* --------------------------------------------------------------- features --
+ * First-hit feature buffers for a denoiser or compositor: albedo, normal, depth and coverage of the primary hit,
+ * summed over THE VERY SAMPLES that made the pixel's colour (their camera rays are made inside the kernel from the
+ * pixel's RNG stream, so no caller could ask rtmi_intersect for them).  Added without a version change: a caller detects
+ * it by the symbol rtmi_render_features.
+ *
+ * rtmi_render_features is rtmi_render_budget in every respect stated above -- which samples are rendered and the order
+ * of the additions; what padding and budget-0 items leave alone (everything, the feature buffers included); the cap
+ * f->spp; d_work and its layout; the errors.  On top of that, for each rendered sample, with rec the HitRecord of the
+ * sample's primary query world->Hit(camera_ray, 1e-3, INFINITY, &rec) (the first closest-hit query Trace makes for it):
+ *   - no hit: nothing is added to any feature buffer;
+ *   - Sky: d_albedo[q] += Sky's Emit(p), the value Trace returns for that sample (sky.cu:9-14); normal, depth and
+ *     coverage get nothing -- the background is not a surface;
+ *   - any other hitable: d_coverage[q] += 1;  d_depth[q] += (float)rec.t (what rtmi_hit.t reports);  d_normal[q] +=
+ *     rec.normal (what rtmi_hit.normal reports: oriented against the ray for triangles, parallelograms and mesh faces,
+ *     outward for spheres);  d_albedo[q] += the material's own colour at the hit -- Lambertian: its texture's
+ *     Value(u, v, p), the attenuation Scatter would set (an image texture: the texel / 255); Metal: its albedo;
+ *     Dielectric: its colour; DiffuseLight: Emit(u, v, p).  No RNG draw is made for any of this and none is skipped.
+ * Every addition is one binary32 addition per sample and channel, in sample order, starting from the value the buffer
+ * holds: all four buffers ACCUMULATE over calls like d_sum (the caller zeroes them once); d_coverage wraps modulo 2^32.
+ * Each pointer of *feat is nullable.  feat == NULL, or all four null, IS rtmi_render_budget; with any of them non-null
+ * the other outputs -- d_sum, d_sq, d_samples, d_ray_counts, the states, d_work[0] and d_work[1] -- are bit for bit what
+ * rtmi_render_budget would have written.
+ * Errors, before any HIP call, besides rtmi_render_budget's: RTMI_ERR_INVALID for feat->size != sizeof(rtmi_features) or
+ * feat->reserved != 0; RTMI_ERR_DEPTH for max_depth == 0 with any feature buffer non-null -- at depth 0 Trace returns
+ * before it ever looks at the primary record (ray_tracing.cu:23), so there is no first hit to describe. */
+typedef struct rtmi_features {
+  int32_t size;          /* sizeof(rtmi_features) of the caller: must match the library's */
+  int32_t reserved;      /* 0 */
+  float *d_albedo;       /* nullable, float[items][3] */
+  float *d_normal;       /* nullable, float[items][3] */
+  float *d_depth;        /* nullable, float[items]    */
+  uint32_t *d_coverage;  /* nullable, uint32[items]; as rtmi_resolve_features' OUTPUT: the bits of a float (below) */
+} rtmi_features;
+int rtmi_render_features(const rtmi_scene *s, const rtmi_frame *f, const uint32_t *d_budget, void *d_states,
+                         float *d_sum, float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts,
+                         const rtmi_features *feat, unsigned long long *d_work, void *stream);
+/* Per-pixel means of the feature sums, in binary32 with every operation rounded on its own.  With n = d_samples[q],
+ * nf = (float)n, c = sums->d_coverage[q]:
+ *     out->d_albedo[q]   = sums->d_albedo[q] / nf              (per channel)
+ *     out->d_normal[q]   = sums->d_normal[q] / nf              (the MEAN normal: NOT renormalised, so its length says
+ *                                                               how much the samples' normals agree)
+ *     out->d_depth[q]    = c ? sums->d_depth[q] / (float)c : 0 (the mean over the samples that hit a surface)
+ *     out->d_coverage[q] = the BITS OF THE FLOAT (float)c / nf, the alpha -- declared uint32_t * only so that one
+ *                          struct serves both calls; read it as float
+ * Everything is 0 where n == 0 and for padding.  A null pointer in *out skips that buffer.  RTMI_ERR_INVALID before
+ * any HIP call for a bad frame, a null sums, out or d_samples, a wrong size or non-zero reserved in either struct, and
+ * for a non-null out buffer whose sums twin is null (out->d_depth and out->d_coverage both need sums->d_coverage).
+ * All buffers are tile-major per shard, float[items][3] or 32-bit [items]: rtmi_untile takes the two 3-channel ones as
+ * they are, rtmi_untile_u32 takes depth and alpha by their bits, rtmi_gather moves the 3-channel ones.
+ * Asynchronous on `stream`. */
+int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const uint32_t *d_samples,
+                          const rtmi_features *out, void *stream);
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

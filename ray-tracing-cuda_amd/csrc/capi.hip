@@ -954,13 +954,31 @@ static int budget_frame(const rtmi_frame *f, bool arrays, const char *null_array
   return RTMI_OK;
 }
 
-int rtmi_render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
-                       float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
+// rtmi_features -> FeatureBufs; false: the struct is not this library's (size) or its reserved word is set.
+static bool feature_bufs(const rtmi_features *feat, FeatureBufs *fb) {
+  static_assert(sizeof(rtmi_features) == 40, "rtmi_features is 40 bytes");
+  *fb = FeatureBufs{};
+  if (!feat) return true;
+  if (feat->size != (int32_t)sizeof(rtmi_features) || feat->reserved != 0) return false;
+  fb->albedo = feat->d_albedo, fb->normal = feat->d_normal, fb->depth = feat->d_depth, fb->coverage = feat->d_coverage;
+  return true;
+}
+static const char *const kBadFeatures = "rtmi_features.size does not match this library, or reserved is not 0";
+
+int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
+                         float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, const rtmi_features *feat,
+                         unsigned long long *d_work, void *stream) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  FeatureBufs fb;
+  if (!feature_bufs(feat, &fb)) return fail(RTMI_ERR_INVALID, kBadFeatures);
+  const bool features = fb.albedo || fb.normal || fb.depth || fb.coverage;
   FrameDev d;
   int rc = budget_frame(f, d_budget && d_states && d_sum && d_samples && d_work,
                         "null budget, state, sum, sample-count or work array", &d);
   if (rc) return rc;
+  // (before the scene is looked at: max_depth is the frame's, and at depth 0 Trace never looks at the primary record)
+  if (features && d.max_depth == 0)
+    return fail(RTMI_ERR_DEPTH, "max_depth must be at least 1 with a feature buffer: at depth 0 Trace never looks at the primary hit");
   const Scene *s = S(sp);
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   if (d.max_depth < 0 || d.max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
@@ -978,7 +996,27 @@ int rtmi_render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t
   HIP_TRY(hipMemsetAsync(d_work, 0, kBudgetParamsOffset, st));
   if (d.spp == 0) return RTMI_OK;  // (every budget is capped at 0: nothing to render)
   HIP_TRY(launch_budget(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, d, d_budget,
-                        reinterpret_cast<uint32_t *>(d_states), d_sum, d_sq, d_samples, d_ray_counts, d_work, st));
+                        reinterpret_cast<uint32_t *>(d_states), d_sum, d_sq, d_samples, d_ray_counts, &fb, d_work, st));
+  return RTMI_OK;
+}
+
+int rtmi_render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
+                       float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
+  return rtmi_render_features(sp, f, d_budget, d_states, d_sum, d_sq, d_samples, d_ray_counts, nullptr, d_work, stream);
+}
+
+int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const uint32_t *d_samples,
+                          const rtmi_features *out, void *stream) {
+  FrameDev d;
+  const int rc = budget_frame(f, sums && out && d_samples, "null feature sums, sample-count array or output struct", &d);
+  if (rc) return rc;
+  FeatureBufs in, to;
+  if (!feature_bufs(sums, &in) || !feature_bufs(out, &to)) return fail(RTMI_ERR_INVALID, kBadFeatures);
+  if ((to.albedo && !in.albedo) || (to.normal && !in.normal) || (to.depth && !in.depth) ||
+      ((to.depth || to.coverage) && !in.coverage))
+    return fail(RTMI_ERR_INVALID, "an output feature buffer without its sums (depth and alpha also need the coverage sums)");
+  if (d.items == 0) return RTMI_OK;
+  HIP_TRY(launch_resolve_features(d, in, d_samples, to, (hipStream_t)stream));
   return RTMI_OK;
 }
 

@@ -125,7 +125,12 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
 constexpr size_t kBudgetParamsOffset = kTraceParamsOffset;
 hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &fr,
                          const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
-                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
+                         uint32_t *d_ray_counts, const FeatureBufs *feat, unsigned long long *d_work, hipStream_t stream);
+// feat (rtmi_render_features; nullable): with any buffer of it non-null the launch is feature_kernel, budget_kernel's
+// twin that also adds each sample's primary-hit albedo, normal, depth and coverage into them; else budget_kernel.
+// Per-item means of those sums (rtmi_resolve_features): null buffers of `out` are skipped.
+hipError_t launch_resolve_features(const FrameDev &fr, const FeatureBufs &sums, const uint32_t *d_samples,
+                                   const FeatureBufs &out, hipStream_t stream);
 // The next pass's budget per work item by the stopping rule of include/rtmi.h; d_totals[2] = {items with a budget, sum of
 // budgets}, zeroed on the stream first.
 hipError_t launch_budget_plan(const FrameDev &fr, int min_samples, int max_samples, int step, float tolerance, float floor,

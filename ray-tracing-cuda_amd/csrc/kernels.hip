@@ -206,6 +206,7 @@ struct BudgetParams {
   float *sq;
   uint32_t *samples;
   int32_t tex_layers;  // as TraceParams::tex_layers
+  FeatureBufs feat;    // rtmi_render_features: read by feature_kernel only (all null for budget_kernel)
 };
 static_assert(kBudgetParamsOffset + sizeof(BudgetParams) <= (size_t)RTMI_BUDGET_WORK_WORDS * 8u,
               "RTMI_BUDGET_WORK_WORDS must hold the budget kernel's argument block");
@@ -218,6 +219,15 @@ __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)
   const BudgetParams *kp = (const BudgetParams *)(const RT_CONSTANT BudgetParams *)(uintptr_t)p;
   render_body<F, false, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
                               nullptr, nullptr, kp->tex_layers != 0, kp->budget, kp->sq, kp->samples);
+}
+// rtmi_render_features: budget_kernel's twin with the FEATURES flag of the body set -- at a sample's primary hit the lane
+// adds the hit's albedo, normal, depth and coverage into its item's words of kp->feat.  A kernel of its own, so that
+// budget_kernel stays instruction for instruction what it is.
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void feature_kernel(const BudgetParams *p) {
+  const BudgetParams *kp = (const BudgetParams *)(const RT_CONSTANT BudgetParams *)(uintptr_t)p;
+  render_body<F, false, true, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
+                                    nullptr, nullptr, kp->tex_layers != 0, kp->budget, kp->sq, kp->samples, &kp->feat);
 }
 
 // ------------------------------------------------------------------ untile / post
@@ -969,11 +979,13 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
 // render_body.h in its budget mode on the query variants + F_DEFOCUS, launched as launch_trace launches: a persistent
 // grid sized by occupancy, the lanes refilling from the call's own queue cursor (d_work[2]) in image order.  A pixel is
 // a serial chain, so a call lasts at least as long as its largest budget x that pixel's rays per sample.
-hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
-                         const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
-                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
-  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
-    constexpr uint32_t F = decltype(v)::value | F_DEFOCUS;
+// Kernel: budget_kernel<F>, or feature_kernel<F> (rtmi_render_features with a feature buffer: `feat`).
+template <uint32_t F, auto Kernel>
+static hipError_t launch_budget_as(const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
+                                   const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq,
+                                   uint32_t *d_samples, uint32_t *d_ray_counts, const FeatureBufs &feat,
+                                   unsigned long long *d_work, hipStream_t stream) {
+  {
     FrameDev fr = frame;
     fr.post = 0, fr.k_begin = 0, fr.k_end = fr.spp;
     const int64_t n = fr.items;
@@ -982,8 +994,8 @@ hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, 
       size_t lds_t = 0;
       (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
       int nb = 0;
-      if (lds_t > 160 * 1024 || dynamic_lds<budget_kernel<F>>(lds_t) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, budget_kernel<F>, t, lds_t) != hipSuccess)
+      if (lds_t > 160 * 1024 || dynamic_lds<Kernel>(lds_t) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, t, lds_t) != hipSuccess)
         nb = 0;
       if (t * nb > threads * per_cu) threads = t, per_cu = nb;
     }
@@ -995,7 +1007,7 @@ hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, 
     const int per_atomic = fr.spp < 32 ? 256 / (fr.spp > 0 ? fr.spp : 1) : 64 / fr.spp;
     lc.fetch_batch = per_atomic < 1 ? 1 : per_atomic > 64 ? 64 : per_atomic;
     lc.rate_scale = 1.f;
-    const hipError_t e = dynamic_lds<budget_kernel<F>>(lds);
+    const hipError_t e = dynamic_lds<Kernel>(lds);
     if (e != hipSuccess) return e;
     const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
     const int blocks = (int)(want < cap ? want : cap);
@@ -1003,11 +1015,56 @@ hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, 
     bp.rp.sc = sc, bp.rp.fr = fr, bp.rp.lc = lc;
     bp.rp.states = d_states, bp.rp.out = d_sum, bp.rp.ray_counts = d_ray_counts, bp.rp.counters = d_work;
     bp.budget = d_budget, bp.sq = d_sq, bp.samples = d_samples, bp.tex_layers = tex_layers ? 1 : 0;
+    bp.feat = feat;
     BudgetParams *dp = reinterpret_cast<BudgetParams *>(reinterpret_cast<char *>(d_work) + kBudgetParamsOffset);
     hipLaunchKernelGGL(budget_params_write_kernel, dim3(1), dim3(64), 0, stream, bp, dp);
-    hipLaunchKernelGGL(budget_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const BudgetParams *)dp);
+    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(threads), lds, stream, (const BudgetParams *)dp);
     return hipGetLastError();
+  }
+}
+hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
+                         const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
+                         uint32_t *d_ray_counts, const FeatureBufs *feat, unsigned long long *d_work, hipStream_t stream) {
+  const bool features = feat && (feat->albedo || feat->normal || feat->depth || feat->coverage);
+  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value | F_DEFOCUS;
+    if (features)
+      return launch_budget_as<F, feature_kernel<F>>(sc, tex_layers, n_cu, frame, d_budget, d_states, d_sum, d_sq, d_samples,
+                                                    d_ray_counts, *feat, d_work, stream);
+    return launch_budget_as<F, budget_kernel<F>>(sc, tex_layers, n_cu, frame, d_budget, d_states, d_sum, d_sq, d_samples,
+                                                 d_ray_counts, FeatureBufs{}, d_work, stream);
   });
+}
+
+// Per-pixel means of the feature sums (rtmi_resolve_features; include/rtmi.h states the rule): one lane per work item,
+// every operation in binary32 and rounded on its own.  Null pointers skip their buffer (capi.hip checks the pairs).
+__global__ __launch_bounds__(256) void resolve_features_kernel(FrameDev fr, FeatureBufs sums, const uint32_t *__restrict__ samples,
+                                                                FeatureBufs out) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= fr.items) return;
+  const uint32_t n = frame_pixel_of_rank(fr, fr.rank, q) >= 0 ? samples[q] : 0u;
+  const float nf = (float)n;
+  V3 a = splat(0.f), nm = splat(0.f);
+  float dp = 0.f, alpha = 0.f;
+  if (n > 0u) {
+    if (out.albedo) a = mk(sums.albedo[q * 3 + 0], sums.albedo[q * 3 + 1], sums.albedo[q * 3 + 2]) / nf;
+    if (out.normal) nm = mk(sums.normal[q * 3 + 0], sums.normal[q * 3 + 1], sums.normal[q * 3 + 2]) / nf;
+    if (out.depth || out.coverage) {
+      const uint32_t c = sums.coverage[q];
+      if (out.depth && c) dp = __fdiv_rn(sums.depth[q], (float)c);
+      alpha = __fdiv_rn((float)c, nf);
+    }
+  }
+  if (out.albedo) out.albedo[q * 3 + 0] = a.x, out.albedo[q * 3 + 1] = a.y, out.albedo[q * 3 + 2] = a.z;
+  if (out.normal) out.normal[q * 3 + 0] = nm.x, out.normal[q * 3 + 1] = nm.y, out.normal[q * 3 + 2] = nm.z;
+  if (out.depth) out.depth[q] = dp;
+  if (out.coverage) out.coverage[q] = __float_as_uint(alpha);
+}
+hipError_t launch_resolve_features(const FrameDev &fr, const FeatureBufs &sums, const uint32_t *d_samples,
+                                   const FeatureBufs &out, hipStream_t stream) {
+  if (fr.items == 0) return hipSuccess;
+  hipLaunchKernelGGL(resolve_features_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, fr, sums, d_samples, out);
+  return hipGetLastError();
 }
 
 // The stopping rule of include/rtmi.h (rtmi_budget_plan), operation by operation in binary32 (the file is compiled

@@ -138,7 +138,12 @@ __device__ __forceinline__ bool finite3(V3 v) {
 // BUDGET (rtmi_render_budget): the frame's items, fr.k_begin = 0, fr.post = 0, fr.spp = fr.k_end = the cap on one call's
 // samples per pixel; budget uint32[items]; out (sums), sq (second moments, nullable), samples, ray_counts (nullable) all
 // ACCUMULATE; counters is the call's d_work, laid out and served as for RAYS (the list queue, every variant; tex_layers).
-template <uint32_t F, bool RAYS = false, bool BUDGET = false>
+// FEATURES (rtmi_render_features; BUDGET only): at the primary hit of every sample -- depth == 0, the record of the first
+// closest-hit query Trace makes -- the lane adds the hit's albedo, normal, depth and coverage into its item's own words of
+// the non-null buffers of *feat, one binary32 addition per channel, in sample order.  A read-modify-write in global
+// memory, not running sums in registers: the lane owns the item, so these are plain vector loads and stores, and nothing
+// more is live across closest_hit and the fold than in the budget mode.  No RNG draw is made or skipped.
+template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -146,8 +151,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const float *__restrict__ ray_o = nullptr,
                                             const float *__restrict__ ray_d = nullptr, bool tex_layers = true,
                                             const uint32_t *__restrict__ budget = nullptr,
-                                            float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr) {
+                                            float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr,
+                                            const FeatureBufs *feat = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
+  static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
   constexpr bool QUEUE = RAYS || BUDGET;  // the call owns its device state (d_work) and draws from the list queue
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   MatRec *s_mats = reinterpret_cast<MatRec *>(smem);
@@ -232,6 +239,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   auto k_end = [&]() -> int {
     if constexpr (BUDGET) return k_end_px;
     else return fr.k_end;
+  };
+  auto feature_add3 = [&](float *buf, V3 v) {  // (FEATURES) the lane's item of a 3-channel feature buffer += v
+    float *w = buf + (int64_t)q32 * 3;
+    w[0] = __fadd_rn(w[0], v.x), w[1] = __fadd_rn(w[1], v.y), w[2] = __fadd_rn(w[2], v.z);
   };
   uint32_t rays = 0;
   Rng rng = {0, 0, 0, 0, 0, 0};
@@ -671,6 +682,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           float tg = (float)(0.5 * ((double)dir.y + 1.0));
           float w0 = 1.0f - tg;
           result = mk(w0 * 1.0f + tg * 0.5f, w0 * 1.0f + tg * 0.7f, w0 * 1.0f + tg * 1.0f);
+          if constexpr (FEATURES) {  // the background is not a surface: its colour, and nothing else
+            if (depth == 0 && feat->albedo) feature_add3(feat->albedo, result);
+          }
         } else {
           V3 nrm = splat(0.f);
           int mat = 0;
@@ -750,6 +764,15 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               const uint32_t px = tex_fetch(sc.texs[m.tex], tu, (float)(1.0 - (double)tv));
               layer = 0x80000000u | px;
               if (m.kind == MAT_LIGHT) rgb = texel_rgb(px);
+            }
+          }
+          if constexpr (FEATURES) {
+            if (depth == 0) {  // the sample's primary HitRecord: rec.t, rec.normal, the material's own colour at the hit
+              // (a fetched texel is in `layer`, bit 31 set: the Lambertian's attenuation, the light's emission)
+              if (feat->albedo) feature_add3(feat->albedo, ((F & F_TEX) && (layer >> 31)) ? texel_rgb(layer) : rgb);
+              if (feat->normal) feature_add3(feat->normal, nrm);
+              if (feat->depth) feat->depth[q32] = __fadd_rn(feat->depth[q32], h.t);
+              if (feat->coverage) feat->coverage[q32] += 1u;
             }
           }
           if (m.kind == MAT_LIGHT) {

@@ -300,4 +300,13 @@ struct FrameDev {
   int64_t items;                       // local_tiles * 64
 };
 
+// First-hit feature buffers of rtmi_render_features / rtmi_resolve_features (rtmi_features of include/rtmi.h), each
+// nullable, tile-major per shard: float[items][3], float[items][3], float[items], uint32[items].
+struct FeatureBufs {
+  float *albedo = nullptr;
+  float *normal = nullptr;
+  float *depth = nullptr;
+  uint32_t *coverage = nullptr;
+};
+
 }  // namespace rtmi

@@ -78,6 +78,18 @@ def adaptive_opts(min_spp, max_spp, step, tolerance, floor=0.01):
     return AdaptiveOpts(C.sizeof(AdaptiveOpts), int(min_spp), int(max_spp), int(step), float(tolerance), float(floor))
 
 
+class Features(C.Structure):
+    """rtmi_features of include/rtmi.h (first-hit feature buffers, each nullable)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("d_albedo", C.c_void_p), ("d_normal", C.c_void_p),
+                ("d_depth", C.c_void_p), ("d_coverage", C.c_void_p)]
+
+
+def feature_bufs(albedo=None, normal=None, depth=None, coverage=None):
+    """An rtmi_features over torch tensors (None: that buffer is left out); keep the tensors alive while it is used."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return Features(C.sizeof(Features), 0, ptr(albedo), ptr(normal), ptr(depth), ptr(coverage))
+
+
 TRANSFORM_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p)
 
 _lib = None
@@ -158,6 +170,9 @@ SYMBOLS = [
     ("rtmi_budget_plan", C.c_int, [_frp, C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     ("rtmi_resolve", C.c_int, [_frp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("rtmi_render_features", C.c_int, [C.c_void_p, _frp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(Features), C.c_void_p, C.c_void_p]),
+    ("rtmi_resolve_features", C.c_int, [_frp, C.POINTER(Features), C.c_void_p, C.POINTER(Features), C.c_void_p]),
 ]
 
 
@@ -267,9 +282,16 @@ class Trace:
         return int(self.work[1].item())
 
 
-class Adaptive(collections.namedtuple("Adaptive", "tiles samples passes total_samples")):
+class Adaptive(collections.namedtuple("Adaptive", "tiles samples passes total_samples features", defaults=(None,))):
     """What ``Renderer.render_adaptive`` returns: ``tiles`` (items, 3) float32, the resolved tile buffer; ``samples``
-    (items,) int32, the samples each work item got; ``passes`` rendered; ``total_samples`` over the shard."""
+    (items,) int32, the samples each work item got; ``passes`` rendered; ``total_samples`` over the shard;
+    ``features``: with ``features=True`` the resolved ``ResolvedFeatures``, else None."""
+
+
+ResolvedFeatures = collections.namedtuple("ResolvedFeatures", "albedo normal depth alpha")
+"""What ``Renderer.resolve_features`` returns, tile-major: ``albedo`` and ``normal`` (items, 3) float32 (the mean normal
+is not renormalised), ``depth`` (items,) float32 (the mean over the samples that hit a surface, 0 where none did),
+``alpha`` (items,) float32 (the share of the samples that hit a surface)."""
 
 
 def rng_states(seed, n, first=0, device=None):
@@ -624,24 +646,54 @@ class Renderer:
             self.budget = torch.zeros((n,), dtype=torch.int32, device=dev)
             self.totals = torch.zeros((2,), dtype=torch.int64, device=dev)
 
-    def render_budget(self, budget, count_rays=True):
+    def _feature_buffers(self):
+        if getattr(self, "albedo", None) is None:
+            torch, n, dev = self.torch, self.items, self.device
+            self.albedo = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+            self.normal = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+            self.depth = torch.zeros((n,), dtype=torch.float32, device=dev)
+            self.coverage = torch.zeros((n,), dtype=torch.int32, device=dev)
+
+    def render_budget(self, budget, count_rays=True, features=False):
         """``budget[q]`` more samples (at most the frame's spp per call) of every pixel q of this shard
         (rtmi_render_budget), enqueued on torch's current stream: continues each pixel's RNG stream in ``states`` and
         adds to ``sum`` (radiance), ``sq`` (squares), ``samples`` and, with ``count_rays``, ``budget_rays`` -- zeroed
         on first use and kept as attributes.  ``budget``: a contiguous (items,) int32 CUDA tensor.  The frame must
-        have been made with ``post=False``."""
+        have been made with ``post=False``.  ``features``: also add the primary hit of every sample to ``albedo``,
+        ``normal``, ``depth`` and ``coverage`` (rtmi_render_features; zeroed on first use; max_depth >= 1)."""
         torch = self.torch
         if not _is_buffer(budget, (self.items,), self.device, torch.int32):
             raise RtmiError("budget must be a contiguous CUDA int32 tensor of shape (items,) on the renderer's device")
         self._budget_buffers()
+        args = (self.scene.h, C.byref(self.frame), C.c_void_p(budget.data_ptr()), C.c_void_p(self.states.data_ptr()),
+                C.c_void_p(self.sum.data_ptr()), C.c_void_p(self.sq.data_ptr()), C.c_void_p(self.samples.data_ptr()),
+                C.c_void_p(self.budget_rays.data_ptr()) if count_rays else None)
         with torch.cuda.device(self.device):
-            _check(self.L.rtmi_render_budget(self.scene.h, C.byref(self.frame), C.c_void_p(budget.data_ptr()),
-                                             C.c_void_p(self.states.data_ptr()), C.c_void_p(self.sum.data_ptr()),
-                                             C.c_void_p(self.sq.data_ptr()), C.c_void_p(self.samples.data_ptr()),
-                                             C.c_void_p(self.budget_rays.data_ptr()) if count_rays else None,
-                                             C.c_void_p(self.d_work.data_ptr()), self._stream()), "rtmi_render_budget")
+            if features:
+                self._feature_buffers()
+                feat = feature_bufs(self.albedo, self.normal, self.depth, self.coverage)
+                _check(self.L.rtmi_render_features(*args, C.byref(feat), C.c_void_p(self.d_work.data_ptr()), self._stream()),
+                       "rtmi_render_features")
+            else:
+                _check(self.L.rtmi_render_budget(*args, C.c_void_p(self.d_work.data_ptr()), self._stream()),
+                       "rtmi_render_budget")
             self.budget_abandoned += self.d_work[0]  # (stream-ordered: the next call resets d_work)
         return self
+
+    def resolve_features(self):
+        """``ResolvedFeatures`` (albedo, normal, depth, alpha) of the feature sums so far, tile-major
+        (rtmi_resolve_features; the rule is in include/rtmi.h): 0 where a pixel has no samples and for padding."""
+        self._budget_buffers()
+        self._feature_buffers()
+        torch, n, dev = self.torch, self.items, self.device
+        out = ResolvedFeatures(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                               torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev))
+        sums = feature_bufs(self.albedo, self.normal, self.depth, self.coverage)
+        to = feature_bufs(*out)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_resolve_features(C.byref(self.frame), C.byref(sums), C.c_void_p(self.samples.data_ptr()),
+                                                C.byref(to), self._stream()), "rtmi_resolve_features")
+        return out
 
     def plan(self, min_spp, max_spp, step, tolerance, floor=0.01):
         """The next pass's budget from the sums so far (rtmi_budget_plan; the rule is in include/rtmi.h).  Returns
@@ -666,10 +718,11 @@ class Renderer:
                                        self._stream()), "rtmi_resolve")
         return out
 
-    def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True):
+    def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True, features=False):
         """Plan / render passes until no pixel has a budget left: every pixel gets ``min_spp`` samples, then ``step``
         more per pass until it meets the stopping rule or has ``max_spp``.  One host read of the plan's totals per
-        pass is the only synchronisation.  The frame's spp must be at least max(min_spp, step)."""
+        pass is the only synchronisation.  The frame's spp must be at least max(min_spp, step).  ``features``: every
+        pass also adds to the first-hit feature buffers, and the result's ``features`` holds them resolved."""
         if self.frame.spp < max(int(min_spp), int(step)):
             raise RtmiError("the frame's spp (%d) caps one pass: it must be at least max(min_spp, step)" % self.frame.spp)
         passes = total = 0
@@ -677,10 +730,10 @@ class Renderer:
             budget, active, pass_total = self.plan(min_spp, max_spp, step, tolerance, floor)
             if active == 0:
                 break
-            self.render_budget(budget)
+            self.render_budget(budget, features=features)
             passes, total = passes + 1, total + pass_total
         self.check()
-        return Adaptive(self.resolve(post), self.samples, passes, total)
+        return Adaptive(self.resolve(post), self.samples, passes, total, self.resolve_features() if features else None)
 
     def scratch_bytes(self):
         return int(self.L.rtmi_render_scratch_bytes(C.byref(self.frame)))
@@ -717,7 +770,9 @@ class Renderer:
         return out.value
 
     def untile(self, all_tiles=None, all_counts=None):
-        """Row-major (H,W,3) image [and (H,W) ray counts] from tile-major buffers of all ranks."""
+        """Row-major (H,W,3) image [and (H,W) ray counts] from tile-major buffers of all ranks.  ``all_tiles`` may be
+        any 3-channel float32 buffer (resolved albedo or normal), ``all_counts`` any 32-bit one: a float32 buffer
+        (resolved depth or alpha) is moved by its bits and comes back as float32."""
         torch = self.torch
         f = self.frame
         with torch.cuda.device(self.device):
@@ -731,7 +786,8 @@ class Renderer:
             cnt = None
             counts = self.ray_counts if (all_counts is None and f.world_size == 1) else all_counts
             if counts is not None:
-                cnt = torch.zeros((f.height, f.width), dtype=torch.int32, device=self.device)
+                cnt = torch.zeros((f.height, f.width), device=self.device,
+                                  dtype=torch.float32 if counts.dtype == torch.float32 else torch.int32)
                 _check(self.L.rtmi_untile_u32(C.byref(f), C.c_void_p(counts.data_ptr()), C.c_void_p(cnt.data_ptr()),
                                               self._stream()), "rtmi_untile_u32")
         return img, cnt
