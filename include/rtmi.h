@@ -302,7 +302,10 @@ typedef struct rtmi_render_opts {
                               * launch resumes every pixel at sample s1 (s1 = probe_spp, or by default spp / 16, at most 64,
                               * for a frame that will be planned, else 2); N > 1 = the same with spp / N; 0 = probe_spp
                               * samples on a scratch copy of the RNG states, discarded */
-  int32_t reserved;
+  int32_t fast_path;         /* 0 default (1, or RTMI_FAST_PATH).  1 = a launch of a list-triangle scene whose run-time modes are all
+                              * the common ones (at most 16 materials, the scene's tables staged in LDS, no signed colour, a
+                              * power-of-two frame, every lane taking pixels, wave priorities on) uses a kernel compiled for
+                              * exactly those modes; -1 = every launch uses the general kernel.  Same pixels either way. */
   void *d_scratch;           /* optional device memory for ALL per-call state (work-queue cursors, ray total,
                               * completion flag, the scheduler's buffers), owned by the caller, at least */
   size_t scratch_bytes;      /* rtmi_render_scratch_bytes(frame) bytes: with it, concurrent renders of one scene
@@ -322,6 +325,21 @@ int rtmi_render_launch_shape(const rtmi_scene *s, const rtmi_frame *f, const rtm
  * planned chains (0: from the work queue), wave-priority interval in iterations (0: off), lane stride (1: every lane
  * takes pixels), waves of the grid, tiles of this shard}.  Informational: none of it changes a pixel. */
 int rtmi_render_mode(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t out[8]);
+/* The same report with its later fields: the first min(n, RTMI_MODE_FIELDS) of {the eight of rtmi_render_mode, fast_path
+ * (1: the launch that finishes the frame uses a kernel compiled for its modes, see rtmi_render_opts.fast_path; 0: the
+ * general kernel)}.  Added without a version change: a caller detects it by the symbol. */
+#define RTMI_MODE_FIELDS 9
+int rtmi_render_mode_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t *out, int n);
+/* The rule behind that field, as a pure function (no device, no scene): which trace kernel a launch with these facts
+ * gets -- 0 the general one, 1 the fast kernel that draws from the work queue, 2 the fast kernel that walks planned
+ * chains.  facts = {fast path enabled, kernel variant (2: list triangles only), materials, material table staged in LDS,
+ * pair records staged in LDS, no signed colour, determinants safe, width, height, lane stride, wave priorities on,
+ * planned chains, resumes a first pass, has the probe's tile costs}.  Every fast kernel needs: enabled, variant 2, 1..16
+ * materials, both tables staged, no signed colour, safe determinants, width and height powers of two up to 2^20, lane
+ * stride 1, priorities on; the chain kernel also a resumed pass with tile costs (else such a launch is the general
+ * kernel's).  RTMI_ERR_INVALID for a null argument. */
+#define RTMI_FAST_PATH_FACTS 14
+int rtmi_fast_path_kernel(const int32_t facts[RTMI_FAST_PATH_FACTS]);
 /* rtmi_render with per-call options (opts == NULL: the defaults). */
 int rtmi_render_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream);
@@ -566,7 +584,8 @@ int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const 
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /
- * RTMI_LANE_STRIDE / RTMI_PROMOTE (promote_after) / RTMI_COST_PROBE / RTMI_FIRST_PASS environment variables override the built-in defaults
+ * RTMI_LANE_STRIDE / RTMI_PROMOTE (promote_after) / RTMI_COST_PROBE / RTMI_FIRST_PASS / RTMI_FAST_PATH (0: the general kernel
+ * always, what fast_path = -1 asks of one call) environment variables override the built-in defaults
  * of those fields and are read once, when the library is first used.  (RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST, 1..64: the
  * largest batch a wave of a list frame draws from the work queue per atomic in longest-first order / in a first pass of a
  * few samples -- measurement knobs without an option field; defaults 16 / 64.) */

@@ -69,6 +69,7 @@ static RenderTuning default_tuning() {
     if (g_tune.plan < 0 || g_tune.plan > 2) g_tune.plan = 1;
     g_tune.prio_every = env_int("RTMI_PRIO", 16);  // wave priorities: update interval in iterations (0: off)
     if (g_tune.prio_every < 0 || (g_tune.prio_every & (g_tune.prio_every - 1)) != 0) g_tune.prio_every = 16;
+    g_tune.fast_path = env_int("RTMI_FAST_PATH", 1) != 0;  // 0: every launch uses the general kernel (kernels.h: fast_path_mode)
   });
   std::lock_guard<std::mutex> lk(g_tune_mu);
   return g_tune;
@@ -665,7 +666,8 @@ static int resolve_opts(const rtmi_render_opts *opts, RenderTuning *tune, void *
       opts->threads_per_block > 512 || (opts->sparse_stride != 0 && !valid_stride(opts->sparse_stride)) || opts->exclusive > 1 ||
       opts->outlier_x10 < 0 || opts->probe_spp < 0 || opts->probe_spp > 64 || opts->plan > 2 || opts->wave_priority > 4096 ||
       (opts->wave_priority > 0 && (opts->wave_priority & (opts->wave_priority - 1)) != 0) || opts->lane_stride < 0 ||
-      opts->lane_stride > 64 || (opts->lane_stride & (opts->lane_stride - 1)) != 0 || opts->cost_probe > 1 || opts->first_pass > 4096)
+      opts->lane_stride > 64 || (opts->lane_stride & (opts->lane_stride - 1)) != 0 || opts->cost_probe > 1 || opts->first_pass > 4096 ||
+      opts->fast_path < -1 || opts->fast_path > 1)
     return fail(RTMI_ERR_INVALID, "rtmi_render_opts field out of range");
   for (int i = 0; i < 3; i++)
     if (opts->head_pct[i] < 0 || opts->head_pct[i] > 100) return fail(RTMI_ERR_INVALID, "rtmi_render_opts.head_pct outside [0, 100]");
@@ -682,6 +684,7 @@ static int resolve_opts(const rtmi_render_opts *opts, RenderTuning *tune, void *
   if (opts->promote_after >= 0) tune->promote = opts->promote_after;
   if (opts->cost_probe >= 0) tune->cost_probe = opts->cost_probe;
   if (opts->first_pass >= 0) tune->first_pass = opts->first_pass;
+  if (opts->fast_path != 0) tune->fast_path = opts->fast_path > 0;
   for (int i = 0; i < 3; i++)
     if (opts->head_pct[i] > 0) tune->head_pct[i] = opts->head_pct[i];
   if (!(tune->head_pct[0] >= tune->head_pct[1] && tune->head_pct[1] >= tune->head_pct[2]))
@@ -710,11 +713,13 @@ static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &t
     // room for one 256-lane workgroup only, smaller workgroups keep more lanes resident
     int best = 0;
     for (int t = 256; t >= 64; t /= 2) {
-      const int lanes = t * render_occupancy(variant, s->dev, d, t);
+      const int lanes = t * render_occupancy(variant, s->dev, d, t);  // (mesh variants: no fast kernels)
       if (lanes > best) best = lanes, threads = t;
     }
   }
-  int per_cu = tune.blocks_per_cu > 0 ? tune.blocks_per_cu : render_occupancy(variant, s->dev, d, threads);
+  // (asked of the kernel that will really be launched: the general one, or whichever of the fast ones it may be)
+  int per_cu = tune.blocks_per_cu > 0 ? tune.blocks_per_cu
+                                      : render_occupancy(variant, s->dev, d, threads, fast_path_scene(variant, s->dev, d, threads, tune.fast_path));
   if (per_cu <= 0) per_cu = 1;
   int64_t want = (d.items + threads - 1) / threads;
   int64_t cap = (int64_t)n_cu * per_cu;
@@ -811,7 +816,11 @@ int rtmi_render_launch_shape(const rtmi_scene *sp, const rtmi_frame *f, const rt
 }
 
 int rtmi_render_mode(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t out[8]) {
-  if (!sp || !out) return fail(RTMI_ERR_INVALID, "null argument");
+  return rtmi_render_mode_ex(sp, f, opts, out, 8);
+}
+int rtmi_render_mode_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t *dst, int n) {
+  if (!sp || !dst || n < 0) return fail(RTMI_ERR_INVALID, "null argument");
+  int32_t out[RTMI_MODE_FIELDS];
   const Scene *s = S(sp);
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   FrameDev d;
@@ -835,7 +844,20 @@ int rtmi_render_mode(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_rende
   out[5] = ls.lane_stride;
   out[6] = waves;
   out[7] = d.local_tiles;
+  // the kernel of the launch that finishes the frame (rtmi_render_ex hands launch_render the same facts)
+  out[8] = launch_fast_path(ls.variant, s->dev, d, ls.threads, tune, m.prio, out[3] != 0, m.resume, m.scheduled) != 0u ? 1 : 0;
+  for (int i = 0; i < n && i < RTMI_MODE_FIELDS; i++) dst[i] = out[i];
   return RTMI_OK;
+}
+
+int rtmi_fast_path_kernel(const int32_t facts[RTMI_FAST_PATH_FACTS]) {
+  if (!facts) return fail(RTMI_ERR_INVALID, "null argument");
+  FastPathFacts f{};
+  f.enabled = facts[0], f.variant = (uint32_t)facts[1], f.n_mats = facts[2], f.mats_in_lds = facts[3], f.pairs_in_lds = facts[4];
+  f.unsigned_colours = facts[5], f.det_safe = facts[6], f.width = facts[7], f.height = facts[8], f.lane_stride = facts[9];
+  f.priorities = facts[10], f.chains = facts[11], f.resumed = facts[12], f.tile_cost = facts[13];
+  const uint32_t m = fast_path_mode(f);
+  return m == kFastChains ? 2 : m == kFastQueue ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ batches of caller rays

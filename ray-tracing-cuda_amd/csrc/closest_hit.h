@@ -75,7 +75,8 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 // replay then refuses sets *uncertain (quirk g8: AABB::Hit asks for a crossing of the box's surface inside [t_from,
 // t_to], so a ray that starts inside a box and leaves it beyond t_stop does not enter it, where the unbounded walk
 // would).  With OCC false none of this is compiled in.
-template <uint32_t F, bool OCC = false>
+// M (kernels.h): the run-time modes the caller's launch has pinned at compile time; 0 pins none.
+template <uint32_t F, bool OCC = false, uint32_t M = 0>
 __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_nodes, int lds_nodes, const int *s_paths,
                                            int lds_paths, const float4 *s_pairs, int *ll, uint16_t *cands, int *wl,
                                            unsigned long long *overflow, V3 o, V3 d, bool live, bool count_work
@@ -107,12 +108,12 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   }
 
   const int lane = (int)(threadIdx.x & 63u);
-  const bool det_safe = sc.det_safe != 0;  // (a kernel argument: the branch on it waits for no vector result)
+  const bool det_safe = (M & PIN_DET_SAFE) || sc.det_safe != 0;  // (a kernel argument: the branch on it waits for no vector result)
   // the ray as the culled list scan wants it: 1/d (the hardware reciprocal will do: the test is conservative by
   // a margin of 1e-5, not 1e-7), and -(o +- delta)/d per axis, delta = the distance slack of the mesh search
   // the culled list scan is on when the wave has its task region (ll) and the scene has pair records; the pairs'
   // corners come from LDS when the list was short enough to be staged (s_pairs), else from global memory
-  const bool cull_list = (F & F_TRIS) && ll != nullptr && sc.n_pairs >= kCullMinPairs;  // (wave-uniform)
+  const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
   if ((F & F_TRIS) && cull_list) {
     const float ix = __builtin_amdgcn_rcpf(d.x), iy = __builtin_amdgcn_rcpf(d.y), iz = __builtin_amdgcn_rcpf(d.z);
@@ -213,7 +214,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             mask &= mask - 1u;
             const size_t pidx = (size_t)(pair0 + c0 + bit) * 4;
             float4 qa, qb, qc, qd;
-            if (s_pairs != nullptr) {  // (wave-uniform) staged in LDS
+            if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) staged in LDS
               const float4 *pp = s_pairs + pidx;
               qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2), qd = load_lds<float4>(pp + 3);
             } else {
@@ -293,7 +294,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                 const V3 ro = mk(r0.x, r0.y, r0.z), rd = mk(r1.x, r1.y, r1.z);
                 const size_t pidx = (size_t)(pair0 + c0 + (w & 31)) * 4;
                 float4 qa, qb, qc, qd;
-                if (s_pairs != nullptr) {  // (wave-uniform) staged in LDS
+                if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) staged in LDS
                   const float4 *pp = s_pairs + pidx;
                   qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2), qd = load_lds<float4>(pp + 3);
                 } else {  // a list too long for the staging: per-lane gather of 64 bytes (L1 / L2 resident)

@@ -18,7 +18,8 @@ hipError_t launch_rng_init(uint64_t seed, const FrameDev &fr, const uint32_t *d_
 
 // Kernel specialisation covering a feature set, its occupancy, and its launch.
 uint32_t pick_variant(uint32_t features);
-int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads);
+// fast_path: the launch may be one of the fast kernels (fast_path_scene): the answer holds for whichever is launched.
+int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, bool fast_path = false);
 // d_tile_order (nullable): the work queue hands out local tile d_tile_order[k] as its k-th tile.
 // d_sparse_items (nullable; needs d_tile_order): device word, how many leading work items are outlier
 // tiles that mesh kernels spread one pixel per tune.sparse_stride lanes (launch_tile_order writes it to d_max[1]).
@@ -42,7 +43,48 @@ struct RenderTuning {
   int plan;           // 1: list frames with a probe behind them are rendered as planned chains (launch_chain_plan), not from the queue
   int prio_every;     // > 0: the waves of a SIMD are served longest-remaining-chain-first, each looking at its priority every
                       // this many iterations (a power of two); 0: the hardware's oldest-first order
+  int fast_path;      // 1: a launch whose run-time modes are all the common ones uses the kernel compiled for them (below)
 };
+
+// Compile-time mode word of the trace kernel (render_body.h, closest_hit.h: template parameter M).  One kernel body
+// serves every scene, frame and schedule, and decides between them at run time, from wave-uniform fields that never
+// change during a launch.  A set bit PINS one of those decisions: the body is compiled with the answer known, the other
+// side of the branch is not emitted and the value it was read from is not kept in a register across the loop.  M == 0
+// pins nothing and compiles to the kernel as it was.  What a bit promises the HOST must have checked: fast_path_mode.
+enum : uint32_t {
+  PIN_NIBBLE_IDS = 1u << 0,    // lc.wide_ids == 2: at most 16 materials, two levels of the id stack per byte
+  PIN_LDS_TABLES = 1u << 1,    // materials, pair corners and normals staged in LDS; the culled list scan with shared tests
+  PIN_UNSIGNED = 1u << 2,      // sc.unsigned_colours (with the two above: the four-levels-at-a-time fold alone)
+  PIN_DET_SAFE = 1u << 3,      // sc.det_safe
+  PIN_POW2_FRAME = 1u << 4,    // width and height powers of two up to 2^20: the jitter in binary32
+  PIN_EVERY_LANE = 1u << 5,    // lc.lane_stride == 1
+  PIN_PRIORITIES = 1u << 6,    // lc.prio_tab != nullptr
+  PIN_CHAINS = 1u << 7,        // planned chains on a resumed pass: lc.chain_next, lc.tile_cost, ray_counts set, fr.k_begin > 0
+  PIN_QUEUE = 1u << 8,         // the wave draws from the queue: lc.chain_next == nullptr
+};
+constexpr uint32_t kFastCommon = PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED | PIN_DET_SAFE | PIN_POW2_FRAME |
+                                 PIN_EVERY_LANE | PIN_PRIORITIES;
+constexpr uint32_t kFastChains = kFastCommon | PIN_CHAINS;  // the second launch of a planned frame (C2, a C4 shard)
+constexpr uint32_t kFastQueue = kFastCommon | PIN_QUEUE;    // a first pass, a queued or image-order frame
+// Everything the fast kernels take for granted, as the launch knows it.  One predicate for the launch, for
+// rtmi_render_mode and for the tests (rtmi_fast_path_kernel).
+struct FastPathFacts {
+  int enabled;           // RenderTuning::fast_path
+  uint32_t variant;      // the kernel variant (pick_variant)
+  int n_mats;            // materials of the scene
+  int mats_in_lds;       // the material table is staged (LaunchCfg::lds_mats > 0)
+  int pairs_in_lds;      // pair corners and normals are staged and the culled scan shares its tests (pairs_off, nrm_off, list_off >= 0)
+  int unsigned_colours;  // SceneDev::unsigned_colours
+  int det_safe;          // SceneDev::det_safe
+  int width, height;
+  int lane_stride;
+  int priorities;        // the launch has a priority table
+  int chains;            // the launch walks planned chains
+  int resumed;           // fr.k_begin > 0 and a ray-count buffer to resume from
+  int tile_cost;         // the launch has the probe's tile costs
+};
+// 0: the general kernel; else kFastChains or kFastQueue.
+uint32_t fast_path_mode(const FastPathFacts &f);
 // What the scheduler's probe pass leaves for the real pass (device pointers, all optional).
 struct SchedPlan {
   const uint32_t *tile_order = nullptr;    // the queue's order per quarter tile (launch_quarter_order)
@@ -67,6 +109,14 @@ size_t render_params_bytes();
 hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
                          uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan, bool probe,
                          int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream);
+// The part of fast_path_mode that is known before the launch shape is (scene, frame, switch): without it no launch of
+// this frame uses a fast kernel.
+bool fast_path_scene(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled);
+// The mode word launch_render uses for a launch (0: the general kernel): tune carries the launch shape's lane stride;
+// priorities, chains, tile_cost: the launch has a priority table, walks planned chains, has the probe's tile costs;
+// resumed: it resumes a first pass (fr.k_begin > 0, with a ray-count buffer).
+uint32_t launch_fast_path(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, const RenderTuning &tune,
+                          bool priorities, bool chains, bool resumed, bool tile_cost);
 // Tiles sorted by descending cost (sum of 64 ray counts each); d_cost/d_order hold n_tiles words,
 // d_meta 16: [0] the largest tile cost, [1] the sparse item count.
 // sparse_cap: work items the grid holds at one pixel per tune.sparse_stride lanes (a multiple of 64).

@@ -165,17 +165,19 @@ __global__ void params_write_kernel(RenderParams p, RenderParams *dst) {
 }
 size_t render_params_bytes() { return (sizeof(RenderParams) + 255) & ~(size_t)255; }
 
-template <uint32_t F>
+// M: the mode word (kernels.h).  0 is the general kernel; kFastChains and kFastQueue are instantiated for the
+// list-triangle variant (launch_render) and launched when fast_path_mode says the launch is what they were compiled for.
+template <uint32_t F, uint32_t M = 0>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void render_kernel(const RenderParams *p) {
   // (global -> constant address space -> generic: the compiler's address-space inference turns every access through
   // kp back into a constant-address-space load, i.e. a scalar load that nothing in the kernel can clobber)
   const RenderParams *kp = (const RenderParams *)(const RT_CONSTANT RenderParams *)(uintptr_t)p;
-  render_body<F>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
+  render_body<F, false, false, false, M>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
 }
-template <uint32_t F>
+template <uint32_t F, uint32_t M = 0>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void probe_kernel(const RenderParams *p) {
   const RenderParams *kp = (const RenderParams *)(const RT_CONSTANT RenderParams *)(uintptr_t)p;
-  render_body<F>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
+  render_body<F, false, false, false, M>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
 }
 // rtmi_trace: the same body in its caller-ray mode, its argument block read the render's way (constant address space)
 // from the call's own d_work, behind the kernel's counter words (launch_trace).
@@ -723,14 +725,62 @@ static R with_variant(uint32_t variant, R otherwise, Fn &&f) {
   return otherwise;
 }
 
-int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads) {
+// ------------------------------------------------------------------ the fast path's predicate
+uint32_t fast_path_mode(const FastPathFacts &f) {
+  const auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0 && v <= (1 << 20); };
+  const bool common = f.enabled != 0 && f.variant == (uint32_t)F_TRIS && f.n_mats >= 1 && f.n_mats <= 16 && f.mats_in_lds != 0 &&
+                      f.pairs_in_lds != 0 && f.unsigned_colours != 0 && f.det_safe != 0 && pow2(f.width) && pow2(f.height) &&
+                      f.lane_stride == 1 && f.priorities != 0;
+  if (!common) return 0u;
+  if (!f.chains) return kFastQueue;
+  return f.resumed && f.tile_cost ? kFastChains : 0u;
+}
+static FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
+  size_t lds = 0;
+  const LaunchCfg lc = make_cfg(variant, sc, fr, threads, &lds);
+  FastPathFacts f{};
+  f.enabled = enabled, f.variant = variant, f.n_mats = sc.n_mats, f.mats_in_lds = lc.lds_mats > 0 && lc.wide_ids == 2;
+  f.pairs_in_lds = lc.pairs_off >= 0 && lc.nrm_off >= 0 && lc.list_off >= 0;
+  f.unsigned_colours = sc.unsigned_colours, f.det_safe = sc.det_safe, f.width = fr.width, f.height = fr.height;
+  return f;
+}
+bool fast_path_scene(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
+  FastPathFacts f = fast_path_facts(variant, sc, fr, threads, enabled);
+  f.lane_stride = 1, f.priorities = 1;
+  return fast_path_mode(f) != 0u;
+}
+uint32_t launch_fast_path(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, const RenderTuning &tune,
+                          bool priorities, bool chains, bool resumed, bool tile_cost) {
+  FastPathFacts f = fast_path_facts(variant, sc, fr, threads, tune.fast_path);
+  f.lane_stride = tune.lane_stride > 0 ? tune.lane_stride : 1;
+  f.priorities = priorities, f.chains = chains, f.resumed = resumed, f.tile_cost = tile_cost;
+  return fast_path_mode(f);
+}
+
+// Workgroups of Kernel per compute unit at this launch shape (0: it does not fit).
+template <auto Kernel>
+static int kernel_occupancy(int threads, size_t lds) {
+  int nb = 0;
+  if (dynamic_lds<Kernel>(lds) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, lds) != hipSuccess) nb = 0;
+  return nb;
+}
+int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, bool fast_path) {
   return with_variant(variant, 0, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
-    int nb = 0;
     size_t lds = 0;
     (void)make_cfg(F, sc, fr, threads, &lds);
-    if (threads > RTMI_MAX_THREADS(F) || lds > 160 * 1024 || dynamic_lds<render_kernel<F>>(lds) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel<F>, threads, lds) != hipSuccess) nb = 0;
+    if (threads > RTMI_MAX_THREADS(F) || lds > 160 * 1024) return 0;
+    int nb = kernel_occupancy<render_kernel<F>>(threads, lds);
+    if constexpr (F == (uint32_t)F_TRIS) {
+      // which of the three kernels a launch of this frame gets is decided after the grid is sized (lane stride, plan):
+      // the grid must fit whichever it is (all three are built for the same waves per SIMD and use the same LDS)
+      if (fast_path) {
+        const int nc = kernel_occupancy<render_kernel<F, kFastChains>>(threads, lds);
+        const int nq = kernel_occupancy<render_kernel<F, kFastQueue>>(threads, lds);
+        nb = nb < nc ? nb : nc, nb = nb < nq ? nb : nq;
+      }
+    }
     return nb;
   });
 }
@@ -776,19 +826,28 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
       const int image_batch = per_atomic < 1 ? 1 : per_atomic > 16 ? 16 : per_atomic;
       lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_batch;
     }
-    const hipError_t e = probe ? dynamic_lds<probe_kernel<F>>(lds) : dynamic_lds<render_kernel<F>>(lds);
-    if (e != hipSuccess) return e;
     RenderParams rp;
     rp.sc = sc, rp.fr = fr, rp.lc = lc;
     rp.states = d_states, rp.out = d_out, rp.ray_counts = d_ray_counts, rp.counters = d_counters;
     RenderParams *dp = reinterpret_cast<RenderParams *>(d_params);
-    hipLaunchKernelGGL(params_write_kernel, dim3(1), dim3(64), 0, stream, rp, dp);
-    if (probe) {
-      hipLaunchKernelGGL(probe_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
-    } else {
-      hipLaunchKernelGGL(render_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
+    auto launch = [&](auto kernel) -> hipError_t {
+      constexpr auto Kernel = decltype(kernel)::value;
+      const hipError_t e = dynamic_lds<Kernel>(lds);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(params_write_kernel, dim3(1), dim3(64), 0, stream, rp, dp);
+      hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
+      return hipGetLastError();
+    };
+    if constexpr (F == (uint32_t)F_TRIS) {
+      // the kernels compiled for the common list frame, when this launch is one (fast_path_mode; a probe never walks chains)
+      const uint32_t mode = launch_fast_path(F, sc, fr, threads, tune, lc.prio_tab != nullptr, lc.chain_next != nullptr,
+                                             fr.k_begin > 0 && d_ray_counts != nullptr, lc.tile_cost != nullptr);
+      if (mode == kFastChains && !probe) return launch(std::integral_constant<decltype(&render_kernel<F, kFastChains>), &render_kernel<F, kFastChains>>());
+      if (mode == kFastQueue && !probe) return launch(std::integral_constant<decltype(&render_kernel<F, kFastQueue>), &render_kernel<F, kFastQueue>>());
+      if (mode == kFastQueue && probe) return launch(std::integral_constant<decltype(&probe_kernel<F, kFastQueue>), &probe_kernel<F, kFastQueue>>());
     }
-    return hipGetLastError();
+    if (probe) return launch(std::integral_constant<decltype(&probe_kernel<F>), &probe_kernel<F>>());
+    return launch(std::integral_constant<decltype(&render_kernel<F>), &render_kernel<F>>());
   });
 }
 

@@ -143,7 +143,9 @@ __device__ __forceinline__ bool finite3(V3 v) {
 // the non-null buffers of *feat, one binary32 addition per channel, in sample order.  A read-modify-write in global
 // memory, not running sums in registers: the lane owns the item, so these are plain vector loads and stores, and nothing
 // more is live across closest_hit and the fold than in the budget mode.  No RNG draw is made or skipped.
-template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false>
+// M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
+// the front end folds: with M == 0 every line below is the run-time test it was.
+template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -155,6 +157,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const FeatureBufs *feat = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
   static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
+  static_assert(M == 0 || (F == F_TRIS && !RAYS && !BUDGET), "the pins are the list-triangle render's");
+  static_assert(!((M & PIN_CHAINS) && (M & PIN_QUEUE)), "a wave gets its work one way");
+  // (M) the three pins behind fast_fold; planned chains: pinned on, pinned off, or the launch's
+  constexpr bool FOLD4 = (M & (PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED)) == (PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED);
   constexpr bool QUEUE = RAYS || BUDGET;  // the call owns its device state (d_work) and draws from the list queue
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   MatRec *s_mats = reinterpret_cast<MatRec *>(smem);
@@ -164,8 +170,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // compiler reads with a VECTOR load (global_load_ushort + s_waitcnt vmcnt(0)) at every use inside the loop --
   // three round trips to memory per iteration before round 3
   const uint32_t n_threads = (uint32_t)lc.threads;
-  const uint32_t ids_shift = lc.wide_ids == 1 ? 1u : 0u;
-  const bool nibble_ids = lc.wide_ids == 2;
+  const uint32_t ids_shift = !(M & PIN_NIBBLE_IDS) && lc.wide_ids == 1 ? 1u : 0u;
+  const bool nibble_ids = (M & PIN_NIBBLE_IDS) || lc.wide_ids == 2;
   auto ids_offset = [&](int level) -> uint32_t {  // (nibble_ids: the byte of levels 2k and 2k + 1 is row k)
     return (uint32_t)lc.stack_off + (((uint32_t)level * n_threads + threadIdx.x) << ids_shift);
   };
@@ -175,7 +181,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     wl = reinterpret_cast<int *>(smem + lc.mesh_off) +
          __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kMeshWaveWords;
   const float4 *s_pairs = nullptr;  // corners of the world-list pairs (culled scan) or nullptr (plain scan)
-  if ((F & F_TRIS) && lc.pairs_off >= 0) {
+  if ((F & F_TRIS) && ((M & PIN_LDS_TABLES) || lc.pairs_off >= 0)) {
     s_pairs = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
     const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.pair_pts);
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + lc.pairs_off);
@@ -184,16 +190,16 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     uint32_t *ndst = reinterpret_cast<uint32_t *>(smem + lc.nrm_off);
     for (int w = threadIdx.x; w < sc.n_pairs * 8; w += blockDim.x) ndst[w] = nsrc[w];
   }
-  const float4 *s_nrm = reinterpret_cast<const float4 *>(smem + (lc.nrm_off >= 0 ? lc.nrm_off : 0));
+  const float4 *s_nrm = reinterpret_cast<const float4 *>(smem + ((M & PIN_LDS_TABLES) || lc.nrm_off >= 0 ? lc.nrm_off : 0));
   int *ll = nullptr;  // this wave's region for the shared candidate tests of the culled list scan
-  if ((F & (F_TRIS | F_SGROUP)) && lc.list_off >= 0)
+  if ((F & (F_TRIS | F_SGROUP)) && ((M & PIN_LDS_TABLES) || lc.list_off >= 0))
     ll = reinterpret_cast<int *>(smem + lc.list_off) +
          __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kListWaveWords(F);
   uint16_t *cands = nullptr;  // this wave's candidate slots of the grouped sphere scan
   if ((F & F_SGROUP) && lc.cand_off >= 0)
     cands = reinterpret_cast<uint16_t *>(smem + lc.cand_off) +
             __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (64 * kSphCand + 128);  // slots + 64 counters
-  const bool mats_in_lds = lc.lds_mats > 0;
+  const bool mats_in_lds = (M & PIN_LDS_TABLES) || lc.lds_mats > 0;
   auto lds_rgb = [&](int m) -> V3 {  // a staged material's colour: one 16-byte read (MatRec: r, g, b, kind)
     const float4 c = load_lds<float4>(s_mats + m);
     return mk(c.x, c.y, c.z);
@@ -203,7 +209,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   auto lds_byte = [&](uint32_t byte_offset) -> uint32_t {
     return *(const RT_LDS uint8_t *)(uintptr_t)byte_offset;
   };
-  const bool fast_fold = mats_in_lds && lc.wide_ids != 1 && sc.unsigned_colours;  // see the radiance fold
+  const bool fast_fold = FOLD4 || (mats_in_lds && lc.wide_ids != 1 && sc.unsigned_colours);  // see the radiance fold
   if (mats_in_lds) {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.mats);
     uint32_t *dst = reinterpret_cast<uint32_t *>(s_mats);
@@ -224,7 +230,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   const int64_t n_items = fr.items;
   const bool w_pow2 = (fr.width & (fr.width - 1)) == 0, h_pow2 = (fr.height & (fr.height - 1)) == 0;
   const double inv_w = 1.0 / (double)fr.width, inv_h = 1.0 / (double)fr.height;
-  const bool f32_jitter = w_pow2 && h_pow2 && fr.width <= (1 << 20) && fr.height <= (1 << 20);  // (wave-uniform)
+  const bool f32_jitter = (M & PIN_POW2_FRAME) || (w_pow2 && h_pow2 && fr.width <= (1 << 20) && fr.height <= (1 << 20));  // (wave-uniform)
   // per-lane pixel state
   int32_t q32 = -1;  // the lane's work item (items < 2^31: make_frame); widened where it addresses memory; -1: none yet
   uint32_t work_px = 0;  // (cost probe) lane-steps of the mesh searches of this pixel's rays
@@ -314,7 +320,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       if (k_end_px <= 0) return false;
     } else if (idx < 0 || fr.spp <= 0) {
       out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
-      if (ray_counts) ray_counts[q] = 0;
+      if ((M & PIN_CHAINS) || ray_counts) ray_counts[q] = 0;
       return false;
     }
     if (!RAYS) pij = ((uint32_t)(idx / fr.width) << 16) | (uint32_t)(idx % fr.width);
@@ -328,7 +334,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     rays = 0;
     work_px = 0;
     color = splat(0.f);
-    if (fr.k_begin > 0) {  // (wave-uniform) resume: the first pass left the pixel's raw sum and ray count in the buffers
+    if ((M & PIN_CHAINS) || fr.k_begin > 0) {  // (wave-uniform) resume: the first pass left the pixel's raw sum and ray count in the buffers
       color = mk(out[q * 3 + 0], out[q * 3 + 1], out[q * 3 + 2]);
       rays = ray_counts[q] & 0x7fffffffu;  // (bit 31: the scheduler's head mark on a mesh frame)
     }
@@ -354,8 +360,12 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // A frame with fewer pixels than the grid has lanes (C1: 65,536 on 262,144) is spread THIN: one pixel per
   // lane_stride lanes, so that every SIMD gets a wave and a wave's shared candidate tests serve 16 rays with 64 lanes
   // instead of 64 rays on a quarter of the SIMDs.  The idle lanes never fetch; they work in closest_hit.
-  if (!(F & F_BVH) && lc.lane_stride > 1 && (threadIdx.x & (uint32_t)(lc.lane_stride - 1)) != 0u) done = true;
-  if (!QUEUE && !(F & F_BVH) && lc.chain_next != nullptr) {  // planned chains: this wave's chain and its first tile
+  if (!(F & F_BVH) && !(M & PIN_EVERY_LANE) && lc.lane_stride > 1 && (threadIdx.x & (uint32_t)(lc.lane_stride - 1)) != 0u) done = true;
+  // (macros, not values or lambdas: the unpinned kernels must compile to what they were, testing the launch's fields
+  // where they always did)
+#define RTMI_CHAINS (!QUEUE && !(F & F_BVH) && !(M & PIN_QUEUE) && ((M & PIN_CHAINS) || lc.chain_next != nullptr))  // (wave-uniform) planned chains
+#define RTMI_PRIO ((M & PIN_PRIORITIES) || lc.prio_tab != nullptr)
+  if (RTMI_CHAINS) {  // planned chains: this wave's chain and its first tile
     const int chain = wave_chain_id(lc.prio_tab, counters + 35, lc.plan_simds, lc.plan_rounds);
     const int32_t t = chain >= 0 ? lc.chain_first[chain] : -1;
     heavy = t < 0;
@@ -368,7 +378,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   }
   for (;;) {
     RTMI_STAT(const unsigned long long tq0 = stat_now();)
-    if (lc.prio_tab != nullptr && (prio_tick++ & (uint32_t)(lc.prio_every - 1)) == 0u) {
+    if (RTMI_PRIO && (prio_tick++ & (uint32_t)(lc.prio_every - 1)) == 0u) {
       // queries this lane's pixel still has to do, from its own rays per sample so far (+ 8 rays over one more sample:
       // a pixel that has not started counts as an average one)
       // -- with the scheduler's probe behind the launch, its tile's rays per sample stand in as 64 samples' worth of
@@ -376,9 +386,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       float left = 0.f;
       if (has_px && (active || k < k_end())) {
         float prior_rays = 8.f, prior_n = 1.f;
-        if (lc.tile_cost != nullptr) prior_rays = 64.f * ((float)lc.tile_cost[q32 >> 6] * lc.rate_scale), prior_n = 64.f;
+        if ((M & PIN_CHAINS) || lc.tile_cost != nullptr) prior_rays = 64.f * ((float)lc.tile_cost[q32 >> 6] * lc.rate_scale), prior_n = 64.f;
         left = ((float)rays + prior_rays) * (float)(k_end() - k + 1) * __builtin_amdgcn_rcpf((float)k + prior_n);
-        if (!(F & F_BVH) && lc.chain_next != nullptr && !heavy) left += (float)lc.chain_fut[q32 >> 6];
+        if (!(F & F_BVH) && !(M & PIN_QUEUE) && ((M & PIN_CHAINS) || lc.chain_next != nullptr) && !heavy) left += (float)lc.chain_fut[q32 >> 6];
       }
       wave_priority_update(lc.prio_tab, (uint32_t)fminf(left, 4.0e9f));
     }
@@ -398,7 +408,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         if (sq) sq[q * 3 + 0] = moment.x, sq[q * 3 + 1] = moment.y, sq[q * 3 + 2] = moment.z;
         samples[q] += (uint32_t)k;
         if (ray_counts) ray_counts[q] += rays;
-      } else if (ray_counts) ray_counts[q] = rays;
+      } else if ((M & PIN_CHAINS) || ray_counts) ray_counts[q] = rays;
       if ((F & F_BVH) && lc.visit_counts != nullptr) lc.visit_counts[q] = work_px;
       // the lane's ray total in ONE register: 2^31 at a time goes to the global counter (a constant addend: the
       // compiler's wave-level combining of atomics needs no scan for it), the rest at the end of the kernel
@@ -465,7 +475,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
       }
-    } else if (!QUEUE && !(F & F_BVH) && lc.chain_next != nullptr) {  // (wave-uniform) planned chains
+    } else if (RTMI_CHAINS) {  // (wave-uniform) planned chains
       const uint32_t me = ((blockIdx.x * n_threads + threadIdx.x) >> 6) + 1u;  // this wave's mark in `claims`
       if (!active && !has_px && !heavy) {  // (`heavy` in this mode: the lane has walked its chain to the end)
         for (;;) {
@@ -628,10 +638,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     RTMI_STAT(wave_queries++; const unsigned long long tq1 = stat_now(); st.cyc[0] += tq1 - tq0;
               const unsigned long long in0 = st.cyc[2] + st.cyc[3];)
     Hit h = {};
-    const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && ll != nullptr && sc.n_pairs >= kCullMinPairs) ||
+    const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs))) ||
                               ((F & F_SGROUP) && cands != nullptr);  // wave-uniform
     if (all_lanes_in)  // every lane goes in, with or without a ray of its own: see closest_hit
-      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (QUEUE ? 0 : 2), o, d, active,
+      h = closest_hit<F, false, M>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (QUEUE ? 0 : 2), o, d, active,
                          (F & F_BVH) && lc.visit_counts != nullptr
 #ifdef RTMI_STATS
                          , st
@@ -662,7 +672,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
 #endif
     if (active) {
       if (!all_lanes_in)
-        h = closest_hit<F>(sc, s_nodes, 0, s_paths, 0, s_pairs, nullptr, nullptr, nullptr, nullptr, o, d, true, false
+        h = closest_hit<F, false, M & ~(uint32_t)PIN_LDS_TABLES>(sc, s_nodes, 0, s_paths, 0, s_pairs, nullptr, nullptr, nullptr, nullptr, o, d, true, false
 #ifdef RTMI_STATS
                            , st
 #endif
@@ -692,7 +702,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           if ((F & F_TRIS) && kind == RUN_TRIS) {
             V3 n;
             int flags;
-            if (s_pairs != nullptr) {  // (wave-uniform) the winner's record is in LDS
+            if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) the winner's record is in LDS
               const float4 tn = s_nrm[index];
               n = mk(tn.x, tn.y, tn.z);
               mat = __float_as_int(tn.w) & 0xffffff, flags = __float_as_int(tn.w) >> 24;
@@ -887,7 +897,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
             }
           }
         }
-        for (; i >= 0; i--) {
+        for (; !FOLD4 && i >= 0; i--) {  // (FOLD4: the nibble fold above has left no level)
           V3 a;
           if (tex32) {
             const uint32_t lw = *reinterpret_cast<const uint32_t *>(smem + tex_layer_offset(i));
@@ -924,7 +934,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     RTMI_STAT(st.cyc[4] += stat_now() - tq2;)
   }
 
-  if (lc.prio_tab != nullptr) wave_priority_leave(lc.prio_tab);
+  if (RTMI_PRIO) wave_priority_leave(lc.prio_tab);
+#undef RTMI_CHAINS
+#undef RTMI_PRIO
   {  // total closest-hit queries: wave reduce, one atomic per wave
     unsigned long long ray_total = ray_acc;
     for (int off = 32; off > 0; off >>= 1) ray_total += __shfl_down(ray_total, off);

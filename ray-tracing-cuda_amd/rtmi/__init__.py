@@ -21,6 +21,8 @@ STATE_WORDS = 6
 MAX_DEPTH = 64
 TRACE_WORK_WORDS = 256  # RTMI_TRACE_WORK_WORDS: the device words of one rtmi_trace call
 BUDGET_WORK_WORDS = TRACE_WORK_WORDS  # RTMI_BUDGET_WORK_WORDS: the device words of one rtmi_render_budget call
+MODE_FIELDS = 9  # RTMI_MODE_FIELDS: the words of rtmi_render_mode_ex
+FAST_PATH_FACTS = 14  # RTMI_FAST_PATH_FACTS: the words rtmi_fast_path_kernel reads
 MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
 
 # rtmi_hit.kind (include/rtmi.h)
@@ -50,18 +52,18 @@ class RenderOpts(C.Structure):
                 ("threads_per_block", C.c_int32), ("sparse_stride", C.c_int32), ("exclusive", C.c_int32),
                 ("outlier_x10", C.c_int32), ("probe_spp", C.c_int32), ("head_pct", C.c_int32 * 3),
                 ("plan", C.c_int32), ("wave_priority", C.c_int32), ("lane_stride", C.c_int32),
-                ("promote_after", C.c_int32), ("cost_probe", C.c_int32), ("first_pass", C.c_int32), ("reserved", C.c_int32),
+                ("promote_after", C.c_int32), ("cost_probe", C.c_int32), ("first_pass", C.c_int32), ("fast_path", C.c_int32),
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
 def render_opts(schedule=-1, blocks_per_cu=0, threads_per_block=0, sparse_stride=0, exclusive=-1, outlier_x10=0,
                 probe_spp=0, head_pct=(0, 0, 0), scratch=None, plan=-1, wave_priority=-1, lane_stride=0, promote_after=-1,
-                cost_probe=-1, first_pass=-1):
+                cost_probe=-1, first_pass=-1, fast_path=0):
     """``scratch``: a torch uint8/int32 CUDA tensor of at least ``scratch_bytes(frame)`` bytes that holds ALL
     per-call state of the render (keep it alive until the render has finished)."""
     o = RenderOpts(C.sizeof(RenderOpts), schedule, blocks_per_cu, threads_per_block, sparse_stride, exclusive,
                    outlier_x10, probe_spp, (C.c_int32 * 3)(*head_pct), plan, wave_priority, lane_stride, promote_after,
-                   cost_probe, first_pass, 0, None, 0)
+                   cost_probe, first_pass, fast_path, None, 0)
     if scratch is not None:
         o.d_scratch = scratch.data_ptr()
         o.scratch_bytes = scratch.numel() * scratch.element_size()
@@ -145,6 +147,8 @@ SYMBOLS = [
     ("rtmi_render_scratch_bytes", C.c_size_t, [_frp]),
     ("rtmi_render_launch_shape", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), C.POINTER(C.c_int32)]),
     ("rtmi_render_mode", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), C.POINTER(C.c_int32)]),
+    ("rtmi_render_mode_ex", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), C.POINTER(C.c_int32), C.c_int]),
+    ("rtmi_fast_path_kernel", C.c_int, [C.POINTER(C.c_int32)]),
     ("rtmi_render_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     ("rtmi_last_ray_total", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     ("rtmi_debug_counters", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_void_p]),
@@ -752,13 +756,13 @@ class Renderer:
         return dict(zip(("blocks", "threads", "blocks_per_cu", "compute_units"), list(out)))
 
     def mode(self, opts=None):
-        """How a render of this frame would be scheduled (rtmi_render_mode)."""
-        out = (C.c_int32 * 8)()
+        """How a render of this frame would be scheduled, and whether its last launch is a fast kernel (rtmi_render_mode_ex)."""
+        out = (C.c_int32 * MODE_FIELDS)()
         with self.torch.cuda.device(self.device):
-            _check(self.L.rtmi_render_mode(self.scene.h, C.byref(self.frame), C.byref(opts) if opts is not None else None, out),
-                   "rtmi_render_mode")
+            _check(self.L.rtmi_render_mode_ex(self.scene.h, C.byref(self.frame), C.byref(opts) if opts is not None else None, out,
+                                              MODE_FIELDS), "rtmi_render_mode_ex")
         return dict(zip(("scheduled", "first_pass_samples", "first_pass_resumed", "planned_chains", "wave_priority_every",
-                         "lane_stride", "waves", "tiles"), list(out)))
+                         "lane_stride", "waves", "tiles", "fast_path"), list(out)))
 
     def total_rays(self, scratch=None):
         """Closest-hit queries of the last render (of the one that used ``scratch``, if given); raises when that
