@@ -142,6 +142,24 @@ static int device_cus(int dev, int *n_cu) {
   *n_cu = it->second;
   return RTMI_OK;
 }
+// The scene's device must be the current one.  *n_cu (optional): its compute units.
+static int scene_device(const Scene *s, int *n_cu) {
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  return n_cu ? device_cus(dev, n_cu) : RTMI_OK;
+}
+static int check_depth(int max_depth) {
+  if (max_depth < 0 || max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
+  return RTMI_OK;
+}
+// a pixel's closest-hit queries (at most max_depth + 1 per sample, ray_tracing.cu:22) are counted in 31 bits of its
+// ray_counts word (bit 31: the scheduler's mark) and of the trace kernel's register
+static int check_pixel_queries(const FrameDev &d) {
+  if ((int64_t)d.spp * (d.max_depth + 1) > (int64_t)RTMI_MAX_PIXEL_QUERIES)
+    return fail(RTMI_ERR_INVALID, "spp x (max_depth + 1) above 2^31 - 1 (RTMI_MAX_PIXEL_QUERIES): a pixel's closest-hit queries are counted in 31 bits");
+  return RTMI_OK;
+}
 
 template <typename R>
 static int upload(Scene *s, const std::vector<R> &v, const R **out) {
@@ -700,11 +718,8 @@ struct LaunchShape {
 };
 static constexpr int kMaxLaneStride = 16;
 static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &tune, LaunchShape *out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
   int n_cu = 0;
-  if (int rc = device_cus(dev, &n_cu)) return rc;
+  if (int rc = scene_device(s, &n_cu)) return rc;
   const uint32_t variant = pick_variant(s->features);
   int threads = tune.threads > 0 ? tune.threads : 256;
   if (threads > 256 && !(variant & F_BVH)) threads = 256;  // only the mesh kernels are built for larger workgroups
@@ -873,12 +888,9 @@ static int batch_prologue(const rtmi_scene *sp, int64_t n, bool arrays, const ch
   if (n > 0 && !arrays) return fail(RTMI_ERR_INVALID, null_arrays);
   const Scene *s = *out = S(sp);
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  if (max_depth && (*max_depth < 0 || *max_depth > RTMI_MAX_DEPTH))
-    return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
-  return n == 0 ? RTMI_OK : device_cus(dev, n_cu);
+  if (max_depth)
+    if (int rc = check_depth(*max_depth)) return rc;
+  return scene_device(s, n == 0 ? nullptr : n_cu);
 }
 
 // ------------------------------------------------------------------ closest-hit queries
@@ -962,7 +974,7 @@ int rtmi_trace(const rtmi_scene *sp, int64_t n, const float *d_origins, const fl
   hipStream_t st = (hipStream_t)stream;
   // the counter words (abandoned searches, queries, queue cursor) start from zero; the argument block behind them is
   // written by launch_trace
-  HIP_TRY(hipMemsetAsync(d_work, 0, kTraceParamsOffset, st));
+  HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));
   HIP_TRY(launch_trace(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, n, max_depth, d_origins, d_dirs,
                        reinterpret_cast<uint32_t *>(d_states), d_radiance, d_ray_counts, d_work, st));
   return RTMI_OK;
@@ -1003,19 +1015,15 @@ int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32
     return fail(RTMI_ERR_DEPTH, "max_depth must be at least 1 with a feature buffer: at depth 0 Trace never looks at the primary hit");
   const Scene *s = S(sp);
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  if (d.max_depth < 0 || d.max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
+  if ((rc = check_depth(d.max_depth))) return rc;
   if (d.post) return fail(RTMI_ERR_INVALID, "post_process must be 0: per-pixel sample counts have no uniform division (rtmi_resolve)");
   // (spp caps one call's samples per pixel: a call's closest-hit queries of a pixel stay below 2^31 as a render's do)
-  if ((int64_t)d.spp * (d.max_depth + 1) > (int64_t)RTMI_MAX_PIXEL_QUERIES)
-    return fail(RTMI_ERR_INVALID, "spp x (max_depth + 1) above 2^31 - 1 (RTMI_MAX_PIXEL_QUERIES): a pixel's closest-hit queries are counted in 31 bits");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != s->device) return fail(RTMI_ERR_INVALID, "scene was committed on another device");
+  if ((rc = check_pixel_queries(d))) return rc;
   int n_cu = 0;
-  if ((rc = device_cus(dev, &n_cu))) return rc;
+  if ((rc = scene_device(s, &n_cu))) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the counter words start from zero; the argument block behind them is written by launch_budget
-  HIP_TRY(hipMemsetAsync(d_work, 0, kBudgetParamsOffset, st));
+  HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));
   if (d.spp == 0) return RTMI_OK;  // (every budget is capped at 0: nothing to render)
   HIP_TRY(launch_budget(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, d, d_budget,
                         reinterpret_cast<uint32_t *>(d_states), d_sum, d_sq, d_samples, d_ray_counts, &fb, d_work, st));
@@ -1080,11 +1088,7 @@ int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   FrameDev d;
   if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
-  if (d.max_depth < 0 || d.max_depth > RTMI_MAX_DEPTH) return fail(RTMI_ERR_DEPTH, "max_depth outside [0, 64]");
-  // a pixel's closest-hit queries (at most max_depth + 1 per sample, ray_tracing.cu:22) are counted in 31 bits of its
-  // ray_counts word (bit 31: the scheduler's mark) and of the trace kernel's register
-  if ((int64_t)d.spp * (d.max_depth + 1) > (int64_t)RTMI_MAX_PIXEL_QUERIES)
-    return fail(RTMI_ERR_INVALID, "spp x (max_depth + 1) above 2^31 - 1 (RTMI_MAX_PIXEL_QUERIES): a pixel's closest-hit queries are counted in 31 bits");
+  if ((rc = check_depth(d.max_depth)) || (rc = check_pixel_queries(d))) return rc;
   LaunchShape ls;
   if ((rc = launch_shape(s, d, tune, &ls))) return rc;
   const uint32_t variant = ls.variant;

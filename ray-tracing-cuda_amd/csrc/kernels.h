@@ -162,8 +162,8 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
                             unsigned long long *d_check, hipStream_t stream);
 // Radiance of caller rays (rtmi_trace; kernels.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
 // words, zeroed in stream order before the call -- [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's
-// cursor, and from byte kTraceParamsOffset the kernel's argument block (written in stream order just before the launch).
-constexpr size_t kTraceParamsOffset = 256;  // (a 128-byte line of its own, away from the counter words)
+// cursor, and from byte kCallParamsOffset the kernel's argument block (written in stream order just before the launch).
+constexpr size_t kCallParamsOffset = 256;  // (a 128-byte line of its own, away from the counter words)
 // tex_layers: the scene's features hold F_TEX (image textures, or more materials than the 16-bit id stack holds); without
 // it the F_TEX kernel keeps the untextured id stack.
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
@@ -172,7 +172,6 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
 // Per-pixel sample budgets (rtmi_render_budget; kernels.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).
-constexpr size_t kBudgetParamsOffset = kTraceParamsOffset;
 hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &fr,
                          const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
                          uint32_t *d_ray_counts, const FeatureBufs *feat, unsigned long long *d_work, hipStream_t stream);

@@ -47,6 +47,7 @@
 #include "kernels.h"
 
 #include <cstdlib>
+#include <iterator>
 #include <type_traits>
 #include "scene_dev.h"
 #include "vec.h"
@@ -146,90 +147,55 @@ __global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev f
 // Mesh variants share their per-workgroup tables (reference-tree nodes, materials) between more waves:
 // workgroups of up to 512 lanes, two of which fill a CU's LDS with 16 waves' search regions.
 #define RTMI_MAX_THREADS(F) (((F) & F_BVH) ? 512 : 256)
-// Everything the trace kernel is told lives in ONE block of device memory (written by params_write_kernel, stream-ordered,
-// just before the launch) and the kernel's only argument is its address.  By-value kernel arguments are all loaded in
-// the kernel's first block and stay live from there: with ~150 dwords of them the list kernel parked 76-114 scalars in
-// spill lanes (v_writelane / v_readlane at every use), the mesh kernel 285.  Read through the constant address space
-// the fields arrive by scalar loads where they are used -- the hot loop's stay in SGPRs, the rest never occupy one.
-struct RenderParams {
-  SceneDev sc;
-  FrameDev fr;
-  LaunchCfg lc;
-  uint32_t *states;
-  float *out;
-  uint32_t *ray_counts;
-  unsigned long long *counters;
-};
-__global__ void params_write_kernel(RenderParams p, RenderParams *dst) {
+// One lane copies a kernel's argument block (render_body.h: RenderParams, CallParams) to where the kernel reads it.
+template <class P>
+__global__ void params_write_kernel(P p, P *dst) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
 }
 size_t render_params_bytes() { return (sizeof(RenderParams) + 255) & ~(size_t)255; }
+// The block of rtmi_trace, rtmi_render_budget and rtmi_render_features sits in the call's own d_work, behind the
+// kernel's counter words (launch_call).
+static_assert(kCallParamsOffset + sizeof(CallParams) <= (size_t)RTMI_TRACE_WORK_WORDS * 8u,
+              "RTMI_TRACE_WORK_WORDS must hold the caller-owned kernels' argument block");
+static_assert(kCallParamsOffset % alignof(CallParams) == 0, "the argument block is aligned in d_work");
 
 // M: the mode word (kernels.h).  0 is the general kernel; kFastChains and kFastQueue are instantiated for the
 // list-triangle variant (launch_render) and launched when fast_path_mode says the launch is what they were compiled for.
 template <uint32_t F, uint32_t M = 0>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void render_kernel(const RenderParams *p) {
-  // (global -> constant address space -> generic: the compiler's address-space inference turns every access through
-  // kp back into a constant-address-space load, i.e. a scalar load that nothing in the kernel can clobber)
-  const RenderParams *kp = (const RenderParams *)(const RT_CONSTANT RenderParams *)(uintptr_t)p;
-  render_body<F, false, false, false, M>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
+  const RenderParams &rp = in_constant(p);
+  render_body<F, false, false, false, M>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters);
 }
 template <uint32_t F, uint32_t M = 0>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void probe_kernel(const RenderParams *p) {
-  const RenderParams *kp = (const RenderParams *)(const RT_CONSTANT RenderParams *)(uintptr_t)p;
-  render_body<F, false, false, false, M>(kp->sc, kp->fr, kp->lc, kp->states, kp->out, kp->ray_counts, kp->counters);
+  const RenderParams &rp = in_constant(p);
+  render_body<F, false, false, false, M>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters);
 }
-// rtmi_trace: the same body in its caller-ray mode, its argument block read the render's way (constant address space)
-// from the call's own d_work, behind the kernel's counter words (launch_trace).
-struct TraceParams {
-  RenderParams rp;
-  const float *origins, *dirs;
-  int32_t tex_layers;  // 0: the scene samples no image texture, its layers are material ids (render_body.h)
-};
-static_assert(kTraceParamsOffset + sizeof(TraceParams) <= (size_t)RTMI_TRACE_WORK_WORDS * 8u,
-              "RTMI_TRACE_WORK_WORDS must hold the trace kernel's argument block");
-static_assert(kTraceParamsOffset % alignof(TraceParams) == 0, "the argument block is aligned in d_work");
-__global__ void trace_params_write_kernel(TraceParams p, TraceParams *dst) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
-}
+// rtmi_trace: the same body in its caller-ray mode.
 template <uint32_t F>
-__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void trace_kernel(const TraceParams *p) {
-  const TraceParams *kp = (const TraceParams *)(const RT_CONSTANT TraceParams *)(uintptr_t)p;
-  render_body<F, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
-                       kp->origins, kp->dirs, kp->tex_layers != 0);
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void trace_kernel(const CallParams *p) {
+  const RenderParams &rp = in_constant(p).rp;
+  const CallExtras &ex = in_constant(p).ex;
+  render_body<F, true>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters, ex.rays.origins, ex.rays.dirs, ex.tex_layers != 0);
 }
-
-// rtmi_render_budget: the same body in its budget mode, its argument block read from the call's own d_work as the trace
-// kernel's is.  F always holds F_DEFOCUS (launch_budget): whether a sample draws a lens offset is decided by the
-// wave-uniform sc.cam.defocus at run time, so the eight query variants serve both cameras.
-struct BudgetParams {
-  RenderParams rp;
-  const uint32_t *budget;
-  float *sq;
-  uint32_t *samples;
-  int32_t tex_layers;  // as TraceParams::tex_layers
-  FeatureBufs feat;    // rtmi_render_features: read by feature_kernel only (all null for budget_kernel)
-};
-static_assert(kBudgetParamsOffset + sizeof(BudgetParams) <= (size_t)RTMI_BUDGET_WORK_WORDS * 8u,
-              "RTMI_BUDGET_WORK_WORDS must hold the budget kernel's argument block");
-static_assert(kBudgetParamsOffset % alignof(BudgetParams) == 0, "the argument block is aligned in d_work");
-__global__ void budget_params_write_kernel(BudgetParams p, BudgetParams *dst) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
-}
+// rtmi_render_budget: the same body in its budget mode.  F always holds F_DEFOCUS (launch_budget): whether a sample
+// draws a lens offset is decided by the wave-uniform sc.cam.defocus at run time, so the eight query variants serve both
+// cameras.
 template <uint32_t F>
-__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void budget_kernel(const BudgetParams *p) {
-  const BudgetParams *kp = (const BudgetParams *)(const RT_CONSTANT BudgetParams *)(uintptr_t)p;
-  render_body<F, false, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
-                              nullptr, nullptr, kp->tex_layers != 0, kp->budget, kp->sq, kp->samples);
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void budget_kernel(const CallParams *p) {
+  const RenderParams &rp = in_constant(p).rp;
+  const CallExtras &ex = in_constant(p).ex;
+  render_body<F, false, true>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters, nullptr, nullptr,
+                              ex.tex_layers != 0, ex.px.budget, ex.px.sq, ex.px.samples);
 }
-// rtmi_render_features: budget_kernel's twin with the FEATURES flag of the body set -- at a sample's primary hit the lane
-// adds the hit's albedo, normal, depth and coverage into its item's words of kp->feat.  A kernel of its own, so that
+// rtmi_render_features: budget_kernel's twin with the FEATURES flag of the body set.  A kernel of its own, so that
 // budget_kernel stays instruction for instruction what it is.
 template <uint32_t F>
-__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void feature_kernel(const BudgetParams *p) {
-  const BudgetParams *kp = (const BudgetParams *)(const RT_CONSTANT BudgetParams *)(uintptr_t)p;
-  render_body<F, false, true, true>(kp->rp.sc, kp->rp.fr, kp->rp.lc, kp->rp.states, kp->rp.out, kp->rp.ray_counts, kp->rp.counters,
-                                    nullptr, nullptr, kp->tex_layers != 0, kp->budget, kp->sq, kp->samples, &kp->feat);
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)F_DEFOCUS)) void feature_kernel(const CallParams *p) {
+  const RenderParams &rp = in_constant(p).rp;
+  const CallExtras &ex = in_constant(p).ex;
+  render_body<F, false, true, true>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters, nullptr, nullptr,
+                                    ex.tex_layers != 0, ex.px.budget, ex.px.sq, ex.px.samples, &ex.feat);
 }
 
 // ------------------------------------------------------------------ untile / post
@@ -695,34 +661,30 @@ static hipError_t dynamic_lds(size_t lds) {
   return no_static;
 }
 
-// The specialisations that are instantiated; a feature set outside them uses F_ALL.
-#define RTMI_FOR_EACH_VARIANT(X)                     \
-  X(0u)                                              \
-  X(F_TRIS)                                          \
-  X(F_SPHERE)                                        \
-  X(F_TRIS | F_SPHERE)                               \
-  X(F_SPHERE | F_SGROUP)                             \
-  X(F_TRIS | F_SPHERE | F_SGROUP)                    \
-  X(F_TRIS | F_BVH)                                  \
-  X(F_TRIS | F_SPHERE | F_TEX)                       \
-  X(F_ALL)
-
-uint32_t pick_variant(uint32_t features) {
-#define X(V) \
-  if ((features & ~(uint32_t)(V)) == 0) return (V);
-  RTMI_FOR_EACH_VARIANT(X)
-#undef X
-  return F_ALL;
+// The specialisations that are instantiated; a feature set outside them uses the last, which has every feature.
+constexpr uint32_t kVariants[] = {0u, F_TRIS, F_SPHERE, F_TRIS | F_SPHERE, F_SPHERE | F_SGROUP, F_TRIS | F_SPHERE | F_SGROUP,
+                                  F_TRIS | F_BVH, F_TRIS | F_SPHERE | F_TEX, F_ALL};
+// The query variants (rtmi_intersect, rtmi_occluded, rtmi_trace, rtmi_render_budget): F_TEX always (closest_hit tracks
+// the winner's u, v bitwise only then), never F_DEFOCUS (no camera is involved): the render variants so mapped.
+constexpr uint32_t kQueryVariants[] = {F_TEX, F_TRIS | F_TEX, F_SPHERE | F_TEX, F_TRIS | F_SPHERE | F_TEX,
+                                       F_SPHERE | F_SGROUP | F_TEX, F_TRIS | F_SPHERE | F_SGROUP | F_TEX,
+                                       F_TRIS | F_BVH | F_TEX, F_ALL & ~F_DEFOCUS};
+template <size_t N>
+static uint32_t pick_listed(const uint32_t (&list)[N], uint32_t features) {
+  for (const uint32_t v : list)
+    if ((features & ~v) == 0) return v;
+  return list[N - 1];
 }
-
-// f(std::integral_constant<uint32_t, V>()) for the instantiated variant V that equals `variant`; `otherwise` for any other.
-template <class R, class Fn>
-static R with_variant(uint32_t variant, R otherwise, Fn &&f) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) return f(std::integral_constant<uint32_t, (V)>());
-  RTMI_FOR_EACH_VARIANT(X)
-#undef X
-  return otherwise;
+uint32_t pick_variant(uint32_t features) { return pick_listed(kVariants, features); }
+uint32_t pick_query_variant(uint32_t features) {
+  return pick_listed(kQueryVariants, (features & ~(uint32_t)F_DEFOCUS) | F_TEX);
+}
+// f(std::integral_constant<uint32_t, V>()) for the variant V of List that equals `variant`; `otherwise` for any other.
+template <const auto &List, size_t I = 0, class R, class Fn>
+static R with_listed(uint32_t variant, R otherwise, Fn &&f) {
+  if constexpr (I == std::size(List)) return otherwise;
+  else if (variant == List[I]) return f(std::integral_constant<uint32_t, List[I]>());
+  else return with_listed<List, I + 1>(variant, otherwise, f);
 }
 
 // ------------------------------------------------------------------ the fast path's predicate
@@ -757,27 +719,46 @@ uint32_t launch_fast_path(uint32_t variant, const SceneDev &sc, const FrameDev &
   return fast_path_mode(f);
 }
 
-// Workgroups of Kernel per compute unit at this launch shape (0: it does not fit).
+// *per_cu = workgroups of Kernel per compute unit at this launch shape; 0 with an error: it does not fit, or the HIP
+// call that failed.
 template <auto Kernel>
-static int kernel_occupancy(int threads, size_t lds) {
-  int nb = 0;
-  if (dynamic_lds<Kernel>(lds) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, lds) != hipSuccess) nb = 0;
-  return nb;
+static hipError_t kernel_occupancy(int threads, size_t lds, int *per_cu) {
+  *per_cu = 0;
+  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
+  hipError_t e = dynamic_lds<Kernel>(lds);
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, Kernel, threads, lds);
+  if (e != hipSuccess) *per_cu = 0;
+  return e;
+}
+// A launch of Kernel on its argument block: the block goes to d_block in stream order, just before the kernel that reads it.
+struct LaunchAt {
+  int blocks, threads;
+  size_t lds;
+  hipStream_t stream;
+};
+template <auto Kernel, class P>
+static hipError_t launch_block(const LaunchAt &at, const P &block, P *d_block) {
+  const hipError_t e = dynamic_lds<Kernel>(at.lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(params_write_kernel<P>, dim3(1), dim3(64), 0, at.stream, block, d_block);
+  hipLaunchKernelGGL(Kernel, dim3(at.blocks), dim3(at.threads), at.lds, at.stream, (const P *)d_block);
+  return hipGetLastError();
 }
 int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, bool fast_path) {
-  return with_variant(variant, 0, [&](auto v) {
+  return with_listed<kVariants>(variant, 0, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     size_t lds = 0;
     (void)make_cfg(F, sc, fr, threads, &lds);
-    if (threads > RTMI_MAX_THREADS(F) || lds > 160 * 1024) return 0;
-    int nb = kernel_occupancy<render_kernel<F>>(threads, lds);
+    if (threads > RTMI_MAX_THREADS(F)) return 0;
+    int nb = 0;
+    (void)kernel_occupancy<render_kernel<F>>(threads, lds, &nb);
     if constexpr (F == (uint32_t)F_TRIS) {
       // which of the three kernels a launch of this frame gets is decided after the grid is sized (lane stride, plan):
       // the grid must fit whichever it is (all three are built for the same waves per SIMD and use the same LDS)
       if (fast_path) {
-        const int nc = kernel_occupancy<render_kernel<F, kFastChains>>(threads, lds);
-        const int nq = kernel_occupancy<render_kernel<F, kFastQueue>>(threads, lds);
+        int nc = 0, nq = 0;
+        (void)kernel_occupancy<render_kernel<F, kFastChains>>(threads, lds, &nc);
+        (void)kernel_occupancy<render_kernel<F, kFastQueue>>(threads, lds, &nq);
         nb = nb < nc ? nb : nc, nb = nb < nq ? nb : nq;
       }
     }
@@ -785,10 +766,20 @@ int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, i
   });
 }
 
+// Work items per atomic of a queue in image order: its last tiles weigh as much as any, so batches only where the atomics
+// would otherwise be the frame -- cornell 1024^2 x 16 spp: 8.0 ms a pixel at a time, 5.2 ms four at a time; at 200 spp
+// sixteen at a time cost 8 %
+// (below 32 samples -- where list frames are not scheduled -- 256 / samples: at 24 spp two pixels per atomic left a 2048^2
+// frame at the cursor's rate, 23.8 ms against 22.1 ms for 32 spp)
+static int image_order_batch(int samples, int cap) {
+  const int per_atomic = samples < 32 ? 256 / (samples > 0 ? samples : 1) : 64 / samples;
+  return per_atomic < 1 ? 1 : per_atomic > cap ? cap : per_atomic;
+}
+
 hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
                          uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan, bool probe,
                          int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream) {
-  return with_variant(variant, hipErrorInvalidValue, [&](auto v) {
+  return with_listed<kVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     size_t lds = 0;
     LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds);
@@ -817,37 +808,24 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
       // (a pooled item waits for a lane of its wave: the longer a pixel takes, the fewer -- from 4,096 samples on, none)
       const int samples = fr.k_end - fr.k_begin > 0 ? fr.k_end - fr.k_begin : 1;
       const int by_length = 4096 / samples < 1 ? 1 : 4096 / samples;
-      // image order (a frame too short to be scheduled, or a first pass as long as a frame): its last tiles weigh as much as
-      // any, so batches only where the atomics would otherwise be the frame -- cornell 1024^2 x 16 spp: 8.0 ms a pixel at
-      // a time, 5.2 ms four at a time; at 200 spp sixteen at a time cost 8 %
-      // (below 32 spp -- where list frames are not scheduled -- 256 / samples: at 24 spp two pixels per atomic left a 2048^2
-      // frame at the cursor's rate, 23.8 ms against 22.1 ms for 32 spp)
-      const int per_atomic = samples < 32 ? 256 / samples : 64 / samples;
-      const int image_batch = per_atomic < 1 ? 1 : per_atomic > 16 ? 16 : per_atomic;
-      lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_batch;
+      // image order (a frame too short to be scheduled, or a first pass as long as a frame): image_order_batch
+      lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_order_batch(samples, 16);
     }
     RenderParams rp;
     rp.sc = sc, rp.fr = fr, rp.lc = lc;
     rp.states = d_states, rp.out = d_out, rp.ray_counts = d_ray_counts, rp.counters = d_counters;
     RenderParams *dp = reinterpret_cast<RenderParams *>(d_params);
-    auto launch = [&](auto kernel) -> hipError_t {
-      constexpr auto Kernel = decltype(kernel)::value;
-      const hipError_t e = dynamic_lds<Kernel>(lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(params_write_kernel, dim3(1), dim3(64), 0, stream, rp, dp);
-      hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(threads), lds, stream, (const RenderParams *)dp);
-      return hipGetLastError();
-    };
+    const LaunchAt at{blocks, threads, lds, stream};
     if constexpr (F == (uint32_t)F_TRIS) {
       // the kernels compiled for the common list frame, when this launch is one (fast_path_mode; a probe never walks chains)
       const uint32_t mode = launch_fast_path(F, sc, fr, threads, tune, lc.prio_tab != nullptr, lc.chain_next != nullptr,
                                              fr.k_begin > 0 && d_ray_counts != nullptr, lc.tile_cost != nullptr);
-      if (mode == kFastChains && !probe) return launch(std::integral_constant<decltype(&render_kernel<F, kFastChains>), &render_kernel<F, kFastChains>>());
-      if (mode == kFastQueue && !probe) return launch(std::integral_constant<decltype(&render_kernel<F, kFastQueue>), &render_kernel<F, kFastQueue>>());
-      if (mode == kFastQueue && probe) return launch(std::integral_constant<decltype(&probe_kernel<F, kFastQueue>), &probe_kernel<F, kFastQueue>>());
+      if (mode == kFastChains && !probe) return launch_block<render_kernel<F, kFastChains>>(at, rp, dp);
+      if (mode == kFastQueue && !probe) return launch_block<render_kernel<F, kFastQueue>>(at, rp, dp);
+      if (mode == kFastQueue && probe) return launch_block<probe_kernel<F, kFastQueue>>(at, rp, dp);
     }
-    if (probe) return launch(std::integral_constant<decltype(&probe_kernel<F>), &probe_kernel<F>>());
-    return launch(std::integral_constant<decltype(&render_kernel<F>), &render_kernel<F>>());
+    if (probe) return launch_block<probe_kernel<F>>(at, rp, dp);
+    return launch_block<render_kernel<F>>(at, rp, dp);
   });
 }
 
@@ -874,40 +852,10 @@ hipError_t launch_post(float *d_img, int64_t n, int spp, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ closest-hit queries (rtmi_intersect)
-// query_body.h around the render's closest_hit<F>.  Instantiated with F_TEX always (closest_hit tracks the winner's
-// u, v bitwise only then) and without F_DEFOCUS (no camera is involved): the render variants so mapped.
+// query_body.h around the render's closest_hit<F>, on the query variants (kQueryVariants).
 template <uint32_t F>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void query_kernel(QueryParams qp) {
   query_body<F>(qp);
-}
-
-#define RTMI_FOR_EACH_QUERY_VARIANT(X)               \
-  X(F_TEX)                                           \
-  X(F_TRIS | F_TEX)                                  \
-  X(F_SPHERE | F_TEX)                                \
-  X(F_TRIS | F_SPHERE | F_TEX)                       \
-  X(F_SPHERE | F_SGROUP | F_TEX)                     \
-  X(F_TRIS | F_SPHERE | F_SGROUP | F_TEX)            \
-  X(F_TRIS | F_BVH | F_TEX)                          \
-  X(F_ALL & ~F_DEFOCUS)
-
-uint32_t pick_query_variant(uint32_t features) {
-  features = (features & ~(uint32_t)F_DEFOCUS) | F_TEX;
-#define X(V) \
-  if ((features & ~(uint32_t)(V)) == 0) return (V);
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return F_ALL & ~F_DEFOCUS;
-}
-
-// with_variant over the query variants (rtmi_intersect, rtmi_occluded, rtmi_trace).
-template <class R, class Fn>
-static R with_query_variant(uint32_t variant, R otherwise, Fn &&f) {
-#define X(V) \
-  if (variant == (uint32_t)(V)) return f(std::integral_constant<uint32_t, (V)>());
-  RTMI_FOR_EACH_QUERY_VARIANT(X)
-#undef X
-  return otherwise;
 }
 
 constexpr int kQueryThreads = 256;
@@ -925,11 +873,8 @@ static LaunchCfg query_cfg(uint32_t variant, const SceneDev &sc, size_t *lds) {
 // kQueryThreads rays.
 template <auto Kernel>
 static hipError_t query_blocks(size_t lds, int n_cu, int64_t n, int *blocks) {
-  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
-  hipError_t e = dynamic_lds<Kernel>(lds);
-  if (e != hipSuccess) return e;
   int nb = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, kQueryThreads, lds);
+  const hipError_t e = kernel_occupancy<Kernel>(kQueryThreads, lds, &nb);
   if (e != hipSuccess) return e;
   if (nb < 1) nb = 1;
   const int64_t want = (n + kQueryThreads - 1) / kQueryThreads, cap = (int64_t)n_cu * nb;
@@ -940,7 +885,7 @@ static hipError_t query_blocks(size_t lds, int n_cu, int64_t n, int *blocks) {
 hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
                         const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
                         unsigned long long *d_check, hipStream_t stream) {
-  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     size_t lds = 0;
     QueryParams qp;
@@ -969,7 +914,7 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
                             float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream) {
-  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     size_t lds = 0;
     OcclusionParams p;
@@ -988,110 +933,73 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
   });
 }
 
-// ------------------------------------------------------------------ radiance of caller rays (rtmi_trace)
-// render_body.h in its caller-ray mode on the query variants (F_TEX always: the layer stack is one 32-bit word per level,
-// the material id or the sampled texel).  A persistent grid sized by occupancy; the lanes refill from the call's own
-// queue cursor (d_work[2]) as their paths end, a batch per wave per atomic.
+// ------------------------------------------------------------------ the entries that own their device state
+// rtmi_trace, rtmi_render_budget, rtmi_render_features: render_body.h in a mode of Kernel's on the query variants (F_TEX
+// always: the layer stack is one 32-bit word per level, the material id or the sampled texel -- or, without tex_layers,
+// the untextured id stack).  A persistent grid sized by occupancy; the lanes refill from the call's own queue cursor
+// (d_work[2]) as their items end, fetch_batch items per wave per atomic.  The argument block is written behind the
+// counter words of d_work.
+template <uint32_t F, auto Kernel>
+static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_layers, int fetch_batch, int n_cu,
+                              CallExtras ex, uint32_t *d_states, float *d_out, uint32_t *d_ray_counts,
+                              unsigned long long *d_work, hipStream_t stream) {
+  // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
+  // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
+  int threads = 0, per_cu = 0;
+  for (int t = 256; t >= 64; t /= 2) {
+    size_t lds_t = 0;
+    (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
+    int nb = 0;
+    (void)kernel_occupancy<Kernel>(t, lds_t, &nb);
+    if (t * nb > threads * per_cu) threads = t, per_cu = nb;
+  }
+  if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
+  size_t lds = 0;
+  CallParams cp;
+  cp.rp.sc = sc, cp.rp.fr = fr, cp.rp.lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
+  cp.rp.lc.lane_stride = 1, cp.rp.lc.fetch_batch = fetch_batch, cp.rp.lc.rate_scale = 1.f;
+  cp.rp.states = d_states, cp.rp.out = d_out, cp.rp.ray_counts = d_ray_counts, cp.rp.counters = d_work;
+  cp.ex = ex, cp.ex.tex_layers = tex_layers ? 1 : 0;
+  const int64_t want = (fr.items + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
+  return launch_block<Kernel>(LaunchAt{(int)(want < cap ? want : cap), threads, lds, stream}, cp,
+                              reinterpret_cast<CallParams *>(reinterpret_cast<char *>(d_work) + kCallParamsOffset));
+}
+
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
-  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     FrameDev fr{};
     fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
     fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
     fr.items = n;
-    // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
-    // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
-    int threads = 0, per_cu = 0;
-    for (int t = 256; t >= 64; t /= 2) {
-      size_t lds_t = 0;
-      (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
-      int nb = 0;
-      if (lds_t > 160 * 1024 || dynamic_lds<trace_kernel<F>>(lds_t) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<F>, t, lds_t) != hipSuccess)
-        nb = 0;
-      if (t * nb > threads * per_cu) threads = t, per_cu = nb;
-    }
-    if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
-    size_t lds = 0;
-    LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
-    lc.lane_stride = 1;
-    lc.fetch_batch = 64;  // (the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
-    lc.rate_scale = 1.f;
-    const hipError_t e = dynamic_lds<trace_kernel<F>>(lds);
-    if (e != hipSuccess) return e;
-    const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
-    const int blocks = (int)(want < cap ? want : cap);
-    TraceParams tp;
-    tp.rp.sc = sc, tp.rp.fr = fr, tp.rp.lc = lc;
-    tp.rp.states = d_states, tp.rp.out = d_radiance, tp.rp.ray_counts = d_ray_counts, tp.rp.counters = d_work;
-    tp.origins = d_o, tp.dirs = d_d, tp.tex_layers = tex_layers ? 1 : 0;
-    TraceParams *dp = reinterpret_cast<TraceParams *>(reinterpret_cast<char *>(d_work) + kTraceParamsOffset);
-    hipLaunchKernelGGL(trace_params_write_kernel, dim3(1), dim3(64), 0, stream, tp, dp);
-    hipLaunchKernelGGL(trace_kernel<F>, dim3(blocks), dim3(threads), lds, stream, (const TraceParams *)dp);
-    return hipGetLastError();
+    CallExtras ex{};
+    ex.rays = {d_o, d_d};
+    // (64: the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
+    return launch_call<F, trace_kernel<F>>(sc, fr, tex_layers, 64, n_cu, ex, d_states, d_radiance, d_ray_counts, d_work, stream);
   });
 }
 
-// ------------------------------------------------------------------ per-pixel sample budgets (rtmi_render_budget)
-// render_body.h in its budget mode on the query variants + F_DEFOCUS, launched as launch_trace launches: a persistent
-// grid sized by occupancy, the lanes refilling from the call's own queue cursor (d_work[2]) in image order.  A pixel is
-// a serial chain, so a call lasts at least as long as its largest budget x that pixel's rays per sample.
-// Kernel: budget_kernel<F>, or feature_kernel<F> (rtmi_render_features with a feature buffer: `feat`).
-template <uint32_t F, auto Kernel>
-static hipError_t launch_budget_as(const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
-                                   const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq,
-                                   uint32_t *d_samples, uint32_t *d_ray_counts, const FeatureBufs &feat,
-                                   unsigned long long *d_work, hipStream_t stream) {
-  {
-    FrameDev fr = frame;
-    fr.post = 0, fr.k_begin = 0, fr.k_end = fr.spp;
-    const int64_t n = fr.items;
-    int threads = 0, per_cu = 0;  // (the workgroup size that keeps the most lanes resident: launch_trace)
-    for (int t = 256; t >= 64; t /= 2) {
-      size_t lds_t = 0;
-      (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
-      int nb = 0;
-      if (lds_t > 160 * 1024 || dynamic_lds<Kernel>(lds_t) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, t, lds_t) != hipSuccess)
-        nb = 0;
-      if (t * nb > threads * per_cu) threads = t, per_cu = nb;
-    }
-    if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
-    size_t lds = 0;
-    LaunchCfg lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
-    lc.lane_stride = 1;
-    // items per atomic: a pixel of a few samples is as short as a ray of rtmi_trace; longer ones as launch_render's image order
-    const int per_atomic = fr.spp < 32 ? 256 / (fr.spp > 0 ? fr.spp : 1) : 64 / fr.spp;
-    lc.fetch_batch = per_atomic < 1 ? 1 : per_atomic > 64 ? 64 : per_atomic;
-    lc.rate_scale = 1.f;
-    const hipError_t e = dynamic_lds<Kernel>(lds);
-    if (e != hipSuccess) return e;
-    const int64_t want = (n + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
-    const int blocks = (int)(want < cap ? want : cap);
-    BudgetParams bp;
-    bp.rp.sc = sc, bp.rp.fr = fr, bp.rp.lc = lc;
-    bp.rp.states = d_states, bp.rp.out = d_sum, bp.rp.ray_counts = d_ray_counts, bp.rp.counters = d_work;
-    bp.budget = d_budget, bp.sq = d_sq, bp.samples = d_samples, bp.tex_layers = tex_layers ? 1 : 0;
-    bp.feat = feat;
-    BudgetParams *dp = reinterpret_cast<BudgetParams *>(reinterpret_cast<char *>(d_work) + kBudgetParamsOffset);
-    hipLaunchKernelGGL(budget_params_write_kernel, dim3(1), dim3(64), 0, stream, bp, dp);
-    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(threads), lds, stream, (const BudgetParams *)dp);
-    return hipGetLastError();
-  }
-}
+// The budget mode runs on the query variants + F_DEFOCUS, its items in image order.  A pixel is a serial chain, so a call
+// lasts at least as long as its largest budget x that pixel's rays per sample.
 hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &frame,
                          const uint32_t *d_budget, uint32_t *d_states, float *d_sum, float *d_sq, uint32_t *d_samples,
                          uint32_t *d_ray_counts, const FeatureBufs *feat, unsigned long long *d_work, hipStream_t stream) {
   const bool features = feat && (feat->albedo || feat->normal || feat->depth || feat->coverage);
-  return with_query_variant(variant, hipErrorInvalidValue, [&](auto v) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value | F_DEFOCUS;
-    if (features)
-      return launch_budget_as<F, feature_kernel<F>>(sc, tex_layers, n_cu, frame, d_budget, d_states, d_sum, d_sq, d_samples,
-                                                    d_ray_counts, *feat, d_work, stream);
-    return launch_budget_as<F, budget_kernel<F>>(sc, tex_layers, n_cu, frame, d_budget, d_states, d_sum, d_sq, d_samples,
-                                                 d_ray_counts, FeatureBufs{}, d_work, stream);
+    FrameDev fr = frame;
+    fr.post = 0, fr.k_begin = 0, fr.k_end = fr.spp;
+    // items per atomic: a pixel of a few samples is as short as a ray of rtmi_trace; longer ones as launch_render's image order
+    const int batch = image_order_batch(fr.spp, 64);
+    CallExtras ex{};
+    ex.px = {d_budget, d_sq, d_samples};
+    if (features) {
+      ex.feat = *feat;
+      return launch_call<F, feature_kernel<F>>(sc, fr, tex_layers, batch, n_cu, ex, d_states, d_sum, d_ray_counts, d_work, stream);
+    }
+    return launch_call<F, budget_kernel<F>>(sc, fr, tex_layers, batch, n_cu, ex, d_states, d_sum, d_ray_counts, d_work, stream);
   });
 }
 

@@ -1,11 +1,13 @@
 // The persistent per-pixel trace loop.  Included by kernels.hip inside namespace rtmi, after closest_hit.h
 // (not a stand-alone header).
 //
-// render_body<F, RAYS, BUDGET>: neither is the render (render_kernel, probe_kernel); RAYS is rtmi_trace
+// render_body<F, RAYS, BUDGET, FEATURES, M>: no mode set is the render (render_kernel, probe_kernel); RAYS is rtmi_trace
 // (trace_kernel): work item q is the caller's ray q instead of a pixel, traced once from the ray it is given -- no
 // camera, no jitter -- with the same bounce, shading, layer stack and fold, one copy of them for both.  BUDGET is
 // rtmi_render_budget (budget_kernel): a work item is a pixel as in the render, but how many samples it gets is its own
-// word of a budget map, and the sums, second moments, sample and ray counts it finds in the buffers are carried on.
+// word of a budget map, and the sums, second moments, sample and ray counts it finds in the buffers are carried on;
+// with FEATURES (rtmi_render_features, feature_kernel) it also sums what each sample's primary hit looks like.
+// What each mode is told: RenderParams and CallExtras below.
 #pragma once
 
 // ================================================================== trace kernel
@@ -130,19 +132,66 @@ __device__ __forceinline__ bool finite3(V3 v) {
   return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
 }
 
-// RAYS (rtmi_trace): fr.items rays, fr.spp = 1, fr.k_begin = 0, fr.k_end = 1, fr.post = 0; ray_o / ray_d float[items][3];
-// counters is the call's d_work: [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's cursor (a
-// render's counters hold the cursor in [0] and the abandoned searches in [2]).  The list queue serves every variant.
-// tex_layers (RAYS, BUDGET): false keeps the untextured id stack in an F_TEX variant -- for scenes without image textures,
-// whose layers are material ids (launch_trace: a quarter or less of the 32-bit layer words' LDS).
-// BUDGET (rtmi_render_budget): the frame's items, fr.k_begin = 0, fr.post = 0, fr.spp = fr.k_end = the cap on one call's
-// samples per pixel; budget uint32[items]; out (sums), sq (second moments, nullable), samples, ray_counts (nullable) all
-// ACCUMULATE; counters is the call's d_work, laid out and served as for RAYS (the list queue, every variant; tex_layers).
-// FEATURES (rtmi_render_features; BUDGET only): at the primary hit of every sample -- depth == 0, the record of the first
-// closest-hit query Trace makes -- the lane adds the hit's albedo, normal, depth and coverage into its item's own words of
-// the non-null buffers of *feat, one binary32 addition per channel, in sample order.  A read-modify-write in global
-// memory, not running sums in registers: the lane owns the item, so these are plain vector loads and stores, and nothing
-// more is live across closest_hit and the fold than in the budget mode.  No RNG draw is made or skipped.
+// Everything a kernel around render_body is told lives in ONE block of device memory (written by params_write_kernel,
+// stream-ordered, just before the launch) and the kernel's only argument is its address.  By-value kernel arguments are
+// all loaded in the kernel's first block and stay live from there: with ~150 dwords of them the list kernel parked
+// 76-114 scalars in spill lanes (v_writelane / v_readlane at every use), the mesh kernel 285.  Read through the constant
+// address space (in_constant) the fields arrive by scalar loads where they are used -- the hot loop's stay in SGPRs, the
+// rest never occupy one, and a field that a mode does not read is never loaded.
+struct RenderParams {
+  SceneDev sc;
+  FrameDev fr;  // RAYS: items rays, spp = 1, k_begin = 0, k_end = 1, post = 0.  BUDGET: the frame's items, k_begin = 0,
+                // post = 0, spp = k_end = the cap on one call's samples per pixel
+  LaunchCfg lc;
+  uint32_t *states;
+  float *out;                   // RAYS: a radiance per ray.  BUDGET: the sums -- they ACCUMULATE
+  uint32_t *ray_counts;         // nullable.  BUDGET: accumulates
+  unsigned long long *counters; // the render's counters ([0] the queue's cursor, [2] abandoned mesh searches ...), or --
+                                // RAYS, BUDGET -- the call's d_work: [0] abandoned mesh searches, [1] closest-hit
+                                // queries, [2] the queue's cursor.  There the list queue serves every variant.
+};
+// What the modes whose call owns its device state are told besides (CallParams: the block in the call's d_work).
+struct RayBufs {
+  const float *origins, *dirs;  // float[items][3]
+};
+struct BudgetBufs {
+  const uint32_t *budget;  // uint32[items]
+  float *sq;               // the second moments (nullable); accumulates
+  uint32_t *samples;       // samples per item; accumulates
+};
+struct CallExtras {
+  union {  // one work-item source at a time; either way right behind RenderParams' pointers, which they are loaded with
+    RayBufs rays;   // RAYS
+    BudgetBufs px;  // BUDGET
+  };
+  // RAYS, BUDGET: 0 keeps the untextured id stack in an F_TEX variant -- for scenes without image textures, whose layers
+  // are material ids (a quarter or less of the 32-bit layer words' LDS)
+  int32_t tex_layers;
+  // FEATURES (BUDGET only): at the primary hit of every sample -- depth == 0, the record of the first closest-hit query
+  // Trace makes -- the lane adds the hit's albedo, normal, depth and coverage into its item's own words of the non-null
+  // buffers, one binary32 addition per channel, in sample order.  A read-modify-write in global memory, not running sums
+  // in registers: the lane owns the item, so these are plain vector loads and stores, and nothing more is live across
+  // closest_hit and the fold than in the budget mode.  No RNG draw is made or skipped.
+  FeatureBufs feat;
+};
+struct CallParams {
+  RenderParams rp;
+  CallExtras ex;
+};
+// The block at p, read the scalar way.  (global -> constant address space -> generic: the compiler's address-space
+// inference turns every access through the result back into a constant-address-space load, i.e. a scalar load that
+// nothing in the kernel can clobber)
+template <class P>
+__device__ __forceinline__ const P &in_constant(const P *p) {
+  return *(const P *)(const RT_CONSTANT P *)(uintptr_t)p;
+}
+
+// The loop on the block's fields: the kernels hand each over themselves (kernels.hip), the fields of other modes left
+// out.  The buffers are parameters of their own because only a parameter can say that nothing else points into what it
+// points to, and the compiler uses it: with the buffers as locals loaded from the block 44 of the 45 kernels compile to
+// other instructions.  And they are parameters of THIS function, called by the kernels directly: a function in between
+// that spreads the block is one more round of the optimiser over the inlined loop, and 39 of the 45 come out different
+// (NOTES.md 11).
 // M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
 // the front end folds: with M == 0 every line below is the run-time test it was.
 template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0>

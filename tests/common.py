@@ -1,4 +1,9 @@
-"""Shared helpers: build one named scene on either implementation and render it."""
+"""Shared helpers: build one named scene on either implementation and render it; read a built library's kernel metadata."""
+import os
+import re
+import subprocess
+import tempfile
+
 import numpy as np
 
 from rtmi import scenes
@@ -71,3 +76,18 @@ def rel_l2(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.sqrt(((a - b) ** 2).sum()) / max(np.sqrt((b ** 2).sum()), 1e-30))
+
+
+def kernel_notes(lib):
+    """Kernel name -> its block of metadata notes (llvm-readelf --notes) in the gfx950 code object embedded in the
+    shared library at path `lib`."""
+    llvm = "/opt/rocm/lib/llvm/bin"
+    assert os.path.exists(llvm + "/llvm-readelf"), "llvm-readelf reads the code object's metadata"
+    assert os.path.exists(lib), lib + " missing: __graft_entry__.build() builds it"
+    with tempfile.TemporaryDirectory() as tmp:
+        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
+        subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
+        subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
+        notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
+    return {re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]}

@@ -11,10 +11,10 @@ import re
 import numpy as np
 import pytest
 
+import common
 import rtmi
-from test_trace_host import _kernels
 
-QUERY_VARIANTS = 8  # kernels.hip: RTMI_FOR_EACH_QUERY_VARIANT
+QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
 F_DEFOCUS = 32      # scene_dev.h
 OK, ERR_INVALID, ERR_DEPTH = 0, -1, -5  # include/rtmi.h
 LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
@@ -189,9 +189,8 @@ def test_budget_kernels_one_per_variant_without_static_lds():
     """The budget kernels address the layer stack at byte offsets of the DYNAMIC LDS array, as every mode of the trace
     loop does: right only while they declare no static LDS (group_segment_fixed_size == 0), in both builds.  Eight
     kernels -- the query variants, each with F_DEFOCUS set -- not sixteen."""
-    assert os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), "llvm-readelf reads the code object's metadata"
     for lib in LIBS:
-        ks = {n: blk for n, blk in _kernels(lib).items() if "budget_kernel" in n}
+        ks = {n: blk for n, blk in common.kernel_notes(lib).items() if "budget_kernel" in n}
         assert len(ks) == QUERY_VARIANTS, (lib, sorted(ks))
         for name, blk in ks.items():
             assert not any(k in name for k in ("render_kernel", "probe_kernel", "trace_kernel", "query_kernel")), name

@@ -10,6 +10,7 @@ import tempfile
 
 import pytest
 
+import common
 import rtmi
 from test_budget_host import LIBS
 
@@ -124,20 +125,10 @@ def test_fast_kernels_are_in_both_builds_at_six_waves_per_simd():
     """render_kernel<F_TRIS, kFastChains = 255>, <F_TRIS, kFastQueue = 383> and the first pass's probe_kernel<F_TRIS, 383>:
     present, no static LDS (render_body.h addresses LDS by byte offsets), and -- the product build -- at most 80 VGPRs,
     the six-waves-per-SIMD step the list kernel is held at."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(llvm + "/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
     want = ("render_kernelILj2ELj255E", "render_kernelILj2ELj383E", "probe_kernelILj2ELj383E")
     for lib in LIBS:
-        with tempfile.TemporaryDirectory() as tmp:
-            fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
-            subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-            subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-            notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
         seen = set()
-        for blk in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        for name, blk in common.kernel_notes(lib).items():
             for w in want:
                 if w in name:
                     seen.add(w)

@@ -9,9 +9,9 @@ import tempfile
 
 import numpy as np
 
+import common
 import rtmi
 from test_budget_host import DUMMY, ERR_DEPTH, ERR_INVALID, F_DEFOCUS, LIBS, QUERY_VARIANTS, _frame
-from test_trace_host import _kernels
 
 ENTRIES = ("rtmi_render_features", "rtmi_resolve_features")
 F32 = np.float32
@@ -151,7 +151,7 @@ def test_feature_kernels_one_per_variant_without_static_lds():
     both builds; and none runs at lower occupancy than its twin (the same VGPR step of the allocation table)."""
     waves = lambda v: next(w for lim, w in ((64, 8), (72, 7), (80, 6), (96, 5), (128, 4), (168, 3), (256, 2), (512, 1)) if v <= lim)
     for lib in LIBS:
-        ks = _kernels(lib)
+        ks = common.kernel_notes(lib)
         fk = {n: blk for n, blk in ks.items() if "feature_kernel" in n}
         assert len(fk) == QUERY_VARIANTS, (lib, sorted(fk))
         for name, blk in fk.items():

@@ -285,23 +285,9 @@ def test_trace_kernels_declare_no_static_lds():
     (group_segment_fixed_size == 0 in the code object's metadata).  Checked on the product AND on the diagnostic
     margin-check build (a __shared__ added under one of its macros would make the fold read wrong ids without a fault);
     the launcher asks the same of whatever build is loaded (kernels.hip: hipFuncGetAttributes, once per variant)."""
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(llvm + "/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    libs = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
-    assert os.path.exists(libs[1]), "librtmi_check1.so missing: __graft_entry__.build() builds it"
-    for lib in libs:
-        with tempfile.TemporaryDirectory() as tmp:
-            fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
-            subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-            subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-            notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
+    for lib in (rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")):
         seen = 0
-        for blk in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        for name, blk in common.kernel_notes(lib).items():
             if "render_kernel" in name or "probe_kernel" in name:
                 seen += 1
                 assert re.search(r"\.group_segment_fixed_size:\s+0\b", blk), (lib, name)

@@ -7,8 +7,9 @@ import subprocess
 
 import pytest
 
+import common
 import rtmi
-from test_query_host import QUERY_VARIANTS, _kernel_notes
+from test_query_host import QUERY_VARIANTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib")
@@ -115,12 +116,9 @@ def test_python_occluded_refuses_before_gpu_work():
 def test_occlusion_kernels_one_per_variant_without_static_lds():
     """occlusion_body.h hands closest_hit LDS regions by byte offset of the dynamic array: every occlusion kernel of the
     product and of the margin-check build must declare no static LDS, and there is one per query variant."""
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
     for lib in (rtmi.LIB_PATH, CHECK_LIB):
         names = set()
-        for blk in _kernel_notes(lib).split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        for name, blk in common.kernel_notes(lib).items():
             if "occlusion_kernel" in name:
                 assert not any(k in name for k in ("query_kernel", "render_kernel", "probe_kernel")), name
                 names.add(name)

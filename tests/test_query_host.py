@@ -4,15 +4,15 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import pytest
 
+import common
 import rtmi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib")
-QUERY_VARIANTS = 8  # kernels.hip: RTMI_FOR_EACH_QUERY_VARIANT
+QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
 
 
 def test_intersect_is_exported():
@@ -105,28 +105,13 @@ def test_python_intersect_refuses_before_gpu_work():
             b.intersect(g, g)
 
 
-def _kernel_notes(lib):
-    llvm = "/opt/rocm/lib/llvm/bin"
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
-        subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-        subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-        return subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
-
-
 def test_query_kernels_declare_no_static_lds():
     """query_body.h hands closest_hit LDS regions by byte offset of the dynamic array, as render_body.h does: every
     query kernel of the product and of the margin-check build must declare no static LDS, and there is one per query
     variant."""
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    libs = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
-    assert os.path.exists(libs[1]), "librtmi_check1.so missing: __graft_entry__.build() builds it"
-    for lib in libs:
+    for lib in (rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")):
         names = set()
-        for blk in _kernel_notes(lib).split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        for name, blk in common.kernel_notes(lib).items():
             if "query_kernel" in name:
                 names.add(name)
                 assert re.search(r"\.group_segment_fixed_size:\s+0\b", blk), (lib, name)

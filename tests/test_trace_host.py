@@ -3,14 +3,13 @@ binding's refusals, and the trace kernels in both builds of the library.  No GPU
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
+import common
 import rtmi
 
-QUERY_VARIANTS = 8  # kernels.hip: RTMI_FOR_EACH_QUERY_VARIANT
+QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_DEPTH = 0, -1, -2, -5  # include/rtmi.h
 LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
 
@@ -65,25 +64,11 @@ def test_python_trace_refusals():
         b.trace(o, o, st, 8)  # CPU tensors: there is no CPU path
 
 
-def _kernels(lib):
-    llvm = "/opt/rocm/lib/llvm/bin"
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
-        subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-        subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
-    return {re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]}
-
-
 def test_trace_kernels_declare_no_static_lds():
     """The trace kernels fold the layer stack at LDS addresses formed from byte offsets of the DYNAMIC LDS array, as
     the render does: right only while they declare no static LDS (group_segment_fixed_size == 0), in both builds."""
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    assert os.path.exists(LIBS[1]), "librtmi_check1.so missing: __graft_entry__.build() builds it"
     for lib in LIBS:
-        ks = {n: blk for n, blk in _kernels(lib).items() if "trace_kernel" in n}
+        ks = {n: blk for n, blk in common.kernel_notes(lib).items() if "trace_kernel" in n}
         assert len(ks) == QUERY_VARIANTS, (lib, sorted(ks))
         for name, blk in ks.items():
             assert re.search(r"\.group_segment_fixed_size:\s+0\b", blk), (lib, name)
