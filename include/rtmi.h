@@ -586,9 +586,10 @@ int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const 
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /
  * RTMI_LANE_STRIDE / RTMI_PROMOTE (promote_after) / RTMI_COST_PROBE / RTMI_FIRST_PASS / RTMI_FAST_PATH (0: the general kernel
  * always, what fast_path = -1 asks of one call) environment variables override the built-in defaults
- * of those fields and are read once, when the library is first used.  (RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST, 1..64: the
- * largest batch a wave of a list frame draws from the work queue per atomic in longest-first order / in a first pass of a
- * few samples -- measurement knobs without an option field; defaults 16 / 64.) */
+ * of those fields and are read once, when the library is first used.  (So are the measurement knobs without an option
+ * field: RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST, 1..64: the largest batch a wave of a list frame draws from the work
+ * queue per atomic in longest-first order / in a first pass of a few samples, defaults 16 / 64; RTMI_FIRST_PRIO, 0: a
+ * first pass of the frame's own samples never has wave priorities, default 1: from 32 samples on.) */
 int rtmi_set_launch(int blocks_per_cu, int threads_per_block);
 int rtmi_set_schedule(int mode);
 

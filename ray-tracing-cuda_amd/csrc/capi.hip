@@ -70,6 +70,10 @@ static RenderTuning default_tuning() {
     g_tune.prio_every = env_int("RTMI_PRIO", 16);  // wave priorities: update interval in iterations (0: off)
     if (g_tune.prio_every < 0 || (g_tune.prio_every & (g_tune.prio_every - 1)) != 0) g_tune.prio_every = 16;
     g_tune.fast_path = env_int("RTMI_FAST_PATH", 1) != 0;  // 0: every launch uses the general kernel (kernels.h: fast_path_mode)
+    g_tune.head_classes = env_int("RTMI_HEAD_CLASSES", 1) != 0;
+    g_tune.first_prio = env_int("RTMI_FIRST_PRIO", 1) != 0;
+    g_tune.fetch_batch = std::clamp(env_int("RTMI_FETCH_BATCH", 16), 1, 64);
+    g_tune.fetch_batch_first = std::clamp(env_int("RTMI_FETCH_BATCH_FIRST", 64), 1, 64);
   });
   std::lock_guard<std::mutex> lk(g_tune_mu);
   return g_tune;
@@ -503,12 +507,17 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   return RTMI_OK;
 }
 
+// *tmp = a flattened copy of the scene, so that an uncommitted one can be inspected.
+static int flattened(const rtmi_scene *sp, Scene *tmp) {
+  *tmp = *S(sp);
+  tmp->dev_allocs.clear();
+  const std::string err = tmp->flatten();
+  return err.empty() ? RTMI_OK : fail(RTMI_ERR_INVALID, err);
+}
 int rtmi_scene_stats(const rtmi_scene *sp, int64_t out[8]) {
   if (!sp || !out) return fail(RTMI_ERR_INVALID, "null argument");
-  Scene tmp = *S(sp);  // flatten a copy so an uncommitted scene can be inspected
-  tmp.dev_allocs.clear();
-  std::string err = tmp.flatten();
-  if (!err.empty()) return fail(RTMI_ERR_INVALID, err);
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
   out[0] = (int64_t)tmp.list_counts[0];
   out[1] = (int64_t)tmp.n_spheres;
   out[2] = (int64_t)tmp.n_pgrams;
@@ -522,19 +531,15 @@ int rtmi_scene_stats(const rtmi_scene *sp, int64_t out[8]) {
 
 int64_t rtmi_scene_sliver_faces(const rtmi_scene *sp) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  Scene tmp = *S(sp);
-  tmp.dev_allocs.clear();
-  std::string err = tmp.flatten();
-  if (!err.empty()) return fail(RTMI_ERR_INVALID, err);
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
   return tmp.sliver_faces;
 }
 
 int64_t rtmi_scene_bytes_per_ray(const rtmi_scene *sp) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  Scene tmp = *S(sp);
-  tmp.dev_allocs.clear();
-  std::string err = tmp.flatten();
-  if (!err.empty()) return fail(RTMI_ERR_INVALID, err);
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
   return tmp.bytes_per_ray;
 }
 
@@ -631,7 +636,7 @@ int rtmi_rng_get_state(const rtmi_frame *f, const void *d_states, int64_t q, uin
 }
 
 // ------------------------------------------------------------------ render
-// Per-call scratch of a frame, the one description of it (rtmi_render_scratch_bytes, rtmi_render_ex).  The counters come
+// Per-call scratch of a frame, the one description of it (rtmi_render_scratch_bytes, run_plan).  The counters come
 // first so that rtmi_render_status can find them from the scratch pointer alone; then what the scheduler's probe pass
 // leaves for the real pass, rounded up to 256 bytes; then the wave-priority table and the kernel-argument blocks.
 static constexpr size_t kCounterBytes = RTMI_COUNTER_WORDS * sizeof(unsigned long long);
@@ -692,7 +697,7 @@ static int resolve_opts(const rtmi_render_opts *opts, RenderTuning *tune, void *
   if (opts->schedule >= 0) tune->schedule = opts->schedule;
   if (opts->blocks_per_cu > 0) tune->blocks_per_cu = opts->blocks_per_cu;
   if (opts->threads_per_block > 0) tune->threads = opts->threads_per_block;
-  if (opts->sparse_stride > 0) tune->sparse_stride = opts->sparse_stride;
+  if (opts->sparse_stride > 0) tune->sparse_stride = opts->sparse_stride, tune->head_classes = 0;  // (a named stride is for outlier tiles)
   if (opts->exclusive >= 0) tune->exclusive = opts->exclusive;
   if (opts->outlier_x10 > 0) tune->outlier_x10 = opts->outlier_x10;
   if (opts->probe_spp > 0) tune->probe_spp = opts->probe_spp;
@@ -715,7 +720,15 @@ static int resolve_opts(const rtmi_render_opts *opts, RenderTuning *tune, void *
 struct LaunchShape {
   uint32_t variant;
   int threads, per_cu, blocks, n_cu, lane_stride;
+  FastPathFacts fast;  // what the fast kernels ask of scene and frame (fast_mode adds a launch's own facts)
 };
+// The fast-path mode word of one launch (kernels.h: fast_path_mode; 0: the general kernel).  priorities, chains,
+// tile_cost: the launch has a priority table, walks planned chains, has the probe's tile costs; resumed: it resumes a
+// first pass.
+static uint32_t fast_mode(FastPathFacts f, int lane_stride, bool priorities, bool chains, bool resumed, bool tile_cost) {
+  f.lane_stride = lane_stride, f.priorities = priorities, f.chains = chains, f.resumed = resumed, f.tile_cost = tile_cost;
+  return fast_path_mode(f);
+}
 static constexpr int kMaxLaneStride = 16;
 static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &tune, LaunchShape *out) {
   int n_cu = 0;
@@ -732,9 +745,11 @@ static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &t
       if (lanes > best) best = lanes, threads = t;
     }
   }
-  // (asked of the kernel that will really be launched: the general one, or whichever of the fast ones it may be)
+  // (asked of the kernel that will really be launched: the general one, or whichever of the fast ones it may be -- without
+  // the facts of scene and frame no launch of this frame uses a fast kernel)
+  out->fast = fast_path_facts(variant, s->dev, d, threads, tune.fast_path);
   int per_cu = tune.blocks_per_cu > 0 ? tune.blocks_per_cu
-                                      : render_occupancy(variant, s->dev, d, threads, fast_path_scene(variant, s->dev, d, threads, tune.fast_path));
+                                      : render_occupancy(variant, s->dev, d, threads, fast_mode(out->fast, 1, true, false, false, false) != 0u);
   if (per_cu <= 0) per_cu = 1;
   int64_t want = (d.items + threads - 1) / threads;
   int64_t cap = (int64_t)n_cu * per_cu;
@@ -756,22 +771,49 @@ static int launch_shape(const Scene *s, const FrameDev &d, const RenderTuning &t
   return RTMI_OK;
 }
 
-// How a frame will be rendered: everything rtmi_render_ex decides before it launches anything (rtmi_render_mode reports
-// it).  `tune` is the call's tuning, already carrying the launch shape's lane stride; prio_every may be lowered here.
-struct RenderMode {
-  bool scheduled, resume, may_plan, prio;
-  int probe_spp;
+// How a frame will be rendered: everything that is decided, from host values alone, before anything is launched.
+// rtmi_render_ex executes it (run_plan); rtmi_render_launch_shape and rtmi_render_mode report it.
+struct RenderPlan {
+  const Scene *s;                    // the call, as render_prologue resolves it: scene, frame, the caller's scratch (or null)
+  FrameDev d;                        //   and the tuning; plan_render then gives the tuning the shape's lane stride and lowers
+  void *user_scratch;                //   its prio_every for a short frame
+  size_t user_scratch_bytes;
+  RenderTuning tune;
+  LaunchShape ls;
+  int waves, probe_spp;              // waves of the grid; samples per pixel of the first pass
+  bool scheduled, resume, prio;      // a first pass orders the rest; it is the frame's own first samples; wave priorities
+  bool chains, by_cost, first_prio;  // list tiles run as planned chains; mesh frames: the probe books its searches' cost; the
+                                     // first pass has wave priorities too
+  int plan_simds, plan_rounds;       // chains: on this many SIMDs, this many waves each
+  uint32_t sparse_cap;               // work items the grid holds at one pixel per tune.sparse_stride lanes (a multiple of 64)
+  bool scratch;                      // the call needs scratch memory at all
+  FrameDev first, finish;            // the first pass; the launch that finishes the frame: all of it, or what a first pass left
+  uint32_t first_fast, finish_fast;  // their fast-path mode words
 };
-static RenderMode decide_mode(const FrameDev &d, uint32_t variant, const LaunchShape &ls, RenderTuning &tune) {
-  const int blocks = ls.blocks, threads = ls.threads;
-  const int64_t resident = (int64_t)blocks * threads;
+// What the three render entries resolve first, in this order: options, committed, frame.
+static int render_prologue(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, RenderPlan *p) {
+  if (int rc = resolve_opts(opts, &p->tune, &p->user_scratch, &p->user_scratch_bytes)) return rc;
+  p->s = S(sp);
+  if (!p->s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if (!make_frame(f, &p->d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
+  return RTMI_OK;
+}
+static int plan_render(RenderPlan *p) {
+  const FrameDev &d = p->d;
+  LaunchShape &ls = p->ls;
+  RenderTuning &tune = p->tune;
+  if (int rc = launch_shape(p->s, d, tune, &ls)) return rc;
+  tune.lane_stride = ls.lane_stride;
+  const uint32_t variant = ls.variant;
+  const int64_t resident = (int64_t)ls.blocks * ls.threads;
+  p->waves = ls.blocks * (ls.threads / 64);
   // When is a list frame planned?  The plan wins where the queue cannot even things out (few tiles per wave) AND its
   // estimates are good enough (long pixels: many samples).  Measured, planned against queued, cornell depth 50: 1.33
   // tiles per wave (a 2048^2 frame over eight GPUs): 128 spp 20.9 / 21.0 ms, 512 spp 66 / 77, 4096 spp 480 / 590; 2.67
   // tiles per wave (1024^2): 128 spp 38.3 / 35.1, 256 spp 66.8 / 64.3, 512 spp 122.4 / 123.5, 1024 spp 237 / 241; 5.3
   // (half a 2048^2 x 4096 frame) 1763 / 1787; 6.4 (a C5 shard, 8192 spp) 2853 / 2917; 10.7: the same.  Spheres 1024^2 x
   // 64 spp, 3.2 tiles per wave: 21.3-22.6 / 20.4.
-  const int64_t plan_tiles = d.local_tiles, plan_waves = (int64_t)blocks * (threads / 64);
+  const int64_t plan_tiles = d.local_tiles, plan_waves = p->waves;
   const bool plan_pays = (2 * plan_tiles <= 3 * plan_waves && d.spp >= 128) || (plan_tiles <= 3 * plan_waves && d.spp >= 512) ||
                          (plan_tiles <= 8 * plan_waves && d.spp >= 2048);
   const bool may_plan = tune.plan && tune.prio_every > 0 && d.spp >= 64 && !(variant & F_BVH) && ls.lane_stride == 1 &&
@@ -780,7 +822,7 @@ static RenderMode decide_mode(const FrameDev &d, uint32_t variant, const LaunchS
   // order only has to be roughly longest-first: 2 / 4 / 8 / 16 spp gave 606 / 620 / 609 / 614 ms on a round-3 C4 shard),
   // 1 / 256 of the frame's samples, at most 16, for a plan, which is only as balanced as its estimates (C4 shard 2 / 8 /
   // 16 / 32 / 64: 495 / 486 / 484 / 482 / 484 ms, probe included).  rtmi_render_opts.probe_spp overrides either way.
-  int probe_spp = tune.probe_spp > 0 ? tune.probe_spp : 2;
+  int &probe_spp = p->probe_spp = tune.probe_spp > 0 ? tune.probe_spp : 2;
   if (tune.probe_spp <= 0 && may_plan) probe_spp = d.spp / 256 < 2 ? 2 : d.spp / 256 > 16 ? 16 : d.spp / 256;
   const bool many_tiles = (int64_t)d.local_tiles * 64 > resident;
   // The probe is the frame's own first samples (tune.first_pass): samples [0, s1) of every pixel are rendered into the
@@ -801,32 +843,40 @@ static RenderMode decide_mode(const FrameDev &d, uint32_t variant, const LaunchS
   // outlier pixels -- the reference's own bunny program, 1280 x 720 x 20 spp: 7.3 -> 4.9 ms -- from 8 samples per pixel
   // on; list frames from 32: at the reference's defaults, 100-200 spp, scheduled and unscheduled differ by +-4 %)
   const int min_spp = two_pass ? ((variant & F_BVH) ? 8 : 32) : 32 * probe_spp;
-  const bool scheduled = tune.schedule == 2 || (tune.schedule == 1 && many_tiles && d.spp >= min_spp && d.spp >= 2 * probe_spp);
+  p->scheduled = tune.schedule == 2 || (tune.schedule == 1 && many_tiles && d.spp >= min_spp && d.spp >= 2 * probe_spp);
   // wave priorities (render_body.h: wave_priority_update) pay for themselves when a wave lives for many updates
   // ... from eight samples per pixel on; a short frame's waves live for tens of iterations, so they look every four
   // (C1, spheres 256^2 x 16 spp: 2.07 -> 1.86 ms; every 16: 1.89, every 2: 1.94, every iteration: 2.07)
-  const bool prio = tune.prio_every > 0 && d.spp >= 8;
-  if (prio && d.spp < 64 && tune.prio_every > 4) tune.prio_every = 4;
-  RenderMode m;
-  m.scheduled = scheduled, m.may_plan = may_plan, m.prio = prio, m.probe_spp = probe_spp;
-  m.resume = scheduled && two_pass && probe_spp < d.spp;
-  return m;
+  p->prio = tune.prio_every > 0 && d.spp >= 8;
+  if (p->prio && d.spp < 64 && tune.prio_every > 4) tune.prio_every = 4;
+  p->resume = p->scheduled && two_pass && probe_spp < d.spp;
+  // list frames: planned chains instead of the queue (kernels.h: launch_chain_plan), one per wave of the grid
+  p->plan_simds = ls.n_cu * 4 < p->waves ? ls.n_cu * 4 : p->waves;  // (four SIMDs per compute unit)
+  p->plan_rounds = (p->waves + p->plan_simds - 1) / p->plan_simds;
+  p->chains = p->scheduled && may_plan && p->prio && p->plan_simds * p->plan_rounds <= kMaxChains;
+  // mesh frames (binary32 t): the probe also books the lane-steps of its mesh searches on the pixels they serve
+  p->by_cost = tune.cost_probe && (variant & F_BVH) && !(variant & F_SPHERE);
+  // (a first pass of the frame's own samples is a frame of s1 samples per pixel: from 32 on it has wave priorities too)
+  p->first_prio = p->prio && p->resume && probe_spp >= 32 && tune.first_prio;
+  p->sparse_cap = (uint32_t)((resident / tune.sparse_stride) / 64 * 64);
+  p->scratch = p->scheduled || p->prio;
+  // first pass: the frame's own samples [0, probe_spp) into the caller's buffers, or a discarded probe on copies
+  p->first = p->finish = d;
+  p->first.k_end = probe_spp;
+  if (p->resume) p->finish.k_begin = probe_spp;
+  else p->first.spp = probe_spp;
+  // the kernels compiled for the common list frame, where a launch is one (a first pass never walks chains)
+  p->first_fast = fast_mode(ls.fast, ls.lane_stride, p->first_prio, false, false, false);
+  p->finish_fast = fast_mode(ls.fast, ls.lane_stride, p->prio, p->chains, p->resume, p->scheduled);
+  return RTMI_OK;
 }
 
 int rtmi_render_launch_shape(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t out[4]) {
   if (!sp || !out) return fail(RTMI_ERR_INVALID, "null argument");
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  FrameDev d;
-  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
-  RenderTuning tune;
-  void *scratch;
-  size_t scratch_bytes;
-  int rc = resolve_opts(opts, &tune, &scratch, &scratch_bytes);
-  if (rc) return rc;
-  LaunchShape ls;
-  if ((rc = launch_shape(s, d, tune, &ls))) return rc;
-  out[0] = ls.blocks, out[1] = ls.threads, out[2] = ls.per_cu, out[3] = ls.n_cu;
+  RenderPlan p;
+  int rc;
+  if ((rc = render_prologue(sp, f, opts, &p)) || (rc = plan_render(&p))) return rc;
+  out[0] = p.ls.blocks, out[1] = p.ls.threads, out[2] = p.ls.per_cu, out[3] = p.ls.n_cu;
   return RTMI_OK;
 }
 
@@ -835,34 +885,147 @@ int rtmi_render_mode(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_rende
 }
 int rtmi_render_mode_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, int32_t *dst, int n) {
   if (!sp || !dst || n < 0) return fail(RTMI_ERR_INVALID, "null argument");
-  int32_t out[RTMI_MODE_FIELDS];
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  FrameDev d;
-  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
-  RenderTuning tune;
-  void *scratch;
-  size_t scratch_bytes;
-  int rc = resolve_opts(opts, &tune, &scratch, &scratch_bytes);
-  if (rc) return rc;
-  LaunchShape ls;
-  if ((rc = launch_shape(s, d, tune, &ls))) return rc;
-  tune.lane_stride = ls.lane_stride;
-  const RenderMode m = decide_mode(d, ls.variant, ls, tune);
-  const int waves = ls.blocks * (ls.threads / 64);
-  out[0] = m.scheduled ? 1 : 0;
-  out[1] = m.scheduled ? m.probe_spp : 0;
-  out[2] = m.resume ? 1 : 0;
-  const int simds = ls.n_cu * 4 < waves ? ls.n_cu * 4 : waves, rounds = simds > 0 ? (waves + simds - 1) / simds : 0;
-  out[3] = m.scheduled && m.may_plan && m.prio && simds * rounds <= kMaxChains ? 1 : 0;
-  out[4] = m.prio ? tune.prio_every : 0;
-  out[5] = ls.lane_stride;
-  out[6] = waves;
-  out[7] = d.local_tiles;
-  // the kernel of the launch that finishes the frame (rtmi_render_ex hands launch_render the same facts)
-  out[8] = launch_fast_path(ls.variant, s->dev, d, ls.threads, tune, m.prio, out[3] != 0, m.resume, m.scheduled) != 0u ? 1 : 0;
+  RenderPlan p;
+  int rc;
+  if ((rc = render_prologue(sp, f, opts, &p)) || (rc = plan_render(&p))) return rc;
+  // ([8]: the kernel of the launch that finishes the frame)
+  const int32_t out[RTMI_MODE_FIELDS] = {p.scheduled, p.scheduled ? p.probe_spp : 0, p.resume, p.chains, p.prio ? p.tune.prio_every : 0,
+                                         p.ls.lane_stride, p.waves, p.d.local_tiles, p.finish_fast != 0u};
   for (int i = 0; i < n && i < RTMI_MODE_FIELDS; i++) dst[i] = out[i];
   return RTMI_OK;
+}
+
+// The regions of a call's scratch (ScratchLayout's offsets) as pointers.
+struct Scratch {
+  uint32_t *states, *rays, *cost, *order, *meta, *head, *work, *qcost, *qsorted, *qmap, *qmax, *fut, *claims, *prio_tab;
+  int32_t *next, *first;
+};
+static Scratch scratch_regions(void *base, const ScratchLayout &l) {
+  const auto at = [base](size_t off) { return reinterpret_cast<uint32_t *>(static_cast<char *>(base) + off); };
+  const auto ints = [&at](size_t off) { return reinterpret_cast<int32_t *>(at(off)); };
+  return Scratch{at(l.states), at(l.rays), at(l.cost), at(l.order), at(l.meta), at(l.head), at(l.work), at(l.qcost), at(l.qsorted),
+                 at(l.qmap), at(l.qmax), at(l.fut), at(l.claims), at(l.prio_tab), ints(l.next), ints(l.first)};
+}
+
+// Executes a plan: resolves the scratch, then memsets, copies and launches in stream order.  Decides nothing.
+static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uint32_t *d_ray_counts, hipStream_t st) {
+  const Scene *s = p.s;
+  const FrameDev &d = p.d;
+  const ScratchLayout sl = scratch_layout(d);
+  if (p.user_scratch && p.user_scratch_bytes < sl.total)
+    return fail(RTMI_ERR_INVALID, "rtmi_render_opts.scratch_bytes < rtmi_render_scratch_bytes(frame)");
+  // Every piece of device state of this call -- queue cursors, ray total, abandoned-search flag, the scheduler's
+  // buffers -- lives in the caller's scratch when one is given: renders of one scene on several streams (or as N
+  // shards on one device) then share nothing but the read-only scene.  Without one the scene's own (a cache, not
+  // scene state) is used, which ties renders of this scene to one at a time.
+  unsigned long long *counters = p.user_scratch ? reinterpret_cast<unsigned long long *>(p.user_scratch) : s->d_counters;
+  // the kernels' argument blocks (kernels.hip: RenderParams): probe pass, real pass
+  char *params = p.user_scratch ? reinterpret_cast<char *>(p.user_scratch) + sl.params
+                                : reinterpret_cast<char *>(s->d_counters) + kCounterBytes;
+  void *scratch = p.user_scratch;
+  if (!scratch && p.scratch) {
+    Scene *ms = const_cast<Scene *>(s);
+    std::lock_guard<std::mutex> lk(g_mu);  // (re)allocation only
+    if (ms->sched_bytes < sl.total) {
+      if (ms->d_sched) (void)hipFree(ms->d_sched);
+      ms->d_sched = nullptr, ms->sched_bytes = 0;
+      HIP_TRY(hipMalloc(&ms->d_sched, sl.total));
+      ms->sched_bytes = sl.total;
+    }
+    scratch = ms->d_sched;
+  }
+  const Scratch r = scratch ? scratch_regions(scratch, sl) : Scratch{};
+  SchedPlan plan;
+  uint32_t *ray_buf = d_ray_counts;  // (a resumed pixel reads its count back: scratch when the caller wants none)
+  if (p.prio) {
+    plan.prio_tab = r.prio_tab;
+    HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
+  }
+  if (p.scheduled) {
+    const size_t n = (size_t)d.items, nt = (size_t)d.local_tiles;
+    uint32_t *first_states = p.resume ? d_states : r.states;
+    uint32_t *first_rays = p.resume && d_ray_counts ? d_ray_counts : r.rays;
+    if (p.resume) ray_buf = first_rays;
+    else HIP_TRY(hipMemcpyAsync(r.states, d_states, n * RTMI_STATE_WORDS * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
+    // (a discarded probe writes its radiance into d_tiles, which the real pass overwrites)
+    SchedPlan probe_plan;
+    if (p.by_cost) {
+      HIP_TRY(hipMemsetAsync(r.work, 0, n * 4, st));
+      probe_plan.visit_counts = r.work;
+    }
+    if (p.first_prio) probe_plan.prio_tab = plan.prio_tab;
+    HIP_TRY(launch_render(p.ls.variant, s->dev, p.first, first_states, d_tiles, first_rays, counters, probe_plan, true,
+                          p.first_fast, p.ls.blocks, p.ls.threads, p.tune, params, st));
+#ifdef RTMI_CHECK_MARGINS
+    // Test hook of the check build: RTMI_CHECK_PLANT_ABANDONED=1 (read once) counts one abandoned mesh search after every
+    // first pass the frame keeps.  No world makes the search abandon one (mesh_search.h), and a test has to see that
+    // rtmi_render_status still reports it after the second launch (tests/test_gpu_first_pass_status.py).
+    static const bool plant_abandoned = env_int("RTMI_CHECK_PLANT_ABANDONED", 0) != 0;
+    if (plant_abandoned && p.resume) HIP_TRY(launch_add_one(counters + 2, st));
+#endif
+    if (p.first_prio) HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
+    // The scheduler's kernels read the first pass's ray counts and MARK the head's pixels in them (bit 31), and the
+    // marks must outlive the pixels' final counts, which the second launch writes into the same words as it goes: they
+    // work on a copy (in the region a discarded probe's RNG states would have used).
+    if (p.resume) HIP_TRY(hipMemcpyAsync(r.states, first_rays, n * 4, hipMemcpyDeviceToDevice, st));
+    uint32_t *rays = p.resume ? r.states : r.rays;
+    // the head of a mesh frame's queue: pixels in weight classes (the default), or -- when the call names a
+    // sparse stride, or RTMI_HEAD_CLASSES=0 -- the outlier tiles at one pixel per that many lanes
+    const bool by_pixels = p.tune.head_classes != 0;
+    uint32_t *head = (p.ls.variant & F_BVH) && by_pixels ? r.head : nullptr;
+    HIP_TRY(launch_tile_order(rays, d.local_tiles, r.cost, r.meta, r.order, head, p.sparse_cap, p.waves, p.tune.outlier_x10,
+                              p.tune.head_pct, st));
+    // (the head's marks in rays are bit 31: quarter_cost_kernel masks them off)
+    HIP_TRY(launch_quarter_order(r.order, p.by_cost && by_pixels ? r.work : nullptr, rays, d.local_tiles, r.qcost, r.qsorted,
+                                 r.qmax, r.qmap, st));
+    plan.tile_order = r.qmap;
+    plan.sparse_items = r.meta + 1;
+    plan.head_list = head;
+    plan.probe_marks = head ? rays : nullptr;
+    plan.probe_spp = p.probe_spp;
+    plan.tile_cost = r.cost;
+    if (p.chains) {
+      HIP_TRY(launch_chain_plan(r.order, r.cost, d.local_tiles, p.plan_simds, p.plan_rounds, d.spp, p.probe_spp, r.first, r.next,
+                                r.fut, st));
+      HIP_TRY(hipMemsetAsync(r.claims, 0, nt * 4, st));
+      plan.chain_next = r.next, plan.chain_fut = r.fut, plan.chain_first = r.first, plan.claims = r.claims;
+      plan.plan_simds = p.plan_simds, plan.plan_rounds = p.plan_rounds;
+      plan.tile_order = r.order;  // (per tile in this mode: the take-over's order)
+    }
+  }
+  // The counter words (render_body.h, mesh_search.h; rtmi_debug_counters) before the launch that finishes the frame:
+  //   [0]       work-queue cursor                                   zeroed (per launch)
+  //   [1]       closest-hit queries                                 zeroed (a resumed pixel re-adds its whole count)
+  //   [2]       abandoned mesh searches (rtmi_render_status)        kept after a first pass the frame keeps
+  //   [3]       head-queue cursor                                   zeroed (per launch)
+  //   [4..32]   -DRTMI_STATS wave step counts and cycles            zeroed (per launch)
+  //   [33] [34] -DRTMI_CHECK_MARGINS queries re-done, disagreements kept after a first pass the frame keeps
+  //   [35] [36] planned chains: SIMD arrival, take-over cursor      zeroed (per launch)
+  //   [37..39]  unused                                              zeroed
+  // So a resumed frame reports in [2], [33] and [34] over both launches.  Otherwise every word is zeroed: a discarded
+  // probe's samples are not in the image.
+  if (p.resume) {
+    HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(counters + 3, 0, 30 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(counters + 35, 0, (RTMI_COUNTER_WORDS - 35) * sizeof(unsigned long long), st));
+  } else {
+    HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
+  }
+  HIP_TRY(launch_render(p.ls.variant, s->dev, p.finish, d_states, d_tiles, ray_buf, counters, plan, false, p.finish_fast,
+                        p.ls.blocks, p.ls.threads, p.tune, params + render_params_bytes(), st));
+  return RTMI_OK;
+}
+
+int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
+                   float *d_tiles, uint32_t *d_ray_counts, void *stream) {
+  if (!sp || !d_states || !d_tiles) return fail(RTMI_ERR_INVALID, "null argument");
+  RenderPlan p;
+  int rc;
+  if ((rc = render_prologue(sp, f, opts, &p)) || (rc = check_depth(p.d.max_depth)) || (rc = check_pixel_queries(p.d)) ||
+      (rc = plan_render(&p)))
+    return rc;
+  return run_plan(p, reinterpret_cast<uint32_t *>(d_states), d_tiles, d_ray_counts, (hipStream_t)stream);
 }
 
 int rtmi_fast_path_kernel(const int32_t facts[RTMI_FAST_PATH_FACTS]) {
@@ -1073,163 +1236,6 @@ int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samp
   const int rc = budget_frame(f, d_sum && d_samples && d_tiles, "null sum, sample-count or tile array", &d);
   if (rc) return rc;
   HIP_TRY(launch_resolve(d, d_sum, d_samples, post_process, d_tiles, (hipStream_t)stream));
-  return RTMI_OK;
-}
-
-int rtmi_render_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
-                   float *d_tiles, uint32_t *d_ray_counts, void *stream) {
-  if (!sp || !d_states || !d_tiles) return fail(RTMI_ERR_INVALID, "null argument");
-  RenderTuning tune;
-  void *user_scratch = nullptr;
-  size_t user_scratch_bytes = 0;
-  int rc = resolve_opts(opts, &tune, &user_scratch, &user_scratch_bytes);
-  if (rc) return rc;
-  const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  FrameDev d;
-  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
-  if ((rc = check_depth(d.max_depth)) || (rc = check_pixel_queries(d))) return rc;
-  LaunchShape ls;
-  if ((rc = launch_shape(s, d, tune, &ls))) return rc;
-  const uint32_t variant = ls.variant;
-  const int threads = ls.threads, blocks = ls.blocks;
-  tune.lane_stride = ls.lane_stride;
-  hipStream_t st = (hipStream_t)stream;
-  const ScratchLayout sl = scratch_layout(d);
-  const size_t need = sl.total;
-  if (user_scratch && user_scratch_bytes < need)
-    return fail(RTMI_ERR_INVALID, "rtmi_render_opts.scratch_bytes < rtmi_render_scratch_bytes(frame)");
-  // Every piece of device state of this call -- queue cursors, ray total, abandoned-search flag, the scheduler's
-  // buffers -- lives in the caller's scratch when one is given: renders of one scene on several streams (or as N
-  // shards on one device) then share nothing but the read-only scene.  Without one the scene's own (a cache, not
-  // scene state) is used, which ties renders of this scene to one at a time.
-  unsigned long long *counters = user_scratch ? reinterpret_cast<unsigned long long *>(user_scratch) : s->d_counters;
-  // the kernels' argument blocks (kernels.hip: RenderParams): probe pass, real pass
-  char *params = user_scratch ? reinterpret_cast<char *>(user_scratch) + sl.params
-                              : reinterpret_cast<char *>(s->d_counters) + kCounterBytes;
-  // Longest-first tile order, first pass, plan, priorities: decide_mode
-  SchedPlan plan;
-  const RenderMode mode = decide_mode(d, variant, ls, tune);
-  const bool scheduled = mode.scheduled, may_plan = mode.may_plan, prio = mode.prio;
-  const int probe_spp = mode.probe_spp;
-  void *scratch = user_scratch;
-  if (!scratch && (scheduled || prio)) {
-    Scene *ms = const_cast<Scene *>(s);
-    std::lock_guard<std::mutex> lk(g_mu);  // (re)allocation only
-    if (ms->sched_bytes < need) {
-      if (ms->d_sched) (void)hipFree(ms->d_sched);
-      ms->d_sched = nullptr, ms->sched_bytes = 0;
-      HIP_TRY(hipMalloc(&ms->d_sched, need));
-      ms->sched_bytes = need;
-    }
-    scratch = ms->d_sched;
-  }
-  FrameDev first = d;               // the launch that finishes the frame: all of it, or what a first pass left
-  uint32_t *ray_buf = d_ray_counts;  // (a resumed pixel reads its count back: scratch when the caller wants none)
-  auto region = [scratch](size_t off) { return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scratch) + off); };
-  if (prio) {
-    plan.prio_tab = region(sl.prio_tab);
-    HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
-  }
-  if (scheduled) {
-    const size_t n = (size_t)d.items, nt = (size_t)d.local_tiles;
-    uint32_t *p_states = region(sl.states), *p_rays = region(sl.rays), *p_cost = region(sl.cost), *p_order = region(sl.order);
-    uint32_t *p_meta = region(sl.meta), *p_work = region(sl.work);
-    uint32_t *p_qcost = region(sl.qcost), *p_qsorted = region(sl.qsorted), *p_qmap = region(sl.qmap), *p_qmax = region(sl.qmax);
-    uint32_t *p_fut = region(sl.fut), *p_claims = region(sl.claims);
-    int32_t *p_next = reinterpret_cast<int32_t *>(region(sl.next)), *p_first = reinterpret_cast<int32_t *>(region(sl.first));
-    // mesh frames (binary32 t): the probe also books the lane-steps of its mesh searches on the pixels they serve
-    const bool by_cost = tune.cost_probe && (variant & F_BVH) && !(variant & F_SPHERE);
-    // first pass: the frame's own samples [0, probe_spp) into the caller's buffers, or a discarded probe on copies
-    const bool resume = mode.resume;
-    uint32_t *first_states = resume ? reinterpret_cast<uint32_t *>(d_states) : p_states;
-    uint32_t *first_rays = resume && d_ray_counts ? d_ray_counts : p_rays;
-    if (!resume) HIP_TRY(hipMemcpyAsync(p_states, d_states, n * RTMI_STATE_WORDS * 4, hipMemcpyDeviceToDevice, st));
-    FrameDev probe = d;
-    if (resume) {
-      probe.k_end = probe_spp;
-      first.k_begin = probe_spp, ray_buf = first_rays;
-    } else {
-      probe.spp = probe_spp, probe.k_end = probe_spp;
-    }
-    HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
-    // (a discarded probe writes its radiance into d_tiles, which the real pass overwrites)
-    SchedPlan probe_plan;
-    if (by_cost) {
-      HIP_TRY(hipMemsetAsync(p_work, 0, n * 4, st));
-      probe_plan.visit_counts = p_work;
-    }
-    // (a first pass of the frame's own samples is a frame of s1 samples per pixel: from 32 on it has wave priorities too)
-    const bool first_prio = prio && resume && probe_spp >= 32 && env_int("RTMI_FIRST_PRIO", 1) != 0;
-    if (first_prio) probe_plan.prio_tab = plan.prio_tab;
-    HIP_TRY(launch_render(variant, s->dev, probe, first_states, d_tiles, first_rays, counters, probe_plan, true, blocks,
-                          threads, tune, params, st));
-#ifdef RTMI_CHECK_MARGINS
-    // Test hook of the check build: RTMI_CHECK_PLANT_ABANDONED=1 (read once) counts one abandoned mesh search after every
-    // first pass the frame keeps.  No world makes the search abandon one (mesh_search.h), and a test has to see that
-    // rtmi_render_status still reports it after the second launch (tests/test_gpu_first_pass_status.py).
-    static const bool plant_abandoned = env_int("RTMI_CHECK_PLANT_ABANDONED", 0) != 0;
-    if (plant_abandoned && resume) HIP_TRY(launch_add_one(counters + 2, st));
-#endif
-    if (first_prio) HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
-    if (resume) {
-      // The scheduler's kernels read the first pass's ray counts and MARK the head's pixels in them (bit 31), and the
-      // marks must outlive the pixels' final counts, which the second launch writes into the same words as it goes: they
-      // work on a copy (in the region a discarded probe's RNG states would have used).
-      HIP_TRY(hipMemcpyAsync(p_states, first_rays, n * 4, hipMemcpyDeviceToDevice, st));
-      p_rays = p_states;
-    }
-    const uint32_t sparse_cap = (uint32_t)(((int64_t)blocks * threads / tune.sparse_stride) / 64 * 64);
-    // the head of a mesh frame's queue: pixels in weight classes (the default), or -- when the call names a
-    // sparse stride, or RTMI_HEAD_CLASSES=0 -- the outlier tiles at one pixel per that many lanes
-    static const bool head_classes = env_int("RTMI_HEAD_CLASSES", 1) != 0;
-    const bool by_pixels = head_classes && !(opts && opts->sparse_stride > 0);
-    uint32_t *p_head = (variant & F_BVH) && by_pixels ? region(sl.head) : nullptr;
-    HIP_TRY(launch_tile_order(p_rays, d.local_tiles, p_cost, p_meta, p_order, p_head, sparse_cap, blocks * (threads / 64),
-                              tune.outlier_x10, tune.head_pct, st));
-    // (the head's marks in p_rays are bit 31: quarter_cost_kernel masks them off)
-    HIP_TRY(launch_quarter_order(p_order, by_cost && by_pixels ? p_work : nullptr, p_rays, d.local_tiles, p_qcost, p_qsorted, p_qmax,
-                                 p_qmap, st));
-    plan.tile_order = p_qmap;
-    plan.sparse_items = p_meta + 1;
-    plan.head_list = p_head;
-    plan.probe_marks = p_head ? p_rays : nullptr;
-    plan.probe_spp = probe_spp;
-    plan.tile_cost = p_cost;
-    // list frames: planned chains instead of the queue (kernels.h: launch_chain_plan)
-    const int grid_waves = blocks * (threads / 64);
-    if (may_plan && prio) {
-      const int simds = ls.n_cu * 4 < grid_waves ? ls.n_cu * 4 : grid_waves;  // (four SIMDs per compute unit)
-      const int rounds = (grid_waves + simds - 1) / simds;
-      if (simds * rounds <= kMaxChains) {
-        HIP_TRY(launch_chain_plan(p_order, p_cost, d.local_tiles, simds, rounds, d.spp, probe_spp, p_first, p_next, p_fut, st));
-        HIP_TRY(hipMemsetAsync(p_claims, 0, nt * 4, st));
-        plan.chain_next = p_next, plan.chain_fut = p_fut, plan.chain_first = p_first, plan.claims = p_claims;
-        plan.plan_simds = simds, plan.plan_rounds = rounds;
-        plan.tile_order = p_order;  // (per tile in this mode: the take-over's order)
-      }
-    }
-  }
-  // The counter words (render_body.h, mesh_search.h; rtmi_debug_counters) before the launch that finishes the frame:
-  //   [0]       work-queue cursor                                   zeroed (per launch)
-  //   [1]       closest-hit queries                                 zeroed (a resumed pixel re-adds its whole count)
-  //   [2]       abandoned mesh searches (rtmi_render_status)        kept after a first pass the frame keeps
-  //   [3]       head-queue cursor                                   zeroed (per launch)
-  //   [4..32]   -DRTMI_STATS wave step counts and cycles            zeroed (per launch)
-  //   [33] [34] -DRTMI_CHECK_MARGINS queries re-done, disagreements kept after a first pass the frame keeps
-  //   [35] [36] planned chains: SIMD arrival, take-over cursor      zeroed (per launch)
-  //   [37..39]  unused                                              zeroed
-  // So a resumed frame reports in [2], [33] and [34] over both launches.  Otherwise every word is zeroed: a discarded
-  // probe's samples are not in the image.
-  if (mode.resume) {
-    HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(counters + 3, 0, 30 * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(counters + 35, 0, (RTMI_COUNTER_WORDS - 35) * sizeof(unsigned long long), st));
-  } else {
-    HIP_TRY(hipMemsetAsync(counters, 0, kCounterBytes, st));
-  }
-  HIP_TRY(launch_render(variant, s->dev, first, reinterpret_cast<uint32_t *>(d_states), d_tiles, ray_buf, counters,
-                        plan, false, blocks, threads, tune, params + render_params_bytes(), st));
   return RTMI_OK;
 }
 

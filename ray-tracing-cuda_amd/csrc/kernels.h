@@ -18,7 +18,7 @@ hipError_t launch_rng_init(uint64_t seed, const FrameDev &fr, const uint32_t *d_
 
 // Kernel specialisation covering a feature set, its occupancy, and its launch.
 uint32_t pick_variant(uint32_t features);
-// fast_path: the launch may be one of the fast kernels (fast_path_scene): the answer holds for whichever is launched.
+// fast_path: the launch may be one of the fast kernels: the answer holds for whichever is launched.
 int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, bool fast_path = false);
 // d_tile_order (nullable): the work queue hands out local tile d_tile_order[k] as its k-th tile.
 // d_sparse_items (nullable; needs d_tile_order): device word, how many leading work items are outlier
@@ -44,6 +44,10 @@ struct RenderTuning {
   int prio_every;     // > 0: the waves of a SIMD are served longest-remaining-chain-first, each looking at its priority every
                       // this many iterations (a power of two); 0: the hardware's oldest-first order
   int fast_path;      // 1: a launch whose run-time modes are all the common ones uses the kernel compiled for them (below)
+  int head_classes;   // mesh frames: 1 = the head of the queue is pixels in weight classes; 0 (or a call that names a sparse stride) = outlier tiles
+  int first_prio;     // 1: a first pass of the frame's own samples has wave priorities from 32 samples on
+  int fetch_batch, fetch_batch_first;  // list frames: the largest batch a wave draws from the queue per atomic in longest-first order /
+                                       // in a first pass of a few samples (1..64; A/B measurements)
 };
 
 // Compile-time mode word of the trace kernel (render_body.h, closest_hit.h: template parameter M).  One kernel body
@@ -66,8 +70,8 @@ constexpr uint32_t kFastCommon = PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED 
                                  PIN_EVERY_LANE | PIN_PRIORITIES;
 constexpr uint32_t kFastChains = kFastCommon | PIN_CHAINS;  // the second launch of a planned frame (C2, a C4 shard)
 constexpr uint32_t kFastQueue = kFastCommon | PIN_QUEUE;    // a first pass, a queued or image-order frame
-// Everything the fast kernels take for granted, as the launch knows it.  One predicate for the launch, for
-// rtmi_render_mode and for the tests (rtmi_fast_path_kernel).
+// Everything the fast kernels take for granted, as the call's plan knows it (capi.hip: plan_render).  One predicate for
+// the plan, which the launch and rtmi_render_mode both read, and for the tests (rtmi_fast_path_kernel).
 struct FastPathFacts {
   int enabled;           // RenderTuning::fast_path
   uint32_t variant;      // the kernel variant (pick_variant)
@@ -85,6 +89,9 @@ struct FastPathFacts {
 };
 // 0: the general kernel; else kFastChains or kFastQueue.
 uint32_t fast_path_mode(const FastPathFacts &f);
+// The facts that are known before the launch shape is (scene, frame, switch); the plan adds the lane stride and each
+// launch's last four.
+FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled);
 // What the scheduler's probe pass leaves for the real pass (device pointers, all optional).
 struct SchedPlan {
   const uint32_t *tile_order = nullptr;    // the queue's order per quarter tile (launch_quarter_order)
@@ -106,17 +113,11 @@ struct SchedPlan {
 // d_params: render_params_bytes() of device memory that stays untouched until the launch has finished (the kernel's
 // argument block, written in stream order just before it).
 size_t render_params_bytes();
+// fast: the launch's mode word as the plan computed it (0: the general kernel); hipErrorInvalidValue when the block this
+// launch would write breaks what a pinned kernel's bits promise.
 hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
                          uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan, bool probe,
-                         int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream);
-// The part of fast_path_mode that is known before the launch shape is (scene, frame, switch): without it no launch of
-// this frame uses a fast kernel.
-bool fast_path_scene(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled);
-// The mode word launch_render uses for a launch (0: the general kernel): tune carries the launch shape's lane stride;
-// priorities, chains, tile_cost: the launch has a priority table, walks planned chains, has the probe's tile costs;
-// resumed: it resumes a first pass (fr.k_begin > 0, with a ray-count buffer).
-uint32_t launch_fast_path(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, const RenderTuning &tune,
-                          bool priorities, bool chains, bool resumed, bool tile_cost);
+                         uint32_t fast, int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream);
 // Tiles sorted by descending cost (sum of 64 ray counts each); d_cost/d_order hold n_tiles words,
 // d_meta 16: [0] the largest tile cost, [1] the sparse item count.
 // sparse_cap: work items the grid holds at one pixel per tune.sparse_stride lanes (a multiple of 64).

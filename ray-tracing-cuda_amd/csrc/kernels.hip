@@ -160,7 +160,7 @@ static_assert(kCallParamsOffset + sizeof(CallParams) <= (size_t)RTMI_TRACE_WORK_
 static_assert(kCallParamsOffset % alignof(CallParams) == 0, "the argument block is aligned in d_work");
 
 // M: the mode word (kernels.h).  0 is the general kernel; kFastChains and kFastQueue are instantiated for the
-// list-triangle variant (launch_render) and launched when fast_path_mode says the launch is what they were compiled for.
+// list-triangle variant (launch_render) and launched when the call's plan says the launch is what they were compiled for.
 template <uint32_t F, uint32_t M = 0>
 __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void render_kernel(const RenderParams *p) {
   const RenderParams &rp = in_constant(p);
@@ -697,7 +697,7 @@ uint32_t fast_path_mode(const FastPathFacts &f) {
   if (!f.chains) return kFastQueue;
   return f.resumed && f.tile_cost ? kFastChains : 0u;
 }
-static FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
+FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
   size_t lds = 0;
   const LaunchCfg lc = make_cfg(variant, sc, fr, threads, &lds);
   FastPathFacts f{};
@@ -705,18 +705,6 @@ static FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const
   f.pairs_in_lds = lc.pairs_off >= 0 && lc.nrm_off >= 0 && lc.list_off >= 0;
   f.unsigned_colours = sc.unsigned_colours, f.det_safe = sc.det_safe, f.width = fr.width, f.height = fr.height;
   return f;
-}
-bool fast_path_scene(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
-  FastPathFacts f = fast_path_facts(variant, sc, fr, threads, enabled);
-  f.lane_stride = 1, f.priorities = 1;
-  return fast_path_mode(f) != 0u;
-}
-uint32_t launch_fast_path(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, const RenderTuning &tune,
-                          bool priorities, bool chains, bool resumed, bool tile_cost) {
-  FastPathFacts f = fast_path_facts(variant, sc, fr, threads, tune.fast_path);
-  f.lane_stride = tune.lane_stride > 0 ? tune.lane_stride : 1;
-  f.priorities = priorities, f.chains = chains, f.resumed = resumed, f.tile_cost = tile_cost;
-  return fast_path_mode(f);
 }
 
 // *per_cu = workgroups of Kernel per compute unit at this launch shape; 0 with an error: it does not fit, or the HIP
@@ -778,7 +766,7 @@ static int image_order_batch(int samples, int cap) {
 
 hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &fr, uint32_t *d_states, float *d_out,
                          uint32_t *d_ray_counts, unsigned long long *d_counters, const SchedPlan &plan, bool probe,
-                         int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream) {
+                         uint32_t fast, int blocks, int threads, const RenderTuning &tune, void *d_params, hipStream_t stream) {
   return with_listed<kVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
     size_t lds = 0;
@@ -800,16 +788,14 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
     lc.chain_fut = plan.chain_fut, lc.chain_first = plan.chain_first, lc.claims = plan.claims;
     lc.plan_simds = plan.plan_simds, lc.plan_rounds = plan.plan_rounds;
     lc.prio_every = tune.prio_every > 0 ? tune.prio_every : 16;
-    {  // (render_body.h: the wave draws from the queue in batches; RTMI_FETCH_BATCH / RTMI_FETCH_BATCH_FIRST: A/B measurements)
-      static const int batch_main = [] { const char *e = getenv("RTMI_FETCH_BATCH"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : v > 64 ? 64 : v; }();
-      static const int batch_first = [] { const char *e = getenv("RTMI_FETCH_BATCH_FIRST"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v > 64 ? 64 : v; }();
+    {  // (render_body.h: the wave draws from the queue in batches; tune.fetch_batch / fetch_batch_first: A/B measurements)
       // a first pass of a few samples: whole tiles; longest-first order: 16 (measured 4 / 16 / 64 on frames of 2.3 ...
       // 12.8 pixels per lane, NOTES.md); image order, or a first pass as long as a frame: the lanes that wait
       // (a pooled item waits for a lane of its wave: the longer a pixel takes, the fewer -- from 4,096 samples on, none)
       const int samples = fr.k_end - fr.k_begin > 0 ? fr.k_end - fr.k_begin : 1;
       const int by_length = 4096 / samples < 1 ? 1 : 4096 / samples;
       // image order (a frame too short to be scheduled, or a first pass as long as a frame): image_order_batch
-      lc.fetch_batch = probe && samples <= 4 ? batch_first : plan.tile_order != nullptr ? (by_length < batch_main ? by_length : batch_main) : image_order_batch(samples, 16);
+      lc.fetch_batch = probe && samples <= 4 ? tune.fetch_batch_first : plan.tile_order != nullptr ? std::min(by_length, tune.fetch_batch) : image_order_batch(samples, 16);
     }
     RenderParams rp;
     rp.sc = sc, rp.fr = fr, rp.lc = lc;
@@ -817,13 +803,16 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
     RenderParams *dp = reinterpret_cast<RenderParams *>(d_params);
     const LaunchAt at{blocks, threads, lds, stream};
     if constexpr (F == (uint32_t)F_TRIS) {
-      // the kernels compiled for the common list frame, when this launch is one (fast_path_mode; a probe never walks chains)
-      const uint32_t mode = launch_fast_path(F, sc, fr, threads, tune, lc.prio_tab != nullptr, lc.chain_next != nullptr,
-                                             fr.k_begin > 0 && d_ray_counts != nullptr, lc.tile_cost != nullptr);
-      if (mode == kFastChains && !probe) return launch_block<render_kernel<F, kFastChains>>(at, rp, dp);
-      if (mode == kFastQueue && !probe) return launch_block<render_kernel<F, kFastQueue>>(at, rp, dp);
-      if (mode == kFastQueue && probe) return launch_block<probe_kernel<F, kFastQueue>>(at, rp, dp);
+      // the kernels compiled for the common list frame: which one the plan says (capi.hip: plan_render), checked here
+      // against what their bits promise of this block (kernels.h: PIN_PRIORITIES, PIN_EVERY_LANE, PIN_CHAINS, PIN_QUEUE)
+      const bool chains = fast == kFastChains && !probe && lc.chain_next && lc.tile_cost && fr.k_begin > 0 && d_ray_counts;
+      const bool queue = fast == kFastQueue && !lc.chain_next;
+      if (fast != 0u && (!lc.prio_tab || lc.lane_stride != 1 || !(chains || queue))) return hipErrorInvalidValue;
+      if (chains) return launch_block<render_kernel<F, kFastChains>>(at, rp, dp);
+      if (queue && !probe) return launch_block<render_kernel<F, kFastQueue>>(at, rp, dp);
+      if (queue) return launch_block<probe_kernel<F, kFastQueue>>(at, rp, dp);
     }
+    if (fast != 0u) return hipErrorInvalidValue;  // (only the list-triangle variant has fast kernels)
     if (probe) return launch_block<probe_kernel<F>>(at, rp, dp);
     return launch_block<render_kernel<F>>(at, rp, dp);
   });

@@ -757,7 +757,10 @@ def test_render_mode_reports_the_schedule_of_the_baseline_configs():
     def mode(name, side, spp, depth, rank=0, world=1, **kw):
         b = common.build_scene(rtmi.SceneBuilder(common.scene_seed(name)), name, 1.0).commit()
         R = rtmi.Renderer(b, side, side, spp, depth, True, rank=rank, world_size=world)
-        return R.mode(rtmi.render_opts(**kw) if kw else None)
+        opts = rtmi.render_opts(**kw) if kw else None
+        m, shape = R.mode(opts), R.launch_shape(opts)
+        assert m["waves"] == shape["blocks"] * shape["threads"] // 64, (m, shape)  # both reports read one plan
+        return m
     c2 = mode("cornell_box", 1024, 1024, 50)
     assert c2["scheduled"] == 1 and c2["first_pass_resumed"] == 1 and c2["first_pass_samples"] == 64 and c2["planned_chains"] == 1
     assert c2["wave_priority_every"] == 16 and c2["lane_stride"] == 1 and c2["tiles"] == 16384 and c2["tiles"] <= 3 * c2["waves"]
