@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/*.npz from the CPU oracle (oracle/oracle.cc).
+"""Generates tests/golden/*.npz.
 
-The reference (CUDA-only) cannot run in this image and ships no fixtures, so these
-vectors are produced by the oracle — itself pinned by the known-answer tests in
-tests/test_oracle_known_answers.py and the rocRAND cross-check — and serve as
-(1) a cross-machine determinism check of the oracle and (2) fixed expected outputs for
-the HIP path.  Each file holds the inputs' description and the expected outputs:
-rgb float32 (H,W,3), per-pixel ray counts uint32 (H,W), final RNG states uint32 (H*W,6).
+Without arguments: from the CPU oracle (oracle/oracle.cc).  These serve as (1) a cross-machine determinism check of
+the oracle and (2) fixed expected outputs for the HIP path.  Each file holds rgb float32 (H,W,3), per-pixel ray counts
+uint32 (H,W), final RNG states uint32 (H*W,6).
 
-Run from the repo root:  python tests/golden/make_golden.py
+--ref: from the reference's own renderer built for the CPU (oracle/_ref/libref.so, which needs the reference checkout:
+make -C oracle _ref/libref.so).  Everything written is data that the reference's code produced, with the inputs it
+was given, so the pin travels to machines without the checkout (tests/test_ref_golden.py, tests/test_gpu_ref_golden.py):
+  ref_<scene>_<h>x<w>_s<spp>_d10_{post,raw}.npz   seeds (2,), rgb (2,H,W,3), rays (2,H,W), states (2,H*W,6), total (2,)
+  ref_probe_<world>.npz    table (N,8) {origin, direction, t_from, t_to}, hit, rec {t,u,v,normal}, mat, keep (the fields
+                           of rec that the reference defines; the others are stored as zero)
+  ref_scatter.npz          table, states, scattered, out {attenuation, ray, emitted}, after
+  ref_camera.npz           xy, states, and per camera kind: frame, rays, after
+The cases are those of tests/refcases.py; the probe tables are a quarter of the length tests/test_ref_parity.py uses.
+
+Run from the repo root:  python tests/golden/make_golden.py [--ref]
 """
 import os
 import sys
@@ -47,5 +54,40 @@ def main():
         print("%-12s %dx%d s%d d%d %s -> %d rays" % (name, h, w, spp, depth, "post" if post else "raw", total))
 
 
+def main_ref():
+    import oraclelib
+    import refcases as rc
+    import reflib
+    assert reflib.available(), reflib.SKIP_REASON
+    for name, h, w, spp in rc.FRAMES:
+        for post in (True, False):
+            res = []
+            for seed in rc.SEEDS:
+                res.append(rc.build_frame_scene(reflib.RefBuilder(seed), name, w / h).render(h, w, spp, post=post))
+            rgb, rays, states, total = (np.stack([np.asarray(r[k]) for r in res]) for k in range(4))
+            np.savez_compressed(os.path.join(HERE, rc.frame_file(name, h, w, spp, post)), seeds=np.array(rc.SEEDS, dtype=np.uint64),
+                                rgb=rgb, rays=rays, states=states, total=total.astype(np.uint64))
+            print("%-28s %s" % (rc.frame_file(name, h, w, spp, post), total))
+    for name in rc.PROBE_WORLDS:
+        r = rc.build_probe_world(reflib.RefBuilder(1), name)
+        table = rc.probe_table(r, name, scale=0.25)
+        hit, rec, mat = rc.run_probes(r, table)
+        keep = rc.defined_columns(name, hit, rec, mat)
+        np.savez_compressed(os.path.join(HERE, "ref_probe_%s.npz" % name), table=table, hit=hit, rec=np.where(keep, rec, 0.0),
+                            mat=mat, keep=keep)
+        print("ref_probe_%-18s %d rays, %d hits" % (name, table.shape[0], hit.sum()))
+    r = reflib.RefBuilder(1)
+    rc.scatter_materials(r)
+    table, states = rc.scatter_table(n_per_material=60)
+    sc, out, after = rc.run_scatter(r, table, states)
+    np.savez_compressed(os.path.join(HERE, "ref_scatter.npz"), table=table, states=states, scattered=sc, out=out, after=after)
+    xy, states = rc.camera_table()
+    cam = {"xy": xy, "states": states}
+    for kind in rc.CAMERAS:
+        cam[kind + "_frame"], cam[kind + "_rays"], cam[kind + "_after"] = rc.run_camera(rc.build_camera(reflib.RefBuilder(1), kind), xy, states)
+    np.savez_compressed(os.path.join(HERE, "ref_camera.npz"), **cam)
+    print("ref_scatter.npz, ref_camera.npz")
+
+
 if __name__ == "__main__":
-    main()
+    main_ref() if "--ref" in sys.argv[1:] else main()

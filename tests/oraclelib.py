@@ -73,6 +73,8 @@ def lib():
         L.orc_probe_hit.argtypes = [C.c_void_p, fp, fp, C.c_double, C.c_double, C.POINTER(C.c_double),
                                     C.POINTER(C.c_int)]
         L.orc_probe_scatter.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_double, fp, u32p, fp]
+        L.orc_set_host_variant.argtypes = [C.c_int]
+        L.orc_probe_scatter_ex.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_double, C.c_double, C.c_double, fp, u32p, fp]
         L.orc_probe_camera_ray.argtypes = [C.c_void_p, C.c_double, C.c_double, u32p, fp]
         L.orc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, fp, u32p,
                                  C.POINTER(C.c_int32), C.c_int64, C.c_int]
@@ -81,6 +83,23 @@ def lib():
         L.orc_post_process.argtypes = [fp, C.c_int64, C.c_int]
         _lib = L
     return _lib
+
+
+VARIANT_SPHERE_ROOT_POW, VARIANT_UNSTABLE_SORT, VARIANT_DISKRAND_RTL = 1, 2, 4
+
+
+class host_variant:
+    """``with host_variant(bits):`` the oracle makes the choices of the reference's g++ build for the named operations
+    (oracle.cc, "host-build variants") while scenes are built and queried inside the block; 0 again afterwards."""
+
+    def __init__(self, bits):
+        self.bits = bits
+
+    def __enter__(self):
+        lib().orc_set_host_variant(self.bits)
+
+    def __exit__(self, *exc):
+        lib().orc_set_host_variant(0)
 
 
 def _fp(a):
@@ -220,6 +239,13 @@ class OracleBuilder:
         out = np.zeros(9, dtype=np.float32)
         sc = self.L.orc_probe_scatter(self.h, mat, _fp(_f3(o)), _fp(_f3(d)), float(t), _fp(_f3(n)),
                                       state.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(out))
+        return bool(sc), out
+
+    def probe_scatter_ex(self, mat, o, d, t, u, v, n, state):
+        """Scatter with the record's u, v, then Emit at the hit point: (scattered, 12 floats {att, origin, dir, emitted})."""
+        out = np.zeros(12, dtype=np.float32)
+        sc = self.L.orc_probe_scatter_ex(self.h, mat, _fp(_f3(o)), _fp(_f3(d)), float(t), float(u), float(v),
+                                         _fp(_f3(n)), state.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(out))
         return bool(sc), out
 
     def probe_camera_ray(self, x, y, state=None):

@@ -359,10 +359,15 @@ def test_no_cpu_fallback():
 
 
 def test_product_does_not_import_the_oracle():
-    """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may touch oracle/."""
+    """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may touch oracle/; nothing but tests/ the
+    reference renderer built for the CPU (oracle/_ref/libref.so, tests/reflib.py)."""
     pkg = os.path.join(ROOT, "ray-tracing-cuda_amd")
     for dirpath, _, files in os.walk(pkg):
         for fn in files:
             if fn.endswith((".py", ".hip", ".h", ".cuh", ".cpp", ".hpp")):
                 txt = open(os.path.join(dirpath, fn), errors="ignore").read()
                 assert "oraclelib" not in txt and "liboracle" not in txt and "oracle/" not in txt, fn
+                assert "libref" not in txt and "reflib" not in txt and "ref_harness" not in txt, fn
+    for fn in ("bench.py", "__graft_entry__.py"):  # neither loads the reference renderer (build() only compiles it)
+        txt = open(os.path.join(ROOT, fn), errors="ignore").read()
+        assert "reflib" not in txt and "ref_render" not in txt, fn
