@@ -581,6 +581,77 @@ int rtmi_render_features(const rtmi_scene *s, const rtmi_frame *f, const uint32_
 int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const uint32_t *d_samples,
                           const rtmi_features *out, void *stream);
 
+/* ---------------------------------------------------------------- denoise --
+ * A variance- and feature-guided a-trous filter (edge-avoiding wavelets) for frames of a few samples per pixel, on what
+ * rtmi_render_budget and rtmi_render_features leave behind.  Added without a version change: a caller detects it by the
+ * symbol rtmi_denoise.  The filter is stated operation by operation in binary32, like rtmi_budget_plan: every + - * / is
+ * one operation rounded on its own (no fused multiply-add), sums of three are (x + y) + z, and fmax / fmin are IEEE
+ * maxNum / minNum (fmaxf).
+ *
+ * rtmi_resolve_variance: the variance OF THE MEAN of every work item, tile-major like rtmi_resolve, float[items][3].
+ * With n = d_samples[q], nf = (float)n, S = d_sum[q][c], Q = d_sq[q][c]:
+ *     padding, n == 0:  0
+ *     n == 1:           S * S                      (the sample's own square: an error of 100 %)
+ *     n >= 2:           a = nf * Q;  b = S * S;  c = fmax(a - b, 0);  d = nf * nf;  e = nf - 1;  c / (d * e)
+ * Asynchronous on `stream`; the argument checks are rtmi_resolve's (a bad frame, a null array). */
+int rtmi_resolve_variance(const rtmi_frame *f, const float *d_sum, const float *d_sq, const uint32_t *d_samples,
+                          float *d_var, void *stream);
+
+/* rtmi_denoise works on ROW-MAJOR buffers of the whole frame, float[H*W][3] or float[H*W] -- what rtmi_untile and
+ * rtmi_untile_u32 write: a stencil needs neighbours, which the tile-major shard buffers do not give.
+ *
+ * Start:  with demodulate, per channel ad = fmax(albedo, 0.01f), C = color / ad, V = variance / (ad * ad); else C = color,
+ * V = variance.  Then pass k = 0 .. iterations - 1 with step s = 2^k, for every pixel p = (i, j): the taps are
+ * q = (i + dy s, j + dx s), dy the outer loop from -2 to 2, dx the inner one, the centre included, taps outside the image
+ * skipped.  With h = {1/16, 1/4, 3/8, 1/4, 1/16} and falloff(x) = { m = fmax(1 - 0.25f * x, 0); m2 = m * m; m2 * m2 }:
+ *     surface:  sp = alpha_p > 0, sq = alpha_q > 0; sp != sq: the tap is skipped; neither: wn = wz = 1; both:
+ *       d  = fmax((nx_p nx_q + ny_p ny_q) + nz_p nz_q, 0);  wn = d squared normal_squarings times;
+ *       xz = fabs(z_p - z_q) / (sigma_depth * z_p + 1e-6f);  wz = falloff(xz);
+ *     colour:   dr, dg, db = C_p - C_q;  d2 = (dr dr + dg dg) + db db;
+ *       vs = ((Vr_p + Vg_p) + Vb_p) + ((Vr_q + Vg_q) + Vb_q);
+ *       xc = d2 / ((sigma_color * sigma_color) * vs + 1e-10f);  wc = falloff(xc);
+ *     w = (((h[dy] * h[dx]) * wn) * wz) * wc;
+ *     in tap order:  sw += w;  per channel  sc += w * C_q;  sv += (w * w) * V_q;
+ *     sw > 0:  C'_p = sc / sw,  V'_p = sv / (sw * sw);  otherwise C'_p = C_p, V'_p = V_p.
+ * Pass k + 1 reads C' and V'; the guides never change.  After the last pass d_out = demodulate ? C * ad : C and, where
+ * d_out_variance is not null, d_out_variance = demodulate ? V * (ad * ad) : V.
+ * So a pixel is averaged only with pixels on the same side of a coverage, normal or depth edge, and over a colour range of
+ * about sigma_color standard errors of the two pixels: the filter blurs the noise the variance reports and little else;
+ * d_out_variance is what is left of it (the weights taken as constants).  A non-finite input leaves the pixels whose
+ * footprint reaches it unspecified; it does not fault.
+ *
+ * Defaults (what rtmi.denoise of the Python binding passes): 5 iterations, sigma_color 1, sigma_depth 0.05, 0 normal
+ * squarings, demodulate where an albedo is given.  The mean normal's length is the pixel's coverage, so a power p of the
+ * cosine weighs a fully covered neighbour (1 / alpha_p)^p times the partly covered pixel itself: squarings sharpen
+ * creases inside a surface and eat its silhouette.  sigma_color 1 averages what lies within about one standard error.
+ *
+ * All per-call state -- the ping-pong images and the packed guide records -- lives in d_scratch
+ * (rtmi_denoise_scratch_bytes(height, width) bytes, any alignment): the call shares no device state with any other.  d_out
+ * may be exactly d_color; no other overlap between inputs, outputs and scratch is allowed.  Asynchronous on `stream`.
+ * RTMI_ERR_INVALID before any HIP call for: height or width outside 1..RTMI_MAX_EXTENT; a null o, g, d_color, d_out or
+ * d_scratch; a wrong size in either struct or reserved != 0; an option outside its range; a null required guide;
+ * scratch_bytes too small.  rtmi_denoise_scratch_bytes returns 0 for an extent outside 1..RTMI_MAX_EXTENT. */
+typedef struct rtmi_denoise_opts {
+  int32_t size;             /* sizeof(rtmi_denoise_opts) of the caller: must match the library's */
+  int32_t iterations;       /* 1..8; pass k (0-based) uses step s = 2^k pixels */
+  int32_t normal_squarings; /* 0..8: the normal weight is squared this many times */
+  int32_t demodulate;       /* 0/1: filter colour / albedo, multiply back at the end (needs d_albedo) */
+  float sigma_color;        /* finite, > 0 */
+  float sigma_depth;        /* finite, > 0 */
+} rtmi_denoise_opts;
+typedef struct rtmi_denoise_guides { /* row-major, whole frame */
+  int32_t size;            /* sizeof(rtmi_denoise_guides) of the caller: must match the library's */
+  int32_t reserved;        /* 0 */
+  const float *d_variance; /* required, float[H*W][3]: rtmi_resolve_variance's */
+  const float *d_albedo;   /* float[H*W][3]; required iff demodulate, else nullable and unused */
+  const float *d_normal;   /* required, float[H*W][3]: the MEAN normal of rtmi_resolve_features */
+  const float *d_depth;    /* required, float[H*W] */
+  const float *d_alpha;    /* required, float[H*W]: rtmi_resolve_features' coverage read as float */
+} rtmi_denoise_guides;
+size_t rtmi_denoise_scratch_bytes(int height, int width);
+int rtmi_denoise(int height, int width, const rtmi_denoise_opts *o, const float *d_color, const rtmi_denoise_guides *g,
+                 float *d_out, float *d_out_variance /* nullable */, void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /
  * RTMI_EXCLUSIVE / RTMI_OUTLIER_X10 / RTMI_HEAD_CLASSES (0: tiles) / RTMI_PROBE_SPP / RTMI_PLAN / RTMI_PRIO (wave_priority) /

@@ -1239,6 +1239,51 @@ int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samp
   return RTMI_OK;
 }
 
+int rtmi_resolve_variance(const rtmi_frame *f, const float *d_sum, const float *d_sq, const uint32_t *d_samples, float *d_var,
+                          void *stream) {
+  FrameDev d;
+  const int rc = budget_frame(f, d_sum && d_sq && d_samples && d_var, "null sum, second-moment, sample-count or variance array", &d);
+  if (rc) return rc;
+  HIP_TRY(launch_resolve_variance(d, d_sum, d_sq, d_samples, d_var, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ denoise
+static bool denoise_extent(int height, int width) {
+  return height >= 1 && height <= RTMI_MAX_EXTENT && width >= 1 && width <= RTMI_MAX_EXTENT;
+}
+
+size_t rtmi_denoise_scratch_bytes(int height, int width) {
+  return denoise_extent(height, width) ? denoise_scratch_bytes(height, width) : 0;
+}
+
+int rtmi_denoise(int height, int width, const rtmi_denoise_opts *o, const float *d_color, const rtmi_denoise_guides *g,
+                 float *d_out, float *d_out_variance, void *d_scratch, size_t scratch_bytes, void *stream) {
+  static_assert(sizeof(rtmi_denoise_opts) == 24 && sizeof(rtmi_denoise_guides) == 48, "the denoise structs' sizes");
+  if (!denoise_extent(height, width)) return fail(RTMI_ERR_INVALID, "height and width must be within 1..65535 (RTMI_MAX_EXTENT)");
+  if (!o || !g || !d_color || !d_out || !d_scratch)
+    return fail(RTMI_ERR_INVALID, "null rtmi_denoise_opts, rtmi_denoise_guides, colour, output or scratch");
+  if (o->size != (int32_t)sizeof(rtmi_denoise_opts)) return fail(RTMI_ERR_INVALID, "rtmi_denoise_opts.size does not match this library");
+  if (g->size != (int32_t)sizeof(rtmi_denoise_guides) || g->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_denoise_guides.size does not match this library, or reserved is not 0");
+  if (o->iterations < 1 || o->iterations > 8 || o->normal_squarings < 0 || o->normal_squarings > 8 ||
+      (o->demodulate != 0 && o->demodulate != 1) || !(o->sigma_color > 0.f) || !std::isfinite(o->sigma_color) ||
+      !(o->sigma_depth > 0.f) || !std::isfinite(o->sigma_depth))
+    return fail(RTMI_ERR_INVALID, "rtmi_denoise_opts field out of range (iterations 1..8, normal_squarings 0..8, demodulate 0/1, "
+                                  "finite sigma_color > 0, finite sigma_depth > 0)");
+  if (!g->d_variance || !g->d_normal || !g->d_depth || !g->d_alpha || (o->demodulate && !g->d_albedo))
+    return fail(RTMI_ERR_INVALID, "null guide: variance, normal, depth and alpha are required, albedo with demodulate");
+  if (scratch_bytes < denoise_scratch_bytes(height, width))
+    return fail(RTMI_ERR_INVALID, "scratch_bytes is smaller than rtmi_denoise_scratch_bytes(height, width)");
+  DenoiseCall d{};
+  d.height = height, d.width = width, d.iterations = o->iterations, d.normal_squarings = o->normal_squarings;
+  d.demodulate = o->demodulate, d.sigma_color = o->sigma_color, d.sigma_depth = o->sigma_depth;
+  d.color = d_color, d.variance = g->d_variance, d.albedo = o->demodulate ? g->d_albedo : nullptr, d.normal = g->d_normal;
+  d.depth = g->d_depth, d.alpha = g->d_alpha, d.out = d_out, d.out_variance = d_out_variance, d.scratch = d_scratch;
+  HIP_TRY(launch_denoise(d, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
 int rtmi_render_status(const rtmi_scene *sp, const void *d_scratch, uint64_t *out_rays, void *stream) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null argument");
   const Scene *s = S(sp);

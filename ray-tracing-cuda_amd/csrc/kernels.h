@@ -189,6 +189,19 @@ hipError_t launch_budget_plan(const FrameDev &fr, int min_samples, int max_sampl
 // d_tiles = d_sum / d_samples per work item (0 where there are none), post != 0: then sqrt(clamp(., 0, 1)).
 hipError_t launch_resolve(const FrameDev &fr, const float *d_sum, const uint32_t *d_samples, int post, float *d_tiles,
                           hipStream_t stream);
+// Per-item variance of the mean from the budget sums (rtmi_resolve_variance; include/rtmi.h states the rule), tile-major.
+hipError_t launch_resolve_variance(const FrameDev &fr, const float *d_sum, const float *d_sq, const uint32_t *d_samples,
+                                   float *d_var, hipStream_t stream);
+// The a-trous filter (rtmi_denoise; denoise.hip): row-major whole-frame buffers, every pointer checked by capi.hip.
+struct DenoiseCall {
+  int height, width, iterations, normal_squarings, demodulate;
+  float sigma_color, sigma_depth;
+  const float *color, *variance, *albedo, *normal, *depth, *alpha;  // albedo: null unless demodulate
+  float *out, *out_variance;                                        // out may be color; out_variance nullable
+  void *scratch;                                                    // denoise_scratch_bytes(height, width) bytes
+};
+size_t denoise_scratch_bytes(int height, int width);
+hipError_t launch_denoise(const DenoiseCall &d, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

@@ -1096,4 +1096,37 @@ hipError_t launch_resolve(const FrameDev &fr, const float *d_sum, const uint32_t
   return hipGetLastError();
 }
 
+// The variance of the pixel mean from the raw moments (rtmi_resolve_variance; include/rtmi.h states the rule), one lane per
+// work item and every operation rounded on its own, as budget_plan_kernel's.
+__global__ __launch_bounds__(256) void resolve_variance_kernel(FrameDev fr, const float *__restrict__ sum,
+                                                                const float *__restrict__ sq,
+                                                                const uint32_t *__restrict__ samples, float *__restrict__ var) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= fr.items) return;
+  const uint32_t n = frame_pixel_of_rank(fr, fr.rank, q) >= 0 ? samples[q] : 0u;
+  const float nf = (float)n;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float out = 0.f;
+    if (n == 1u) {
+      const float S = sum[q * 3 + c];
+      out = __fmul_rn(S, S);
+    } else if (n >= 2u) {
+      const float S = sum[q * 3 + c], Q = sq[q * 3 + c];
+      const float cc = fmaxf(__fsub_rn(__fmul_rn(nf, Q), __fmul_rn(S, S)), 0.f);
+      out = __fdiv_rn(cc, __fmul_rn(__fmul_rn(nf, nf), __fsub_rn(nf, 1.0f)));
+    }
+    var[q * 3 + c] = out;
+  }
+}
+hipError_t launch_resolve_variance(const FrameDev &fr, const float *d_sum, const float *d_sq, const uint32_t *d_samples,
+                                   float *d_var, hipStream_t stream) {
+  if (fr.items == 0) return hipSuccess;
+  hipLaunchKernelGGL(resolve_variance_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, fr, d_sum, d_sq,
+                     d_samples, d_var);
+  return hipGetLastError();
+}
+
+#include "denoise_body.h"
+
 }  // namespace rtmi

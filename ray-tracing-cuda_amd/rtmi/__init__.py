@@ -92,6 +92,22 @@ def feature_bufs(albedo=None, normal=None, depth=None, coverage=None):
     return Features(C.sizeof(Features), 0, ptr(albedo), ptr(normal), ptr(depth), ptr(coverage))
 
 
+class DenoiseOpts(C.Structure):
+    """rtmi_denoise_opts of include/rtmi.h."""
+    _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
+
+
+class DenoiseGuides(C.Structure):
+    """rtmi_denoise_guides of include/rtmi.h (row-major, whole-frame guide buffers)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("d_variance", C.c_void_p), ("d_albedo", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_depth", C.c_void_p), ("d_alpha", C.c_void_p)]
+
+
+# rtmi.denoise's defaults (include/rtmi.h names the same figures)
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=1.0, sigma_depth=0.05, normal_squarings=0)
+
+
 TRANSFORM_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p)
 
 _lib = None
@@ -177,6 +193,10 @@ SYMBOLS = [
     ("rtmi_render_features", C.c_int, [C.c_void_p, _frp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(Features), C.c_void_p, C.c_void_p]),
     ("rtmi_resolve_features", C.c_int, [_frp, C.POINTER(Features), C.c_void_p, C.POINTER(Features), C.c_void_p]),
+    ("rtmi_resolve_variance", C.c_int, [_frp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_denoise_scratch_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rtmi_denoise", C.c_int, [C.c_int, C.c_int, C.POINTER(DenoiseOpts), C.c_void_p, C.POINTER(DenoiseGuides), C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 
@@ -314,6 +334,53 @@ def rng_states(seed, n, first=0, device=None):
         _check(lib().rtmi_rng_init_n(C.c_uint64(int(seed) & (2**64 - 1)), C.c_uint64(first), n,
                                      C.c_void_p(out.data_ptr()), stream), "rtmi_rng_init_n")
     return out
+
+
+def denoise(color, variance, normal, depth, alpha, albedo=None, iterations=DENOISE_DEFAULTS["iterations"],
+            sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"],
+            normal_squarings=DENOISE_DEFAULTS["normal_squarings"], demodulate=None, out=None, return_variance=False):
+    """The variance- and feature-guided a-trous filter (rtmi_denoise; the rule is in include/rtmi.h), enqueued on torch's
+    current stream.  Row-major contiguous CUDA float32 tensors on one device: ``color``, ``variance`` (of the pixel MEAN:
+    ``Renderer.resolve_variance``), ``normal`` (the mean normal, not renormalised) and ``albedo`` (H, W, 3); ``depth`` and
+    ``alpha`` (H, W).  Defaults: 5 iterations (steps 1, 2, 4, 8, 16 pixels), ``sigma_color`` 1 (standard errors of the two
+    pixels), ``sigma_depth`` 0.05 (of the pixel's depth), 0 ``normal_squarings`` (the plain cosine of the mean normals, whose
+    lengths are the pixels' coverage: a power of it lets covered neighbours outweigh a silhouette pixel itself).
+    ``demodulate``: filter colour / albedo and multiply back; None means "when albedo is given".  ``out``: an optional
+    (H, W, 3) tensor to write into, which may be ``color`` itself.  The call allocates its own scratch.  Returns the
+    filtered image, or with ``return_variance`` (image, what is left of the variance)."""
+    try:
+        import torch
+    except ImportError:
+        raise RtmiError("color: torch is needed for rtmi_denoise")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dim() == 3 and color.shape[2] == 3):
+        raise RtmiError("color must be a CUDA float32 tensor of shape (H, W, 3): rtmi_denoise has no CPU path")
+    h, w, dev = int(color.shape[0]), int(color.shape[1]), color.device
+    demodulate = (albedo is not None) if demodulate is None else bool(demodulate)
+    if demodulate and albedo is None:
+        raise RtmiError("demodulate needs an albedo")
+    for name, t, shape in (("color", color, (h, w, 3)), ("variance", variance, (h, w, 3)), ("normal", normal, (h, w, 3)),
+                           ("depth", depth, (h, w)), ("alpha", alpha, (h, w)), ("albedo", albedo, (h, w, 3))):
+        if t is not None and not _is_buffer(t, shape, dev, torch.float32):
+            raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape %s on color's device" % (name, shape))
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    elif not _is_buffer(out, (h, w, 3), dev, torch.float32):
+        raise RtmiError("out must be a contiguous CUDA float32 tensor of shape (H, W, 3) on color's device")
+    out_var = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if return_variance else None
+    o = DenoiseOpts(C.sizeof(DenoiseOpts), int(iterations), int(normal_squarings), 1 if demodulate else 0,
+                    float(sigma_color), float(sigma_depth))
+    g = DenoiseGuides(C.sizeof(DenoiseGuides), 0, variance.data_ptr(), albedo.data_ptr() if albedo is not None else None,
+                      normal.data_ptr(), depth.data_ptr(), alpha.data_ptr())
+    L = lib()
+    nbytes = int(L.rtmi_denoise_scratch_bytes(h, w))  # (0 for an extent the call refuses: it says why)
+    # (freed on return, while the call is still queued: the caching allocator hands the block out again in this stream's order)
+    scratch = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(L.rtmi_denoise(h, w, C.byref(o), C.c_void_p(color.data_ptr()), C.byref(g), C.c_void_p(out.data_ptr()),
+                              C.c_void_p(out_var.data_ptr()) if out_var is not None else None,
+                              C.c_void_p(scratch.data_ptr()), nbytes,
+                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rtmi_denoise")
+    return (out, out_var) if return_variance else out
 
 
 class SceneBuilder:
@@ -721,6 +788,47 @@ class Renderer:
                                        C.c_void_p(self.samples.data_ptr()), 1 if post else 0, C.c_void_p(out.data_ptr()),
                                        self._stream()), "rtmi_resolve")
         return out
+
+    def resolve_variance(self):
+        """(items, 3) tile buffer: the variance of each pixel's MEAN from the sums so far (rtmi_resolve_variance; the
+        rule is in include/rtmi.h): 0 where a pixel has no samples and for padding."""
+        self._budget_buffers()
+        out = self.torch.empty((self.items, 3), dtype=self.torch.float32, device=self.device)
+        with self.torch.cuda.device(self.device):
+            _check(self.L.rtmi_resolve_variance(C.byref(self.frame), C.c_void_p(self.sum.data_ptr()),
+                                                C.c_void_p(self.sq.data_ptr()), C.c_void_p(self.samples.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), self._stream()), "rtmi_resolve_variance")
+        return out
+
+    def denoise_inputs(self):
+        """The row-major buffers ``denoise`` filters, as a dict of rtmi.denoise's arguments: color (resolved without
+        post-processing), variance, normal, depth, alpha, albedo."""
+        if self.frame.world_size != 1:
+            raise RtmiError("Renderer.denoise works on a whole frame (world_size 1): gather the resolved colour, variance "
+                            "and feature buffers of all ranks, untile them and call rtmi.denoise")
+        if getattr(self, "sum", None) is None or getattr(self, "albedo", None) is None:
+            raise RtmiError("nothing to denoise: render_budget(features=True) or render_adaptive(features=True) comes first")
+        self.check()
+        feat = self.resolve_features()
+        color, depth = self.untile(self.resolve(post=False), feat.depth)
+        variance, alpha = self.untile(self.resolve_variance(), feat.alpha)
+        three = lambda t: self.untile(t, feat.depth)[0]  # (untile moves a 32-bit buffer too: its own ray counts if given none)
+        return dict(color=color, variance=variance, normal=three(feat.normal), depth=depth, alpha=alpha,
+                    albedo=three(feat.albedo))
+
+    def denoise(self, post=True, **opts):
+        """The denoised row-major (H, W, 3) image of the samples so far, after ``render_budget(features=True)`` or
+        ``render_adaptive(features=True)`` on a whole frame (world_size 1): resolves colour (without post-processing),
+        variance and features, untiles each and calls ``rtmi.denoise`` with ``opts`` (its keyword arguments; the
+        defaults are its own).  ``post``: finish with the render's post-processing, sqrt(clamp(., 0, 1))."""
+        if opts.get("return_variance"):
+            raise RtmiError("Renderer.denoise returns the image alone: call rtmi.denoise on denoise_inputs() for the variance")
+        img = denoise(**self.denoise_inputs(), **opts)
+        if post:
+            with self.torch.cuda.device(self.device):
+                _check(self.L.rtmi_post_process(C.c_void_p(img.data_ptr()), self.frame.height * self.frame.width, 1,
+                                                self._stream()), "rtmi_post_process")
+        return img
 
     def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True, features=False):
         """Plan / render passes until no pixel has a budget left: every pixel gets ``min_spp`` samples, then ``step``
