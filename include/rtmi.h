@@ -136,6 +136,19 @@ int rtmi_camera_get(const rtmi_scene *s, float out[21]);
 /* Install a camera whose frame was computed elsewhere (a Camera constructed on the device):
  * the same 21 floats, is_defocus_camera_ and lens_radius_ (camera.cuh:12-14). */
 int rtmi_camera_set(rtmi_scene *s, const float frame[21], int is_defocus, double lens_radius);
+/* Move the camera of a COMMITTED scene without committing again (added without a version change: a caller detects it by
+ * the symbol).  The arguments are rtmi_camera_set's.  On an uncommitted scene it is rtmi_camera_set.  On a committed one it
+ * replaces the camera in the scene's host record and in the committed scene, which stays committed: no HIP call is made,
+ * nothing is uploaded and no search tree is rebuilt, because the camera lives on the host and every launch copies it by
+ * value into its argument block at enqueue time.  So work enqueued BEFORE the call keeps the camera it was enqueued with
+ * -- rtmi_render / rtmi_render_ex with and without d_scratch, rtmi_render_budget and rtmi_render_features alike -- and
+ * the update needs no synchronisation with it.  rtmi_intersect, rtmi_occluded and rtmi_trace do not read the camera.  The
+ * one thing a commit derives from the camera, whether the render kernel draws lens offsets (is_defocus), is derived again
+ * here.  Like every call that changes a scene, it must not run concurrently with another call on the same scene.
+ * RTMI_ERR_INVALID for a null argument or a non-finite float in frame.
+ * The 21 floats of a look-at camera come from a throw-away scene: rtmi_scene_create, rtmi_camera_pinhole (or _defocus),
+ * rtmi_camera_get, rtmi_scene_destroy, none of which touches the device. */
+int rtmi_camera_update(rtmi_scene *s, const float frame[21], int is_defocus, double lens_radius);
 
 /* Flatten the recorded graph into the device layout and upload it to the
  * current HIP device.  Synchronous.  Replaces the point in Main where
@@ -651,6 +664,73 @@ typedef struct rtmi_denoise_guides { /* row-major, whole frame */
 size_t rtmi_denoise_scratch_bytes(int height, int width);
 int rtmi_denoise(int height, int width, const rtmi_denoise_opts *o, const float *d_color, const rtmi_denoise_guides *g,
                  float *d_out, float *d_out_variance /* nullable */, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------- accumulate --
+ * Temporal accumulation for a camera that moves through a static scene: the frame is blended with the previous frames'
+ * result wherever the same surface point is still visible.  Added without a version change: a caller detects it by the
+ * symbol rtmi_accumulate.  Buffers are rtmi_denoise's: ROW-MAJOR, whole frame; d_color and g->d_variance float[H*W][3],
+ * g->d_normal the MEAN normal, g->d_depth and g->d_alpha float[H*W]; g->d_albedo is not looked at.  The cameras are the 21
+ * floats of rtmi_camera_get: indices 0..2 the position p, 3..5 llc, 6..8 h, 9..11 v; the rest is unused.
+ *
+ * The caller owns two histories of rtmi_history_bytes(height, width) = 48 * H * W bytes, 16-byte aligned, and swaps them
+ * every frame: the call reads d_history_in (written by the previous frame's call, seen from prev_camera) and writes
+ * d_history_out.  Both d_history_in and prev_camera null: the first frame.  A history is opaque, and valid only for the
+ * extent it was written with.  d_out may be d_color and d_out_variance may be g->d_variance; d_history_out may overlap
+ * nothing.  Asynchronous on `stream`; the call shares no device state with any other.
+ *
+ * The rule is stated operation by operation like rtmi_denoise's: every + - * / and sqrt is one operation rounded on its
+ * own (no fused multiply-add), sums of three are (x + y) + z, fmax is maxNum.
+ * Host, in binary64 from the cameras' binary32 values.  This frame's camera: e = (float)(llc - p) per component.  The
+ * previous one: a = h', b = v', c = llc' - p';  bc = b x c, ca = c x a, ab = a x b with
+ * x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0);  det = (a0 bc0 + a1 bc1) + a2 bc2;  R0 = (float)(bc / det),
+ * R1 = (float)(ca / det), R2 = (float)(ab / det) per component.
+ * Device, binary32, pixel (i, j) with inputs C_p, V_p, N_p, z_p and surface_p = alpha_p > 0.  FRESH means C' = C_p,
+ * V' = V_p, L' = 1.  A pixel is fresh when there is no history or when !surface_p (the background has no point to
+ * reproject).  Otherwise:
+ *     xf = ((float)j + 0.5f) / (float)W;   yf = ((float)(H - i) + 0.5f) / (float)H      (the render's pixel centre, quirk g1)
+ *     D = (e + xf * h) + yf * v;   l = sqrt((Dx Dx + Dy Dy) + Dz Dz);   P = p + (D / l) * z_p        per component
+ *     d = P - p';   alpha = (R0x dx + R0y dy) + R0z dz;  beta, gamma likewise with R1, R2;
+ *     ze = sqrt((dx dx + dy dy) + dz dz)
+ *     !(gamma > 0): fresh.   fx = (alpha / gamma) * (float)W - 0.5f;   fy = ((float)H + 0.5f) - (beta / gamma) * (float)H
+ *     !(fx > -1 && fx < (float)W && fy > -1 && fy < (float)H): fresh          (a NaN is fresh too)
+ *     rx = rint(fx), ry = rint(fy) (ties to even);  fabs(fx - rx) <= 1/64 && fabs(fy - ry) <= 1/64:  fx = rx, fy = ry
+ *     j0 = floor(fx), i0 = floor(fy);  tx = fx - (float)j0,  ty = fy - (float)i0
+ *     taps q = (i0 + di, j0 + dj), di the outer loop 0..1, dj the inner; a tap outside the image is skipped
+ *       b = (di ? ty : 1 - ty) * (dj ? tx : 1 - tx)
+ *       taken iff  surface_q  &&  (nx_p nx_q + ny_p ny_q) + nz_p nz_q >= normal_min
+ *                  &&  fabs(z_q - ze) <= depth_tolerance * ze
+ *       in tap order:  sw += b;  sl += b * L_q;  per channel  sc += b * C_q;  sv += b * V_q
+ *     !(sw > 0): fresh.   Ch = sc / sw,  Vh = sv / sw,  Lh = sl / sw
+ *     L' = Lh + 1;  a = fmax(1 / L', min_blend);  o = 1 - a;   C' = o * Ch + a * C_p;   V' = (o * o) * Vh + (a * a) * V_p
+ * where N_q, z_q, C_q, V_q, L_q and surface_q are what the previous call wrote for pixel q.  Outputs: d_out = C',
+ * d_out_variance = V', d_out_length = L' (how many frames the pixel holds; float[H*W]); the history keeps N_p, z_p, C', L',
+ * V' and surface_p.  A fresh pixel writes all of its outputs too.
+ * So with min_blend 0 a camera that has not moved gives the exact per-pixel running mean (the 1/64 snap makes the
+ * reprojection one tap of weight 1, and L the frame count), and (C', V') go into rtmi_denoise as they are: the blend
+ * propagates the variance of two independent estimates.  The mean normal's length is the pixel's coverage, so a
+ * half-covered silhouette pixel fails normal_min 0.8 and starts fresh.  ze and the history's depth are both distances along
+ * unit rays from p', so they compare directly.
+ * Known limits: a defocus camera reprojects as its pinhole; view-dependent materials (Metal, Dielectric) lag behind the
+ * camera, by at most what min_blend allows; there is no demodulation: the history holds what the caller passes.
+ *
+ * Defaults (what rtmi.accumulate of the Python binding passes): normal_min 0.8, depth_tolerance 0.05, min_blend 0.1.
+ * RTMI_ERR_INVALID before any HIP call for: height or width outside 1..RTMI_MAX_EXTENT; a null o, g, d_color, cur_camera,
+ * d_history_out or d_out; a wrong size in either struct or reserved != 0; an option outside its range; a null
+ * g->d_variance, d_normal, d_depth or d_alpha; exactly one of d_history_in and prev_camera null; a history pointer that is
+ * not 16-byte aligned; a non-finite camera float; a det that is 0 or not finite.  rtmi_history_bytes returns 0 for an extent
+ * outside 1..RTMI_MAX_EXTENT. */
+typedef struct rtmi_accumulate_opts {
+  int32_t size;          /* sizeof(rtmi_accumulate_opts) of the caller: must match the library's */
+  int32_t reserved;      /* 0 */
+  float normal_min;      /* finite, -1..1: a history tap is taken only if its mean normal . the pixel's >= this */
+  float depth_tolerance; /* finite, > 0: ... and its depth is within this fraction of the expected depth */
+  float min_blend;       /* 0..1: floor of the current frame's weight; 0 = the exact running mean */
+} rtmi_accumulate_opts;
+size_t rtmi_history_bytes(int height, int width);
+int rtmi_accumulate(int height, int width, const rtmi_accumulate_opts *o, const float *d_color, const rtmi_denoise_guides *g,
+                    const float cur_camera[21], const void *d_history_in, const float prev_camera[21],
+                    void *d_history_out, float *d_out, float *d_out_variance /* nullable */,
+                    float *d_out_length /* nullable */, void *stream);
 
 /* Process-wide DEFAULTS for the same fields (what rtmi_render and a zero field of rtmi_render_opts use).
  * Kept for callers of the first ABI version; prefer rtmi_render_opts.  The RTMI_SPARSE_STRIDE /

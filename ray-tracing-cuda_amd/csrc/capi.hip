@@ -406,6 +406,21 @@ int rtmi_camera_set(rtmi_scene *s, const float f[21], int is_defocus, double len
   S(s)->committed = false;
   return RTMI_OK;
 }
+int rtmi_camera_update(rtmi_scene *s, const float f[21], int is_defocus, double lens_radius) {
+  if (!s || !f) return fail(RTMI_ERR_INVALID, "null argument");
+  if (!all_finite(f, 21)) return fail(RTMI_ERR_INVALID, "non-finite camera float");
+  Scene *sc = S(s);
+  const bool committed = sc->committed;
+  if (int rc = rtmi_camera_set(s, f, is_defocus, lens_radius)) return rc;
+  if (committed) {
+    // The camera is host state only: every launch copies SceneDev by value into its argument block.  What flatten()
+    // derives from it is the F_DEFOCUS bit of the scene's features (the render variant), and nothing else.
+    sc->dev.cam = sc->cam;
+    sc->features = sc->cam.defocus ? sc->features | F_DEFOCUS : sc->features & ~(uint32_t)F_DEFOCUS;
+    sc->committed = true;
+  }
+  return RTMI_OK;
+}
 int rtmi_camera_get(const rtmi_scene *s, float out[21]) {
   if (!s || !out || !S(s)->has_camera) return fail(RTMI_ERR_INVALID, "scene has no camera");
   const CameraDev &c = S(s)->cam;
@@ -1281,6 +1296,63 @@ int rtmi_denoise(int height, int width, const rtmi_denoise_opts *o, const float 
   d.color = d_color, d.variance = g->d_variance, d.albedo = o->demodulate ? g->d_albedo : nullptr, d.normal = g->d_normal;
   d.depth = g->d_depth, d.alpha = g->d_alpha, d.out = d_out, d.out_variance = d_out_variance, d.scratch = d_scratch;
   HIP_TRY(launch_denoise(d, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ accumulate
+size_t rtmi_history_bytes(int height, int width) { return denoise_extent(height, width) ? history_bytes(height, width) : 0; }
+
+int rtmi_accumulate(int height, int width, const rtmi_accumulate_opts *o, const float *d_color, const rtmi_denoise_guides *g,
+                    const float cur_camera[21], const void *d_history_in, const float prev_camera[21], void *d_history_out,
+                    float *d_out, float *d_out_variance, float *d_out_length, void *stream) {
+  static_assert(sizeof(rtmi_accumulate_opts) == 20, "rtmi_accumulate_opts is 20 bytes");
+  if (!denoise_extent(height, width)) return fail(RTMI_ERR_INVALID, "height and width must be within 1..65535 (RTMI_MAX_EXTENT)");
+  if (!o || !g || !d_color || !cur_camera || !d_history_out || !d_out)
+    return fail(RTMI_ERR_INVALID, "null rtmi_accumulate_opts, rtmi_denoise_guides, colour, camera, output history or output");
+  if (o->size != (int32_t)sizeof(rtmi_accumulate_opts) || o->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_accumulate_opts.size does not match this library, or reserved is not 0");
+  if (g->size != (int32_t)sizeof(rtmi_denoise_guides) || g->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_denoise_guides.size does not match this library, or reserved is not 0");
+  if (!std::isfinite(o->normal_min) || o->normal_min < -1.f || o->normal_min > 1.f || !std::isfinite(o->depth_tolerance) ||
+      !(o->depth_tolerance > 0.f) || !(o->min_blend >= 0.f && o->min_blend <= 1.f))
+    return fail(RTMI_ERR_INVALID, "rtmi_accumulate_opts field out of range (finite normal_min in -1..1, finite depth_tolerance > 0, "
+                                  "min_blend in 0..1)");
+  if (!g->d_variance || !g->d_normal || !g->d_depth || !g->d_alpha)
+    return fail(RTMI_ERR_INVALID, "null guide: variance, normal, depth and alpha are required");
+  if ((d_history_in == nullptr) != (prev_camera == nullptr))
+    return fail(RTMI_ERR_INVALID, "d_history_in and prev_camera go together: both null (the first frame) or neither");
+  if (((uintptr_t)d_history_in | (uintptr_t)d_history_out) & 15u)
+    return fail(RTMI_ERR_INVALID, "a history must be 16-byte aligned");
+  if (!all_finite(cur_camera, 21) || (prev_camera && !all_finite(prev_camera, 21)))
+    return fail(RTMI_ERR_INVALID, "non-finite camera float");
+  AccumulateCall c{};
+  c.height = height, c.width = width;
+  c.normal_min = o->normal_min, c.depth_tolerance = o->depth_tolerance, c.min_blend = o->min_blend;
+  for (int k = 0; k < 3; k++) {
+    c.p[k] = cur_camera[k], c.h[k] = cur_camera[6 + k], c.v[k] = cur_camera[9 + k];
+    c.e[k] = (float)((double)cur_camera[3 + k] - (double)cur_camera[k]);
+  }
+  if (prev_camera) {
+    // the inverse of the matrix whose columns are a = h', b = v', c = llc' - p', in binary64: its rows are b x c, c x a and
+    // a x b over the determinant
+    double a[3], b[3], cc[3];
+    for (int k = 0; k < 3; k++)
+      a[k] = prev_camera[6 + k], b[k] = prev_camera[9 + k], cc[k] = (double)prev_camera[3 + k] - (double)prev_camera[k];
+    const auto cross = [](const double *x, const double *y, double *out) {
+      out[0] = x[1] * y[2] - x[2] * y[1], out[1] = x[2] * y[0] - x[0] * y[2], out[2] = x[0] * y[1] - x[1] * y[0];
+    };
+    double rows[3][3];
+    cross(b, cc, rows[0]), cross(cc, a, rows[1]), cross(a, b, rows[2]);
+    const double det = (a[0] * rows[0][0] + a[1] * rows[0][1]) + a[2] * rows[0][2];
+    if (det == 0.0 || !std::isfinite(det)) return fail(RTMI_ERR_INVALID, "prev_camera is singular: its h, v and llc - p span no volume");
+    for (int r = 0; r < 3; r++)
+      for (int k = 0; k < 3; k++) c.r[r][k] = (float)(rows[r][k] / det);
+    for (int k = 0; k < 3; k++) c.prev_p[k] = prev_camera[k];
+  }
+  c.color = d_color, c.variance = g->d_variance, c.normal = g->d_normal, c.depth = g->d_depth, c.alpha = g->d_alpha;
+  c.history_in = d_history_in, c.history_out = d_history_out;
+  c.out = d_out, c.out_variance = d_out_variance, c.out_length = d_out_length;
+  HIP_TRY(launch_accumulate(c, (hipStream_t)stream));
   return RTMI_OK;
 }
 

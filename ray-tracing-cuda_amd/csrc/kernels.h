@@ -202,6 +202,20 @@ struct DenoiseCall {
 };
 size_t denoise_scratch_bytes(int height, int width);
 hipError_t launch_denoise(const DenoiseCall &d, hipStream_t stream);
+// Temporal accumulation (rtmi_accumulate; accumulate_body.h): row-major whole-frame buffers, every pointer checked by
+// capi.hip, which also forms the camera terms in binary64 and rounds them.
+struct AccumulateCall {
+  int height, width;
+  float normal_min, depth_tolerance, min_blend;
+  float e[3], h[3], v[3], p[3];                          // this frame's camera: llc - p, horizontal, vertical, position
+  float prev_p[3], r[3][3];                              // the history's: position, the inverse of [h' v' llc' - p'] by rows
+  const float *color, *variance, *normal, *depth, *alpha;
+  const void *history_in;                                // null: the first frame
+  void *history_out;                                     // history_bytes(height, width) bytes, 16-byte aligned
+  float *out, *out_variance, *out_length;                // out may be color, out_variance may be variance; the last two nullable
+};
+size_t history_bytes(int height, int width);
+hipError_t launch_accumulate(const AccumulateCall &c, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

@@ -1128,5 +1128,6 @@ hipError_t launch_resolve_variance(const FrameDev &fr, const float *d_sum, const
 }
 
 #include "denoise_body.h"
+#include "accumulate_body.h"
 
 }  // namespace rtmi

@@ -108,6 +108,16 @@ class DenoiseGuides(C.Structure):
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=1.0, sigma_depth=0.05, normal_squarings=0)
 
 
+class AccumulateOpts(C.Structure):
+    """rtmi_accumulate_opts of include/rtmi.h."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("normal_min", C.c_float), ("depth_tolerance", C.c_float),
+                ("min_blend", C.c_float)]
+
+
+# rtmi.accumulate's defaults (include/rtmi.h names the same figures)
+ACCUMULATE_DEFAULTS = dict(normal_min=0.8, depth_tolerance=0.05, min_blend=0.1)
+
+
 TRANSFORM_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p)
 
 _lib = None
@@ -197,6 +207,10 @@ SYMBOLS = [
     ("rtmi_denoise_scratch_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("rtmi_denoise", C.c_int, [C.c_int, C.c_int, C.POINTER(DenoiseOpts), C.c_void_p, C.POINTER(DenoiseGuides), C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rtmi_camera_update", C.c_int, [C.c_void_p, _fp, C.c_int, C.c_double]),
+    ("rtmi_history_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("rtmi_accumulate", C.c_int, [C.c_int, C.c_int, C.POINTER(AccumulateOpts), C.c_void_p, C.POINTER(DenoiseGuides), _fp,
+                                  C.c_void_p, _fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -383,6 +397,109 @@ def denoise(color, variance, normal, depth, alpha, albedo=None, iterations=DENOI
     return (out, out_var) if return_variance else out
 
 
+def _camera21(camera, name):
+    a = np.ascontiguousarray(np.asarray(camera, dtype=np.float32).reshape(-1))
+    if a.size != 21:
+        raise RtmiError("%s must hold the 21 floats of rtmi_camera_get" % name)
+    return a
+
+
+def accumulate(color, variance, normal, depth, alpha, camera, history=None, prev_camera=None, out_history=None, **opts):
+    """Temporal accumulation (rtmi_accumulate; the rule is in include/rtmi.h), enqueued on torch's current stream.  Row-major
+    contiguous CUDA float32 tensors on one device, as for ``denoise``: ``color``, ``variance`` and ``normal`` (H, W, 3),
+    ``depth`` and ``alpha`` (H, W).  ``camera``: this frame's, the 21 floats of ``SceneBuilder.camera_get`` (any shape).
+    ``history`` and ``prev_camera``: what the previous call returned as its history, and the camera of that frame; both None
+    for the first frame.  ``out_history``: an optional uint8 tensor of ``rtmi_history_bytes(H, W)`` bytes to write the new
+    history into (never ``history`` itself).  ``opts``: normal_min, depth_tolerance, min_blend (ACCUMULATE_DEFAULTS).
+    Returns (color, variance, length, history): the accumulated image and its variance (H, W, 3), the number of frames
+    each pixel holds (H, W), and the new history, a uint8 tensor that only the next call can read."""
+    try:
+        import torch
+    except ImportError:
+        raise RtmiError("color: torch is needed for rtmi_accumulate")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dim() == 3 and color.shape[2] == 3):
+        raise RtmiError("color must be a CUDA float32 tensor of shape (H, W, 3): rtmi_accumulate has no CPU path")
+    unknown = set(opts) - set(ACCUMULATE_DEFAULTS)
+    if unknown:
+        raise RtmiError("rtmi.accumulate has no option %s" % ", ".join(sorted(unknown)))
+    opts = dict(ACCUMULATE_DEFAULTS, **opts)
+    h, w, dev = int(color.shape[0]), int(color.shape[1]), color.device
+    for name, t, shape in (("color", color, (h, w, 3)), ("variance", variance, (h, w, 3)), ("normal", normal, (h, w, 3)),
+                           ("depth", depth, (h, w)), ("alpha", alpha, (h, w))):
+        if not _is_buffer(t, shape, dev, torch.float32):
+            raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape %s on color's device" % (name, shape))
+    if (history is None) != (prev_camera is None):
+        raise RtmiError("history and prev_camera go together: both None (the first frame) or neither")
+    L = lib()
+    nbytes = int(L.rtmi_history_bytes(h, w))  # (0 for an extent the call refuses: it says why)
+    for name, t in (("history", history), ("out_history", out_history)):
+        if t is not None and not _is_buffer(t, (nbytes,), dev, torch.uint8):
+            raise RtmiError("%s must be a contiguous CUDA uint8 tensor of rtmi_history_bytes(H, W) = %d bytes on color's device"
+                            % (name, nbytes))
+    if out_history is None:
+        out_history = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)[:nbytes]
+    elif history is not None and out_history.data_ptr() == history.data_ptr():
+        raise RtmiError("out_history must not be history: the call reads one while it writes the other")
+    cur = _camera21(camera, "camera")
+    prev = _camera21(prev_camera, "prev_camera") if prev_camera is not None else None
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    out_var = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    length = torch.empty((h, w), dtype=torch.float32, device=dev)
+    o = AccumulateOpts(C.sizeof(AccumulateOpts), 0, float(opts["normal_min"]), float(opts["depth_tolerance"]),
+                       float(opts["min_blend"]))
+    g = DenoiseGuides(C.sizeof(DenoiseGuides), 0, variance.data_ptr(), None, normal.data_ptr(), depth.data_ptr(), alpha.data_ptr())
+    with torch.cuda.device(dev):
+        _check(L.rtmi_accumulate(h, w, C.byref(o), C.c_void_p(color.data_ptr()), C.byref(g), cur.ctypes.data_as(_fp),
+                                 C.c_void_p(history.data_ptr()) if history is not None else None,
+                                 prev.ctypes.data_as(_fp) if prev is not None else None, C.c_void_p(out_history.data_ptr()),
+                                 C.c_void_p(out.data_ptr()), C.c_void_p(out_var.data_ptr()), C.c_void_p(length.data_ptr()),
+                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rtmi_accumulate")
+    return out, out_var, length, out_history
+
+
+class Accumulator:
+    """A sequence's accumulation state: the two histories ``rtmi.accumulate`` swaps between, and the previous frame's camera.
+    ``height``, ``width``: the frames' extent; ``device``: a CUDA device (default: torch's current one); ``opts``:
+    rtmi.accumulate's options, for every step."""
+
+    def __init__(self, height, width, device=None, **opts):
+        import torch
+        unknown = set(opts) - set(ACCUMULATE_DEFAULTS)
+        if unknown:
+            raise RtmiError("rtmi.accumulate has no option %s" % ", ".join(sorted(unknown)))
+        self.height, self.width, self.opts = int(height), int(width), opts
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        nbytes = int(lib().rtmi_history_bytes(self.height, self.width))
+        if nbytes == 0:
+            raise RtmiError("height and width must be within 1..65535 (RTMI_MAX_EXTENT)")
+        self._histories = [torch.empty((nbytes,), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next step is a first frame."""
+        self.frames = 0
+        self._prev_camera = None
+        return self
+
+    def step(self, color, variance, normal, depth, alpha, camera):
+        """Accumulate one frame seen from ``camera`` (rtmi.accumulate's arguments) and swap the histories.  Returns
+        (color, variance, length)."""
+        cur = _camera21(camera, "camera").copy()
+        first = self._prev_camera is None
+        out, var, length, _ = accumulate(color, variance, normal, depth, alpha, cur,
+                                         history=None if first else self._histories[0], prev_camera=self._prev_camera,
+                                         out_history=self._histories[1], **self.opts)
+        self._histories.reverse()
+        self._prev_camera = cur
+        self.frames += 1
+        return out, var, length
+
+    @property
+    def history(self):
+        """The history the last step wrote (what the next one reads)."""
+        return self._histories[0]
+
+
 class SceneBuilder:
     """Builder protocol of rtmi/scenes.py over the C ABI's scene recorder.
 
@@ -485,6 +602,27 @@ class SceneBuilder:
         out = np.zeros(21, dtype=np.float32)
         _check(self.L.rtmi_camera_get(self.h, out.ctypes.data_as(_fp)), "rtmi_camera_get")
         return out.reshape(7, 3)
+
+    def camera_update(self, frame21, defocus=False, lens_radius=-1.0):
+        """Move the camera (rtmi_camera_update): ``frame21`` is the 21 floats of ``camera_get``, any shape.  A committed
+        scene stays committed, and nothing is uploaded; renders already enqueued keep the camera they were enqueued with."""
+        f = _camera21(frame21, "frame21")
+        _check(self.L.rtmi_camera_update(self.h, f.ctypes.data_as(_fp), 1 if defocus else 0, float(lens_radius)),
+               "rtmi_camera_update")
+        return self
+
+    def camera_look(self, pos, look_at, up, fov, aspect):
+        """``camera_update`` to a pinhole look-at camera (``camera_pinhole``'s arguments), whose 21 floats a throw-away
+        scene makes: no device work."""
+        tmp = C.c_void_p(self.L.rtmi_scene_create())
+        try:
+            _check(self.L.rtmi_camera_pinhole(tmp, _f(pos)[1], _f(look_at)[1], _f(up)[1], float(fov), float(aspect)),
+                   "rtmi_camera_pinhole")
+            f = np.zeros(21, dtype=np.float32)
+            _check(self.L.rtmi_camera_get(tmp, f.ctypes.data_as(_fp)), "rtmi_camera_get")
+        finally:
+            self.L.rtmi_scene_destroy(tmp)
+        return self.camera_update(f)
 
     def random_float(self, mn, mx):
         return np.float32(self.L.rtmi_rng_host_random_float(C.c_float(float(np.float32(mn))),
@@ -829,6 +967,30 @@ class Renderer:
                 _check(self.L.rtmi_post_process(C.c_void_p(img.data_ptr()), self.frame.height * self.frame.width, 1,
                                                 self._stream()), "rtmi_post_process")
         return img
+
+    def new_frame(self):
+        """Start the next frame of a sequence: zero ``sum``, ``sq``, ``samples``, ``budget_rays``, ``budget_abandoned`` and the
+        four feature sums on torch's current stream.  The RNG states go on, so every frame draws new samples."""
+        self._budget_buffers()
+        self._feature_buffers()
+        with self.torch.cuda.device(self.device):
+            for t in (self.sum, self.sq, self.samples, self.budget_rays, self.budget_abandoned, self.albedo, self.normal,
+                      self.depth, self.coverage):
+                t.zero_()
+        return self
+
+    def accumulate(self, acc):
+        """``denoise_inputs()`` of the frame so far, accumulated into ``acc`` (an ``Accumulator`` of this frame's extent) as
+        seen from the scene's present camera: the same dict with ``color`` and ``variance`` replaced by the accumulated
+        ones, so a sequence is ``scene.camera_look(...)``, ``new_frame()``, ``render_budget(..., features=True)``,
+        ``rtmi.denoise(**R.accumulate(acc))`` per frame."""
+        if self.frame.world_size != 1:
+            raise RtmiError("Renderer.denoise works on a whole frame (world_size 1): gather the resolved colour, variance "
+                            "and feature buffers of all ranks, untile them and call rtmi.denoise")
+        buf = self.denoise_inputs()
+        color, variance, _ = acc.step(buf["color"], buf["variance"], buf["normal"], buf["depth"], buf["alpha"],
+                                      camera=self.scene.camera_get())
+        return dict(buf, color=color, variance=variance)
 
     def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True, features=False):
         """Plan / render passes until no pixel has a budget left: every pixel gets ``min_spp`` samples, then ``step``
