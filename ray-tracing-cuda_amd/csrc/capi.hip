@@ -462,7 +462,8 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   if ((rc = upload(s, s->spheres, &d.spheres))) return rc;
   if ((rc = upload(s, s->tris, &d.tris))) return rc;
   if ((rc = upload(s, s->pair_boxes, &d.pair_boxes))) return rc;
-  if ((rc = upload(s, s->pair_pts, &d.pair_pts))) return rc;
+  // (the staging's source: a list beyond kLdsPairs is never staged and gathers from `tris`)
+  if ((int)s->pair_pts.size() <= kLdsPairs && (rc = upload(s, s->tri_pts, &d.tri_pts))) return rc;
   if ((rc = upload(s, s->tri_nrm, &d.tri_nrm))) return rc;
   if ((rc = upload(s, s->sph_groups, &d.sph_groups))) return rc;
   if ((rc = upload(s, s->sph_members, &d.sph_members))) return rc;
@@ -556,6 +557,37 @@ int64_t rtmi_scene_bytes_per_ray(const rtmi_scene *sp) {
   Scene tmp;
   if (int rc = flattened(sp, &tmp)) return rc;
   return tmp.bytes_per_ray;
+}
+
+// Diagnostics for the tests (host only; like rtmi_debug_wave_stats not declared in rtmi.h, the binding asks for them
+// by name).  The culled list scan's records as flatten() forms them: returns the number of pairs; fills, for
+// the first cap_pairs of them, two TriPts (12 words each) and two HotTri (16 words each) per pair and the pair's four
+// corners (12 floats; a lone Triangle's fourth repeats its third).  Any output may be null.
+int64_t rtmi_debug_list_records(const rtmi_scene *sp, int64_t cap_pairs, uint32_t *tri_pts, uint32_t *hot_tris, float *corners) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
+  const int64_t n = (int64_t)tmp.pair_pts.size();
+  for (int64_t i = 0; i < n && i < cap_pairs; i++) {
+    if (tri_pts) memcpy(tri_pts + 24 * i, &tmp.tri_pts[2 * i], 2 * sizeof(TriPts));
+    if (hot_tris) memcpy(hot_tris + 32 * i, &tmp.tris[2 * i], 2 * sizeof(HotTri));
+    if (corners) memcpy(corners + 12 * i, tmp.pair_pts[i].p0, 12 * sizeof(float));
+  }
+  return n;
+}
+
+// Diagnostic (as above): bytes of dynamic LDS one workgroup of `threads` lanes asks for when this scene is rendered at
+// max_depth (kernels.hip: make_cfg).  A compute unit has 160 KiB.
+int64_t rtmi_debug_render_lds_bytes(const rtmi_scene *sp, int max_depth, int threads) {
+  if (!sp || max_depth < 0 || threads < 64 || threads % 64) return fail(RTMI_ERR_INVALID, "bad arguments");
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
+  SceneDev d{};
+  d.n_pairs = (int)tmp.pair_pts.size(), d.n_mats = (int)tmp.mat_recs.size(), d.n_nodes = (int)tmp.nodes.size();
+  d.n_leaf_paths = (int)tmp.leaf_paths.size(), d.n_sph_groups = (int)tmp.sph_groups.size();
+  FrameDev fr{};
+  fr.max_depth = max_depth;
+  return (int64_t)render_lds_bytes(pick_variant(tmp.features), d, fr, threads);
 }
 
 // ------------------------------------------------------------------ frame
@@ -1017,7 +1049,7 @@ static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uin
   //   [4..32]   -DRTMI_STATS wave step counts and cycles            zeroed (per launch)
   //   [33] [34] -DRTMI_CHECK_MARGINS queries re-done, disagreements kept after a first pass the frame keeps
   //   [35] [36] planned chains: SIMD arrival, take-over cursor      zeroed (per launch)
-  //   [37..39]  unused                                              zeroed
+  //   [37..39]  -DRTMI_STATS flushes of the culled scan by n_now    zeroed (per launch)
   // So a resumed frame reports in [2], [33] and [34] over both launches.  Otherwise every word is zeroed: a discarded
   // probe's samples are not in the image.
   if (p.resume) {

@@ -60,6 +60,27 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 }
 #endif
 
+// One triangle of the culled list scan by its record index (2 * pair + which): base point and the two edges.  Staged
+// lists read the 48-byte TriPts record from LDS; longer ones gather the same words from the HotTri of that index, which
+// begins with them (scene_dev.h).  Returns whether the triangle is there: a lone Triangle has no second one.
+template <uint32_t M>
+__device__ __forceinline__ bool load_tri_pts(const SceneDev &sc, const float4 *s_tris, int rec, int which, V3 &p0, V3 &e1, V3 &e2) {
+  float4 qa, qb, qc;
+  bool present;
+  if ((M & PIN_LDS_TABLES) || s_tris != nullptr) {  // (wave-uniform) staged in LDS
+    const float4 *pp = s_tris + (size_t)rec * 3;
+    qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2);
+    present = !(__float_as_int(qc.y) & TRIPTS_ABSENT);
+  } else {  // a list too long for the staging: per-lane gather of 64 bytes (L1 / L2 resident)
+    const float4 *pp = reinterpret_cast<const float4 *>(sc.tris + rec);
+    qa = load_global<float4>(pp), qb = load_global<float4>(pp + 1), qc = load_global<float4>(pp + 2);
+    const float4 qd = load_global<float4>(pp + 3);  // mat, flags
+    present = which == 0 || (__float_as_int(qd.y) & TRI_SECOND);
+  }
+  p0 = mk(qa.x, qa.y, qa.z), e1 = mk(qa.w, qb.x, qb.y), e2 = mk(qb.z, qb.w, qc.x);
+  return present;
+}
+
 // ================================================================== closest hit
 // HitableList::Hit (hitable_list.cu:7-25) over the flattened world.  A nested
 // Parallelepiped list is equivalent to its six parallelograms inlined at its
@@ -78,7 +99,7 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 // M (kernels.h): the run-time modes the caller's launch has pinned at compile time; 0 pins none.
 template <uint32_t F, bool OCC = false, uint32_t M = 0>
 __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_nodes, int lds_nodes, const int *s_paths,
-                                           int lds_paths, const float4 *s_pairs, int *ll, uint16_t *cands, int *wl,
+                                           int lds_paths, const float4 *s_tris, int *ll, uint16_t *cands, int *wl,
                                            unsigned long long *overflow, V3 o, V3 d, bool live, bool count_work
 #ifdef RTMI_STATS
                                            , MeshStats &st
@@ -111,8 +132,8 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   const bool det_safe = (M & PIN_DET_SAFE) || sc.det_safe != 0;  // (a kernel argument: the branch on it waits for no vector result)
   // the ray as the culled list scan wants it: 1/d (the hardware reciprocal will do: the test is conservative by
   // a margin of 1e-5, not 1e-7), and -(o +- delta)/d per axis, delta = the distance slack of the mesh search
-  // the culled list scan is on when the wave has its task region (ll) and the scene has pair records; the pairs'
-  // corners come from LDS when the list was short enough to be staged (s_pairs), else from global memory
+  // the culled list scan is on when the wave has its task region (ll) and the scene has pair records; the triangles'
+  // records come from LDS when the list was short enough to be staged (s_tris), else from sc.tris in global memory
   const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
   if ((F & F_TRIS) && cull_list) {
@@ -149,7 +170,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
       // (one s_load_dwordx8, wave-uniform) against the lane's ray: a slab test, 27 instructions
       // instead of the 140 of two triangle tests, builds a bit mask of the pairs this ray comes near;
       // (2) while any lane has bits left, each lane takes ITS next pair -- a different one per lane,
-      // corners gathered from LDS -- and runs the reference's two triangle tests on it.  A lane visits
+      // records gathered from LDS -- and runs the reference's two triangle tests on it.  A lane visits
       // its pairs in list order with its own running t_to, so acceptance and ties are as in the full
       // scan; a pair outside the mask cannot pass the triangle test (the bounds carry the same padding
       // and distance slack as the mesh search boxes).
@@ -212,24 +233,14 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
           if (mask != 0u) {
             const int bit = __builtin_ctz(mask);
             mask &= mask - 1u;
-            const size_t pidx = (size_t)(pair0 + c0 + bit) * 4;
-            float4 qa, qb, qc, qd;
-            if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) staged in LDS
-              const float4 *pp = s_pairs + pidx;
-              qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2), qd = load_lds<float4>(pp + 3);
-            } else {
-              const float4 *pp = reinterpret_cast<const float4 *>(sc.pair_pts) + pidx;
-              qa = load_global<float4>(pp), qb = load_global<float4>(pp + 1), qc = load_global<float4>(pp + 2), qd = load_global<float4>(pp + 3);
-            }
-            const V3 p0 = mk(qa.x, qa.y, qa.z), p1 = mk(qa.w, qb.x, qb.y), p2 = mk(qb.z, qb.w, qc.x), p3 = mk(qc.y, qc.z, qc.w);
+            const int rec = 2 * (pair0 + c0 + bit);  // the pair's two records: edges formed on the host (scene.hip: push_pair)
+            V3 p0, e1, e2, p1, e1b, e2b;
+            (void)load_tri_pts<M>(sc, s_tris, rec, 0, p0, e1, e2);
+            const bool second = load_tri_pts<M>(sc, s_tris, rec + 1, 1, p1, e1b, e2b);
             float ta = 0.f, ua = 0.f, va = 0.f, tb = 0.f, ub = 0.f, vb = 0.f;
-            const V3 e1 = p1 - p0, e2 = p2 - p0;
             const bool hit_a = tri_test_flat<T>(p0, e1, e2, cross3(d, e2), o, d, t_to, ta, ua, va, det_safe);
             bool hit_b = false;
-            if (__float_as_int(qd.x) & PAIR_SECOND) {
-              const V3 e1b = p2 - p1, e2b = p3 - p1;
-              hit_b = tri_test_flat<T>(p1, e1b, e2b, cross3(d, e2b), o, d, t_to, tb, ub, vb, det_safe) && !hit_a;  // parallelogram.cu:33
-            }
+            if (second) hit_b = tri_test_flat<T>(p1, e1b, e2b, cross3(d, e2b), o, d, t_to, tb, ub, vb, det_safe) && !hit_a;  // parallelogram.cu:33
             const float t = hit_a ? ta : tb;
             const bool acc = (hit_a || hit_b) && (!ok || (T)t < t_to);
             ok = ok || acc;
@@ -247,8 +258,11 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
           // ---- the (remaining) candidates of all 64 rays are worked off by all 64 lanes.  A ray comes near 2.2 pairs on
           // average but the unluckiest of 64 near 6, and a lane-by-lane loop runs as long as that one.  So
           // (a) every lane writes its ray and one task per candidate pair to LDS (offsets: prefix sum of the
-          // candidate counts by bit planes), (b) lane l takes task l, l + 64, ...: reads that ray and that
-          // pair's corners and runs BOTH triangle tests against the ray's t_to at the start of the chunk,
+          // candidate counts by bit planes), (b) the tasks' triangles are spread over the lanes, two per task: lane l
+          // takes triangle l & 1 of task l >> 1, then of task (l + 64) >> 1, ...: reads that ray and that triangle's
+          // record (base point and edges, subtracted on the host) and runs ONE triangle test against the ray's t_to at
+          // the start of the chunk -- a ray has two candidate pairs or so, so a wave's tasks just overflow 64 and a
+          // round of pair tests would run one-eighth full; a lone Triangle's absent second answers "miss" untested,
           // (c) every lane folds the results of its own candidates in list order with its running t_to:
           // a test that passed against the older, larger t_to passes now iff its t <= the current one,
           // which is the only place t_to enters the test (utils.cu:74).
@@ -274,15 +288,16 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             const int lo_t = __builtin_amdgcn_readlane(base, __builtin_ctzll(__builtin_amdgcn_ballot_w64(todo)));
             const bool now = todo && base + cnt - lo_t <= kListTasks(F);
             const int n_now = __builtin_amdgcn_readlane(base + cnt, 63 - __builtin_clzll(__builtin_amdgcn_ballot_w64(now))) - lo_t;
+            RTMI_STAT(st.nnow_hist[(n_now - 1) >> 5 < 5 ? (n_now - 1) >> 5 : 5]++;)
             if (now) {  // (a)
               int k = base - lo_t;
               for (uint32_t m = mask; m != 0u; m &= m - 1u) tasks[k++] = (lane << 5) | __builtin_ctz(m);
             }
             wave_lds_fence();
-            for (int t0 = 0; t0 < n_now; t0 += 64) {  // (b)
-              const int ti = t0 + lane;
-              if (ti < n_now) {
-                const int w = tasks[ti];
+            for (int t0 = 0; t0 < 2 * n_now; t0 += 64) {  // (b)
+              const int ti = t0 + lane;  // triangle `which` of pair task ti >> 1
+              if (ti < 2 * n_now) {
+                const int w = tasks[ti >> 1], which = ti & 1;
                 const int *orr = ll + (w >> 5) * 8;
                 const float4 r0 = *reinterpret_cast<const float4 *>(orr), r1 = *reinterpret_cast<const float4 *>(orr + 4);
                 T t0_to;
@@ -292,30 +307,14 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                   t0_to = (T)r0.w;
                 }
                 const V3 ro = mk(r0.x, r0.y, r0.z), rd = mk(r1.x, r1.y, r1.z);
-                const size_t pidx = (size_t)(pair0 + c0 + (w & 31)) * 4;
-                float4 qa, qb, qc, qd;
-                if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) staged in LDS
-                  const float4 *pp = s_pairs + pidx;
-                  qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2), qd = load_lds<float4>(pp + 3);
-                } else {  // a list too long for the staging: per-lane gather of 64 bytes (L1 / L2 resident)
-                  const float4 *pp = reinterpret_cast<const float4 *>(sc.pair_pts) + pidx;
-                  qa = load_global<float4>(pp), qb = load_global<float4>(pp + 1), qc = load_global<float4>(pp + 2), qd = load_global<float4>(pp + 3);
-                }
-                const V3 p0 = mk(qa.x, qa.y, qa.z), p1 = mk(qa.w, qb.x, qb.y), p2 = mk(qb.z, qb.w, qc.x), p3 = mk(qc.y, qc.z, qc.w);
-                float ta = 0.f, ua = 0.f, va = 0.f, tb = 0.f, ub = 0.f, vb = 0.f;
-                const V3 e1 = p1 - p0, e2 = p2 - p0;  // utils.cu:54-55, the subtractions scene.hip: make_tri does
-                const bool hit_a = tri_test_flat<T>(p0, e1, e2, cross3(rd, e2), ro, rd, t0_to, ta, ua, va, det_safe);
-                bool hit_b = false;
-                if (__float_as_int(qd.x) & PAIR_SECOND) {
-                  const V3 e1b = p2 - p1, e2b = p3 - p1;
-                  hit_b = tri_test_flat<T>(p1, e1b, e2b, cross3(rd, e2b), ro, rd, t0_to, tb, ub, vb, det_safe);
-                }
-                int *res = results + ti * RW;
-                res[0] = hit_a ? __float_as_int(ta) : (int)0xffffffff;  // (a NaN pattern no t can have)
-                res[1] = hit_b ? __float_as_int(tb) : (int)0xffffffff;
-                if (F & F_TEX) {
-                  res[2] = __float_as_int(ua), res[3] = __float_as_int(va), res[4] = __float_as_int(ub), res[5] = __float_as_int(vb);
-                }
+                V3 p0, e1, e2;  // utils.cu:54-55: the edges as scene.hip: make_tri subtracted them
+                const bool present = load_tri_pts<M>(sc, s_tris, 2 * (pair0 + c0 + (w & 31)) + which, which, p0, e1, e2);
+                float tt = 0.f, uu = 0.f, vv = 0.f;
+                bool hit = false;  // (a lone Triangle's second record: the miss pattern, untested)
+                if (present) hit = tri_test_flat<T>(p0, e1, e2, cross3(rd, e2), ro, rd, t0_to, tt, uu, vv, det_safe);
+                int *res = results + (ti >> 1) * RW;
+                res[which] = hit ? __float_as_int(tt) : (int)0xffffffff;  // (a NaN pattern no t can have)
+                if (F & F_TEX) res[2 + 2 * which] = __float_as_int(uu), res[3 + 2 * which] = __float_as_int(vv);
               }
             }
             wave_lds_fence();

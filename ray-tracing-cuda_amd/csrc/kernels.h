@@ -92,6 +92,8 @@ uint32_t fast_path_mode(const FastPathFacts &f);
 // The facts that are known before the launch shape is (scene, frame, switch); the plan adds the lane stride and each
 // launch's last four.
 FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled);
+// Dynamic LDS of one workgroup of a render launch (host arithmetic only: the counts of `sc`, fr.max_depth).
+size_t render_lds_bytes(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads);
 // What the scheduler's probe pass leaves for the real pass (device pointers, all optional).
 struct SchedPlan {
   const uint32_t *tile_order = nullptr;    // the queue's order per quarter tile (launch_quarter_order)

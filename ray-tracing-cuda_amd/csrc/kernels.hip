@@ -619,7 +619,7 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   const bool cull = (variant & F_TRIS) && sc.n_pairs >= kCullMinPairs && !plain_list_scan();
   const bool staged = cull && sc.n_pairs <= kLdsPairs;
   lc.pairs_off = staged ? (int32_t)poff : -1;
-  size_t noff2 = (poff + (staged ? (size_t)sc.n_pairs * sizeof(PairPts) : 0) + 15) & ~(size_t)15;
+  size_t noff2 = (poff + (staged ? (size_t)sc.n_pairs * 2 * sizeof(TriPts) : 0) + 15) & ~(size_t)15;
   lc.nrm_off = staged ? (int32_t)noff2 : -1;
   size_t loff = (noff2 + (staged ? (size_t)sc.n_pairs * 2 * sizeof(TriNrm) : 0) + 15) & ~(size_t)15;
   const bool groups = (variant & F_SGROUP) && sc.n_sph_groups > 0;  // the grouped sphere scan shares its tests too
@@ -705,6 +705,12 @@ FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameD
   f.pairs_in_lds = lc.pairs_off >= 0 && lc.nrm_off >= 0 && lc.list_off >= 0;
   f.unsigned_colours = sc.unsigned_colours, f.det_safe = sc.det_safe, f.width = fr.width, f.height = fr.height;
   return f;
+}
+
+size_t render_lds_bytes(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads) {
+  size_t lds = 0;
+  (void)make_cfg(variant, sc, fr, threads, &lds);
+  return lds;
 }
 
 // *per_cu = workgroups of Kernel per compute unit at this launch shape; 0 with an error: it does not fit, or the HIP

@@ -39,7 +39,7 @@ struct OcclusionParams {
 struct QueryLds {
   const BvhNode *s_nodes;
   const int *s_paths;
-  const float4 *s_pairs;
+  const float4 *s_tris;
   int *wl, *ll;
   uint16_t *cands;
 };
@@ -50,12 +50,12 @@ __device__ __forceinline__ QueryLds query_stage(const SceneDev &sc, const Launch
   q.wl = nullptr;
   if (F & F_BVH)
     q.wl = reinterpret_cast<int *>(smem + lc.mesh_off) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kMeshWaveWords;
-  q.s_pairs = nullptr;
+  q.s_tris = nullptr;
   if ((F & F_TRIS) && lc.pairs_off >= 0) {
-    q.s_pairs = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.pair_pts);
+    q.s_tris = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.tri_pts);
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + lc.pairs_off);
-    for (int w = threadIdx.x; w < sc.n_pairs * 16; w += blockDim.x) dst[w] = src[w];
+    for (int w = threadIdx.x; w < sc.n_pairs * 24; w += blockDim.x) dst[w] = src[w];
   }
   q.ll = nullptr;
   if ((F & (F_TRIS | F_SGROUP)) && lc.list_off >= 0)
@@ -152,14 +152,14 @@ __device__ __forceinline__ void occlusion_body(const OcclusionParams &p) {
       const double start = pass == 0 ? start0 : (double)INFINITY;
       Hit h = {};
       if (all_lanes_in)  // every lane goes in, with or without a ray of its own
-        h = closest_hit<F, true>(sc, q.s_nodes, lc.lds_nodes, q.s_paths, lc.lds_paths, q.s_pairs, q.ll, q.cands, q.wl,
+        h = closest_hit<F, true>(sc, q.s_nodes, lc.lds_nodes, q.s_paths, lc.lds_paths, q.s_tris, q.ll, q.cands, q.wl,
                                  counts, o, d, go, false
 #ifdef RTMI_STATS
                                  , st
 #endif
                                  , start, seed, &unc);
       else if (go)
-        h = closest_hit<F, true>(sc, q.s_nodes, 0, q.s_paths, 0, q.s_pairs, nullptr, nullptr, nullptr, nullptr, o, d, true,
+        h = closest_hit<F, true>(sc, q.s_nodes, 0, q.s_paths, 0, q.s_tris, nullptr, nullptr, nullptr, nullptr, o, d, true,
                                  false
 #ifdef RTMI_STATS
                                  , st

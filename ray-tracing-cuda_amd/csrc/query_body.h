@@ -105,12 +105,12 @@ __device__ __forceinline__ void query_body(const QueryParams &qp) {
   int *wl = nullptr;
   if (F & F_BVH)
     wl = reinterpret_cast<int *>(smem + lc.mesh_off) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kMeshWaveWords;
-  const float4 *s_pairs = nullptr;
+  const float4 *s_tris = nullptr;
   if ((F & F_TRIS) && lc.pairs_off >= 0) {
-    s_pairs = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.pair_pts);
+    s_tris = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.tri_pts);
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + lc.pairs_off);
-    for (int w = threadIdx.x; w < sc.n_pairs * 16; w += blockDim.x) dst[w] = src[w];
+    for (int w = threadIdx.x; w < sc.n_pairs * 24; w += blockDim.x) dst[w] = src[w];
   }
   int *ll = nullptr;
   if ((F & (F_TRIS | F_SGROUP)) && lc.list_off >= 0)
@@ -159,13 +159,13 @@ __device__ __forceinline__ void query_body(const QueryParams &qp) {
     }
     Hit h = {};
     if (all_lanes_in)  // every lane goes in, with or without a ray of its own
-      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, abandoned, o, d, live, false
+      h = closest_hit<F>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_tris, ll, cands, wl, abandoned, o, d, live, false
 #ifdef RTMI_STATS
                          , st
 #endif
       );
     else if (live)
-      h = closest_hit<F>(sc, s_nodes, 0, s_paths, 0, s_pairs, nullptr, nullptr, nullptr, nullptr, o, d, true, false
+      h = closest_hit<F>(sc, s_nodes, 0, s_paths, 0, s_tris, nullptr, nullptr, nullptr, nullptr, o, d, true, false
 #ifdef RTMI_STATS
                          , st
 #endif

@@ -25,7 +25,7 @@ struct LaunchCfg {
   int32_t lds_nodes;   // reference-tree nodes staged in LDS (the first lds_nodes of SceneDev::nodes)
   int32_t mesh_off;    // byte offset of the per-wave mesh-search regions (kMeshWaveWords words each; BVH variants)
   int32_t exclusive;   // 1: while a wave holds an outlier pixel, its other lanes take no new pixels (they work for it)
-  int32_t pairs_off;   // byte offset of the staged PairPts records, -1: not staged (the culled scan, if on, gathers them
+  int32_t pairs_off;   // byte offset of the staged TriPts records, -1: not staged (the culled scan, if on, gathers them
                        // from global memory)
   int32_t list_off;    // byte offset of the per-wave regions of the shared candidate tests, -1: each lane tests its own
   int32_t paths_off;   // byte offset of the staged leaf-path words
@@ -229,12 +229,12 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   if (F & F_BVH)
     wl = reinterpret_cast<int *>(smem + lc.mesh_off) +
          __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kMeshWaveWords;
-  const float4 *s_pairs = nullptr;  // corners of the world-list pairs (culled scan) or nullptr (plain scan)
+  const float4 *s_tris = nullptr;  // TriPts records of the world-list triangles (culled scan, staged) or nullptr
   if ((F & F_TRIS) && ((M & PIN_LDS_TABLES) || lc.pairs_off >= 0)) {
-    s_pairs = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.pair_pts);
+    s_tris = reinterpret_cast<const float4 *>(smem + lc.pairs_off);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.tri_pts);
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + lc.pairs_off);
-    for (int w = threadIdx.x; w < sc.n_pairs * 16; w += blockDim.x) dst[w] = src[w];
+    for (int w = threadIdx.x; w < sc.n_pairs * 24; w += blockDim.x) dst[w] = src[w];
     const uint32_t *nsrc = reinterpret_cast<const uint32_t *>(sc.tri_nrm);
     uint32_t *ndst = reinterpret_cast<uint32_t *>(smem + lc.nrm_off);
     for (int w = threadIdx.x; w < sc.n_pairs * 8; w += blockDim.x) ndst[w] = nsrc[w];
@@ -690,7 +690,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs))) ||
                               ((F & F_SGROUP) && cands != nullptr);  // wave-uniform
     if (all_lanes_in)  // every lane goes in, with or without a ray of its own: see closest_hit
-      h = closest_hit<F, false, M>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_pairs, ll, cands, wl, counters + (QUEUE ? 0 : 2), o, d, active,
+      h = closest_hit<F, false, M>(sc, s_nodes, lc.lds_nodes, s_paths, lc.lds_paths, s_tris, ll, cands, wl, counters + (QUEUE ? 0 : 2), o, d, active,
                          (F & F_BVH) && lc.visit_counts != nullptr
 #ifdef RTMI_STATS
                          , st
@@ -721,7 +721,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
 #endif
     if (active) {
       if (!all_lanes_in)
-        h = closest_hit<F, false, M & ~(uint32_t)PIN_LDS_TABLES>(sc, s_nodes, 0, s_paths, 0, s_pairs, nullptr, nullptr, nullptr, nullptr, o, d, true, false
+        h = closest_hit<F, false, M & ~(uint32_t)PIN_LDS_TABLES>(sc, s_nodes, 0, s_paths, 0, s_tris, nullptr, nullptr, nullptr, nullptr, o, d, true, false
 #ifdef RTMI_STATS
                            , st
 #endif
@@ -751,7 +751,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           if ((F & F_TRIS) && kind == RUN_TRIS) {
             V3 n;
             int flags;
-            if ((M & PIN_LDS_TABLES) || s_pairs != nullptr) {  // (wave-uniform) the winner's record is in LDS
+            if ((M & PIN_LDS_TABLES) || s_tris != nullptr) {  // (wave-uniform) the winner's record is in LDS
               const float4 tn = s_nrm[index];
               n = mk(tn.x, tn.y, tn.z);
               mat = __float_as_int(tn.w) & 0xffffff, flags = __float_as_int(tn.w) >> 24;
@@ -1006,6 +1006,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     atomicAdd(&counters[30], st.cull_bits);
     atomicAdd(&counters[31], st.cull_iters);
     atomicAdd(&counters[32], st.cull_rays);
+    // (two buckets per word, low half first: a diagnostic frame stays far below 2^32 flushes)
+    for (int i = 0; i < 3; i++)
+      atomicAdd(&counters[37 + i], (unsigned long long)st.nnow_hist[2 * i] | ((unsigned long long)st.nnow_hist[2 * i + 1] << 32));
     const unsigned wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (!(F & F_BVH) && wid < 16384u) {
       atomicAdd(&counters[25], g_wave_stats[wid][9]);

@@ -45,6 +45,11 @@ struct HostBvh {
   int n = 0, mat = -1, leaf_max = 2048;
 };
 
+// A world-list pair's corners, on the host only (check_margins): the device reads per-triangle TriPts records.
+struct PairPts {
+  float p0[3], p1[3], p2[3], p3[3];  // p3 = p1 + p2 - p0 (parallelogram.cu:13); unused for a lone Triangle
+};
+
 struct Scene {
   std::vector<HostTex> texs;
   std::vector<HostMat> mats;
@@ -62,7 +67,8 @@ struct Scene {
   std::vector<SphereRec> spheres;
   std::vector<HotTri> tris;
   std::vector<PairBox> pair_boxes;
-  std::vector<PairPts> pair_pts;
+  std::vector<PairPts> pair_pts;  // host only: the pairs' corners (check_margins)
+  std::vector<TriPts> tri_pts;    // two per pair
   std::vector<TriNrm> tri_nrm;
   std::vector<SphGroup> sph_groups;
   std::vector<SphMember> sph_members;

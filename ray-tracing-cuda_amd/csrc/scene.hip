@@ -33,8 +33,28 @@ static HotTri hot_tri(V3 p0, V3 p1, V3 p2, int mat, int flags) {
 
 static int face_slack_exponent(const V3 p[3]);
 
-// The per-pair records of the culled list scan: corners and padded bounds (n = 3 or 4 points).
-static void push_pair(Scene &s, const V3 *p, int n, int flags) {
+// One triangle of the culled list scan: the base point and the edges by the binary32 subtractions of utils.cu:54-55,
+// the ones make_tri performs for the HotTri of the same index (flatten checks the bit patterns).
+static TriPts tri_pts(V3 a, V3 b, V3 c, int flags) {
+  const V3 e1 = b - a, e2 = c - a;
+  TriPts r{};
+  r.p0[0] = a.x, r.p0[1] = a.y, r.p0[2] = a.z;
+  r.e1[0] = e1.x, r.e1[1] = e1.y, r.e1[2] = e1.z;
+  r.e2[0] = e2.x, r.e2[1] = e2.y, r.e2[2] = e2.z;
+  r.flags = flags;
+  return r;
+}
+
+// The records of the culled list scan for one pair: its two triangles, its corners and padded bounds (n = 3 or 4 points).
+static void push_pair(Scene &s, const V3 *p, int n) {
+  s.tri_pts.push_back(tri_pts(p[0], p[1], p[2], 0));
+  if (n == 4) {
+    s.tri_pts.push_back(tri_pts(p[1], p[2], p[3], 0));
+  } else {
+    TriPts none{};  // a lone Triangle has no second
+    none.flags = TRIPTS_ABSENT;
+    s.tri_pts.push_back(none);
+  }
   PairPts pp{};
   const V3 q[4] = {p[0], p[1], p[2], n == 4 ? p[3] : p[2]};
   for (int c = 0; c < 3; c++) {
@@ -42,7 +62,6 @@ static void push_pair(Scene &s, const V3 *p, int n, int flags) {
                         c == 0 ? q[2].x : c == 1 ? q[2].y : q[2].z, c == 0 ? q[3].x : c == 1 ? q[3].y : q[3].z};
     pp.p0[c] = x[0], pp.p1[c] = x[1], pp.p2[c] = x[2], pp.p3[c] = x[3];
   }
-  pp.flags = flags;
   PairBox bx{};
   float diag = 0.f, mag = 0.f;
   for (int c = 0; c < 3; c++) {
@@ -78,7 +97,7 @@ static void push_pgram(Scene &s, V3 p0, V3 p1, V3 p2, int mat) {
   out.push_back(first);
   out.push_back(second);
   const V3 q[4] = {p0, p1, p2, p3};
-  push_pair(s, q, 4, PAIR_SECOND | ((second.flags & TRI_SAME_E2) ? PAIR_SAME_E2 : 0));
+  push_pair(s, q, 4);
 }
 
 // parallelepiped.cu:8-18: derive the four opposite corners.
@@ -554,7 +573,7 @@ static int build_bvh_nodes(std::vector<BvhNode> &nodes, std::vector<FacePts> &fp
 }
 
 std::string Scene::flatten() {
-  pair_boxes.clear(), pair_pts.clear(), tri_nrm.clear(), list_mag = 0.f;
+  pair_boxes.clear(), pair_pts.clear(), tri_pts.clear(), tri_nrm.clear(), list_mag = 0.f;
   sph_groups.clear(), sph_members.clear(), sph_mag = 0.f;
   sliver_faces = 0;
   runs.clear(), spheres.clear(), tris.clear(), bvh_recs.clear(), face_of_orig.clear(), nodes.clear(), qnodes.clear(), faces.clear(), leaf_paths.clear(), tops.clear(),
@@ -637,7 +656,7 @@ std::string Scene::flatten() {
         if (!check_mat(ob.mat)) return "triangle without a valid material";
         tris.push_back(hot_tri(ob.p[0], ob.p[1], ob.p[2], ob.mat, 0));
         tris.push_back(HotTri{});  // inert second record: the world-list loop walks pairs
-        push_pair(*this, ob.p, 3, 0);
+        push_pair(*this, ob.p, 3);
         push_run(RUN_TRIS, (int)tris.size() - 2);
         name_pairs(QHIT_TRIANGLE);
         features |= F_TRIS;
@@ -891,6 +910,14 @@ std::string Scene::check_margins() const {
         return "margin budget: a world-list pair's bounds do not cover what its triangle tests can accept";
     }
     if (!(mag <= list_mag)) return "margin budget: list_mag is below a pair's coordinates";
+  }
+  // a TriPts record is the head of its HotTri, bit for bit: the staged and the gathered scan test the same operands
+  if (tri_pts.size() != 2 * pair_pts.size() || tris.size() < tri_pts.size()) return "world list: triangle records out of step";
+  for (size_t t = 0; t < tri_pts.size(); t++) {
+    const bool absent = (t & 1) && !(tris[t].flags & TRI_SECOND);
+    if (absent != ((tri_pts[t].flags & TRIPTS_ABSENT) != 0)) return "world list: a triangle record's absent flag is wrong";
+    if (!absent && memcmp(tri_pts[t].p0, tris[t].p0, 9 * sizeof(float)) != 0)
+      return "world list: a triangle record's base point or edges differ from its HotTri's";
   }
   for (size_t g = 0; g + 1 < sph_groups.size(); g++) {  // (the last record is the look-ahead's padding)
     const SphGroup &gr = sph_groups[g];

@@ -76,21 +76,23 @@ struct HotTri {
   int32_t pad[2];
 };
 
-// The same world-list triangles once more, per PAIR (a Parallelogram, or a lone Triangle), for the
-// culled form of the list scan (closest_hit.h: RUN_TRIS): `PairBox` is read at a
-// wave-uniform index (one s_load_dwordx8): the pair's bounds, padded like the mesh search boxes;
-// `PairPts` is staged in LDS and gathered per lane: the four corners, from which the kernel forms the
-// edges with the same binary32 subtractions the host used for HotTri.
-enum : int32_t { PAIR_SECOND = 1, PAIR_SAME_E2 = 2 };
+// The same world-list triangles once more for the culled form of the list scan (closest_hit.h: RUN_TRIS).  Per PAIR
+// (a Parallelogram, or a lone Triangle) a `PairBox`, read at a wave-uniform index (one s_load_dwordx8): the pair's
+// bounds, padded like the mesh search boxes.  Per TRIANGLE a `TriPts`, staged in LDS and read per lane, at index
+// 2 * pair + which like its HotTri: the base point and the two edges, the first twelve words of which are the HotTri's
+// own (scene.hip checks the bit patterns at commit), so that a list too long for the staging gathers them from
+// `tris` instead.  (p0, p1 - p0, p2 - p0), then (p1, p2 - p1, p3 - p1); a lone Triangle's second record is absent.
+enum : int32_t { TRIPTS_ABSENT = 1 };
 struct PairBox {  // 32 B
   float mn[3], mx[3];
   int32_t pad[2];
 };
-struct alignas(16) PairPts {  // 64 B
-  float p0[3], p1[3], p2[3], p3[3];  // p3 = p1 + p2 - p0 (parallelogram.cu:13); unused for a lone Triangle
+struct alignas(16) TriPts {  // 48 B
+  float p0[3], e1[3], e2[3];
   int32_t flags;
-  int32_t pad[3];
+  int32_t pad[2];
 };
+static_assert(sizeof(TriPts) == 48, "TriPts is read with three ds_read_b128");
 // What shading needs of the winning world-list triangle, staged in LDS next to the pairs (one record per
 // HotTri, same index): the unit normal and the material (low 24 bits) | HotTri::flags << 24.  A per-lane read
 // of 16 bytes from LDS instead of a 64-byte gather from global memory on every hit.
@@ -112,7 +114,7 @@ constexpr int kListTasks(uint32_t features) { return (features & 16u) ? 96 : (fe
 constexpr int kListWaveWords(uint32_t features) {
   return 64 * 8 + kListTasks(features) * (1 + ((features & 16u) ? 6 : (features & 1u) ? 3 : 2));  // (16 = F_TEX, 1 = F_SPHERE)
 }
-constexpr int kLdsPairs = 128;  // at most this many PairPts records are staged in LDS (8 KiB); longer lists use the plain scan
+constexpr int kLdsPairs = 128;  // at most this many pairs have their TriPts records staged in LDS (12 KiB); longer lists gather from `tris`
 
 enum MatKind : int32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_LIGHT = 3, MAT_SKY = 4 };
 
@@ -235,8 +237,8 @@ struct SceneDev {
   const SphMember *sph_members;
   float sph_mag;               // largest |coordinate| of the grouped spheres' bounds (scales the distance slack)
   int32_t n_sph_groups;
-  const PairPts *pair_pts;
-  const TriNrm *tri_nrm;      // per `tris` record (2 * n_pairs), staged in LDS with pair_pts
+  const TriPts *tri_pts;      // per `tris` record (2 * n_pairs): the source of the LDS staging (lists up to kLdsPairs)
+  const TriNrm *tri_nrm;      // per `tris` record (2 * n_pairs), staged in LDS with tri_pts
   const BvhRec *bvhs;
   const BvhNode *nodes;
   const QNode4 *qnodes;
@@ -252,7 +254,7 @@ struct SceneDev {
   const MatRec *mats;
   const TexRec *texs;
   int32_t n_runs, n_mats, n_nodes;
-  int32_t n_pairs;    // pairs in pair_boxes / pair_pts (0: the culled list scan is off)
+  int32_t n_pairs;    // pairs in pair_boxes, half the records of tri_pts (0: the culled list scan is off)
   float list_mag;     // largest |coordinate| of the world-list triangles (scales the cull's distance slack)
   int32_t sub_reserve;  // 3 * (deepest search tree) + 3 + kMeshFaceSlack: stack words the wave-wide search keeps free
                         // after a wide step (0 without meshes); see mesh_search

@@ -635,6 +635,22 @@ class SceneBuilder:
         keys = ["world", "spheres", "parallelograms", "triangles", "bvh_faces", "bvh_nodes", "materials", "textures"]
         return dict(zip(keys, list(out)))
 
+    def list_records(self):
+        """The culled list scan's records (rtmi_debug_list_records): (tri_pts uint32 (P, 2, 12), hot_tris uint32
+        (P, 2, 16), corners float32 (P, 4, 3)) for the P pairs of the world list.  Host only."""
+        fn = self.L.rtmi_debug_list_records  # (a diagnostic: bound here, so that lib() asks no A/B build for it)
+        fn.restype, fn.argtypes = C.c_int64, [C.c_void_p, C.c_int64, _u32p, _u32p, _fp]
+        n = _check(fn(self.h, 0, None, None, None), "rtmi_debug_list_records")
+        tp, ht, co = np.zeros((n, 2, 12), np.uint32), np.zeros((n, 2, 16), np.uint32), np.zeros((n, 4, 3), np.float32)
+        _check(fn(self.h, n, tp.ctypes.data_as(_u32p), ht.ctypes.data_as(_u32p), co.ctypes.data_as(_fp)), "rtmi_debug_list_records")
+        return tp, ht, co
+
+    def render_lds_bytes(self, max_depth, threads=256):
+        """Dynamic LDS per workgroup of a render of this scene (rtmi_debug_render_lds_bytes).  Host only."""
+        fn = self.L.rtmi_debug_render_lds_bytes
+        fn.restype, fn.argtypes = C.c_int64, [C.c_void_p, C.c_int, C.c_int]
+        return _check(fn(self.h, max_depth, threads), "rtmi_debug_render_lds_bytes")
+
     def sliver_faces(self):
         return _check(self.L.rtmi_scene_sliver_faces(self.h), "rtmi_scene_sliver_faces")
 

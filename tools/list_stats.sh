@@ -25,5 +25,10 @@ for i, n in enumerate(names):
         print("  %-18s %5.1f%% of wave time, %7.0f cycles per wave_query" % (n, 100.0 * out[17 + i] / life, out[17 + i] / max(wq, 1)))
 print("  shade: up to the material record (divergent lanes stamp separately: upper bound) %.0f, up to before the fold %.0f cycles per wave_query" % (out[25] / max(wq, 1), out[6] / max(wq, 1)))
 print("  wave life mean %.1f Mcyc max %.1f Mcyc, %d waves; cycles per wave_query %.0f" % (life / max(out[28], 1) / 1e6, out[27] / 1e6, out[28], life / max(wq, 1)))
+hist = [(out[37 + i // 2] >> (32 * (i % 2))) & 0xffffffff for i in range(6)]
+nf = max(sum(hist), 1)
+print("flushes by pair tasks in flight (n_now), buckets of 32: %s = %s" % (hist, ["%.3f" % (h / nf) for h in hist]))
+print("  per flush: pair rounds (ceil(n/64)) %.3f, triangle rounds (ceil(2n/64)) %.3f; flushes per wave_query %.3f" % (
+    sum((i // 2 + 1) * h for i, h in enumerate(hist)) / nf, sum((i + 1) * h for i, h in enumerate(hist)) / nf, sum(hist) / max(wq, 1)))
 print("rays %d wave_queries %d: candidate pairs per ray %.2f (of %d lane-chunks), wave iterations per query %.2f" % (rays, wq, bits / max(crays, 1), crays, iters / max(wq, 1)))
 PY
