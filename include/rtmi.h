@@ -625,7 +625,12 @@ int rtmi_resolve_variance(const rtmi_frame *f, const float *d_sum, const float *
  *       xc = d2 / ((sigma_color * sigma_color) * vs + 1e-10f);  wc = falloff(xc);
  *     w = (((h[dy] * h[dx]) * wn) * wz) * wc;
  *     in tap order:  sw += w;  per channel  sc += w * C_q;  sv += (w * w) * V_q;
- *     sw > 0:  C'_p = sc / sw,  V'_p = sv / (sw * sw);  otherwise C'_p = C_p, V'_p = V_p.
+ *     sw >= 0x1p-32f:  C'_p = sc / sw,  V'_p = sv / (sw * sw);  otherwise C'_p = C_p, V'_p = V_p.
+ * The threshold keeps the pass inside the normal numbers: with normal squarings the centre tap's own weight is
+ * |N_p|^(2^(squarings+1)), tiny at any partly covered or crease pixel, and a subnormal sw or an underflowing sw * sw would
+ * make V' infinite or NaN out of finite inputs.  From 2^-32 on, sw * sw >= 2^-64 and the largest tap's w * w >= 2^-64 / 625
+ * are normal, and what a flushed w * w loses is below 2^-50 of the largest term.  A pixel that weighs so little keeps its
+ * value, exactly as one whose weights are all 0.
  * Pass k + 1 reads C' and V'; the guides never change.  After the last pass d_out = demodulate ? C * ad : C and, where
  * d_out_variance is not null, d_out_variance = demodulate ? V * (ad * ad) : V.
  * So a pixel is averaged only with pixels on the same side of a coverage, normal or depth edge, and over a colour range of

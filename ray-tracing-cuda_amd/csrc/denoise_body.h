@@ -16,6 +16,7 @@ namespace {
 constexpr int kTileW = 32, kTileH = 8;  // one workgroup: 32 x 8 pixels, a lane per pixel, a wave = two rows
 constexpr int kLdsStep = 2;             // steps 1 and 2 stage tile + halo in LDS; larger steps read global records
 constexpr int kLdsW = kTileW + 4 * kLdsStep, kLdsH = kTileH + 4 * kLdsStep;  // 40 x 16 records at step 2
+constexpr float kMinWeightSum = 0x1p-32f;  // a pass filters a pixel only from this sum of weights on (include/rtmi.h)
 
 struct DenoiseArgs {
   int height, width;
@@ -141,11 +142,11 @@ __global__ __launch_bounds__(kTileW *kTileH) void atrous_kernel(DenoiseArgs a) {
     }
   }
   float c[3] = {cp.x, cp.y, cp.z}, v[3] = {vp.x, vp.y, vp.z};
-  if (sw > 0.0f) {
-    const float sw2 = sw * sw;
+  // Below 2^-32 the pixel keeps what it has: sw * sw and the largest w * w stay normal numbers above it (a select each).
+  const bool filtered = sw >= kMinWeightSum;
+  const float sw2 = sw * sw;
 #pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = sc[k] / sw, v[k] = sv[k] / sw2;
-  }
+  for (int k = 0; k < 3; k++) c[k] = filtered ? sc[k] / sw : c[k], v[k] = filtered ? sv[k] / sw2 : v[k];
   if (LAST) {
     if (a.demodulate) {
       float ad[3];

@@ -20,6 +20,7 @@ KERNELS = {"atrous_kernel": 4, "denoise_prepare_kernel": 1, "resolve_variance_ke
 F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H5 = [F32(1) / F32(16), F32(1) / F32(4), F32(3) / F32(8), F32(1) / F32(4), F32(1) / F32(16)]
+MIN_WEIGHT_SUM = F32(2.0 ** -32)  # a pass filters a pixel only from this sum of weights on: below it sw * sw leaves the normals
 
 
 # ------------------------------------------------------------------ the rules, restated
@@ -52,10 +53,11 @@ def variance_rule(n, S, Q, pixel=None):
 
 def denoise_rule(color, variance, normal, depth, alpha, albedo=None, iterations=rtmi.DENOISE_DEFAULTS["iterations"],
                  sigma_color=rtmi.DENOISE_DEFAULTS["sigma_color"], sigma_depth=rtmi.DENOISE_DEFAULTS["sigma_depth"],
-                 normal_squarings=rtmi.DENOISE_DEFAULTS["normal_squarings"], demodulate=None):
+                 normal_squarings=rtmi.DENOISE_DEFAULTS["normal_squarings"], demodulate=None, decisions=None):
     """rtmi_denoise in numpy, operation by operation as include/rtmi.h states it: float32 throughout, vectorised over the
     image, the 25 taps in the stated order.  color, variance, normal, albedo (H, W, 3), depth, alpha (H, W).  Returns
-    (out, out_variance), both (H, W, 3) float32."""
+    (out, out_variance), both (H, W, 3) float32.  decisions: a list that receives, per pass, the (H, W) bool array of the
+    pixels the pass filtered (the others kept their value)."""
     C0, V0, N, Z, A = (np.asarray(x, dtype=F32) for x in (color, variance, normal, depth, alpha))
     demodulate = (albedo is not None) if demodulate is None else bool(demodulate)
     H, W = Z.shape
@@ -98,7 +100,9 @@ def denoise_rule(color, variance, normal, depth, alpha, albedo=None, iterations=
                     sw = np.where(take, sw + w, sw)
                     sc = np.where(take[..., None], sc + w[..., None] * Cq, sc)
                     sv = np.where(take[..., None], sv + (w * w)[..., None] * Vq, sv)
-            ok = (sw > 0)[..., None]
+            ok = (sw >= MIN_WEIGHT_SUM)[..., None]
+            if decisions is not None:
+                decisions.append(ok[..., 0])
             Cc, V = np.where(ok, sc / sw[..., None], Cc), np.where(ok, sv / (sw * sw)[..., None], V)
             assert Cc.dtype == F32 and V.dtype == F32
         if demodulate:

@@ -16,7 +16,8 @@ import pytest
 
 import common
 import rtmi
-from test_accumulate_host import FOV, MOVES, SHAPES, accumulate_rule, bits, camera_of, room, same
+from filters_truth import LANDING_M, SNAP, landing_truth, same_or_nan
+from test_accumulate_host import FOV, MOVES, SHAPES, accumulate_rule, bits, camera_of, look_at, room, same
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +49,11 @@ def assert_exact(got, expected, what):
 def chain(h, w, move, seed=0, **opts):
     """Three frames: the home camera without a history, the moved camera, the home camera again.  Yields (frame number, what
     the device gave, what the rule gives), each (out, variance, length, history)."""
-    cams = [camera_of("static", h, w), camera_of(move, h, w), camera_of("static", h, w)]
+    return chain_of(h, w, [camera_of("static", h, w), camera_of(move, h, w), camera_of("static", h, w)], seed, **opts)
+
+
+def chain_of(h, w, cams, seed=0, **opts):
+    """chain() over any sequence of cameras, the first without a history."""
     hist_dev = hist_rule = prev = None
     for k, cam in enumerate(cams):
         d = room(h, w, cam, seed=seed + k)
@@ -71,6 +76,108 @@ def test_accumulate_equals_the_rule(shape, move, opts):
         blended |= bool((exp[2] > 1).any())
     if shape == (33, 70) and move != "about":
         assert blended  # the case is worth its name: some pixel took its history
+
+
+# ------------------------------------------------------------------ 1b. long frames, the extreme extents, non-finite inputs
+@pytest.mark.parametrize("shape", [(9, 300), (300, 9)], ids=lambda s: "%dx%d" % s)
+def test_accumulate_long_thin_frames_equal_the_rule(shape):
+    """Frames 300 pixels long one way (the rule blends 51 % of 9 x 300 and 45 % of 300 x 9 under "slide")."""
+    for k, got, exp in chain(*shape, "slide"):
+        assert_exact(got, exp, "%dx%d slide frame %d" % (shape + (k + 1,)))
+        if k == 1:
+            assert (exp[2] > 1).mean() >= 0.4
+
+
+def extreme_slide(h, w):
+    """A slide that keeps the points of an extreme frame on screen.  1 x 65535: "slide" itself; one pixel is wider than the
+    room there, so it moves every point by less than a pixel, and half of the frame is background.  65535 x 1: "slide" leaves
+    the single column, so the camera and its target move up by 0.05 instead, 3 pixel heights at the back wall and more nearer."""
+    if h == 1:
+        return camera_of("slide", h, w)
+    return look_at((278, 273.05, -800), (278, 273.05, 0), aspect=w / h)
+
+
+@pytest.mark.parametrize("move", ["static", "slide"])
+@pytest.mark.parametrize("shape", [(1, 65535), (65535, 1)], ids=lambda s: "%dx%d" % s)
+def test_accumulate_extreme_extents_equal_the_rule(shape, move):
+    h, w = shape
+    home = camera_of("static", h, w)
+    for k, got, exp in chain_of(h, w, [home, home if move == "static" else extreme_slide(h, w)]):
+        assert_exact(got, exp, "%dx%d %s frame %d" % (shape + (move, k + 1)))
+    assert (exp[2] > 1).mean() >= 0.25  # (the rule alone says so: the history was taken, not only passed by)
+
+
+OUTPUTS = ("out", "out_variance", "out_length", "history")
+
+
+def pixel_differs(g, c):
+    """(H, W) bool: where two outputs of one kind differ in any bit of the pixel (a history is (3, H, W, 4))."""
+    x = bits(g) != bits(c)
+    return x.any(axis=(0, 3)) if x.ndim == 4 else x.any(axis=-1) if x.ndim == 3 else x
+
+
+def _second_frame(d1, cam1, hist0, cam0):
+    """The second frame of a sequence on the device and by the rule: each (out, variance, length, history)."""
+    hist_in = torch.from_numpy(np.ascontiguousarray(hist0).view(np.uint8).reshape(-1)).cuda()
+    h, w = d1["depth"].shape
+    out, var, length, hist = rtmi.accumulate(**on_gpu(d1), camera=cam1, history=hist_in, prev_camera=cam0)
+    torch.cuda.synchronize()
+    exp = accumulate_rule(**d1, camera=cam1, history=hist0, prev_camera=cam0)
+    return (out.cpu().numpy(), var.cpu().numpy(), length.cpu().numpy(), history_of(hist, h, w)), exp[:4]
+
+
+def _slide_33x70():
+    h, w = 33, 70
+    cam0, cam1 = camera_of("static", h, w), camera_of("slide", h, w)
+    d0, d1 = room(h, w, cam0, seed=8), room(h, w, cam1, seed=9)
+    return d1, cam1, accumulate_rule(**d0, camera=cam0)[3], cam0
+
+
+@pytest.mark.parametrize("what", ["nan_depth", "inf_depth", "nan_color"])
+def test_accumulate_non_finite_frame_pixel_touches_nothing_else(what):
+    """One non-finite input in a frame whose pixel would take its history: the call does not fault and equals the rule (a
+    NaN for a NaN); a non-finite depth makes the pixel fresh ("a NaN is fresh too"), a NaN colour stays that pixel's; and
+    every other pixel of every output has the clean run's bits."""
+    d1, cam1, hist0, cam0 = _slide_33x70()
+    at = (16, 36)
+    clean, _ = _second_frame(d1, cam1, hist0, cam0)
+    assert clean[2][at] > 1
+    d = {k: v.copy() for k, v in d1.items()}
+    if what == "nan_color":
+        d["color"][at][1] = np.nan
+    else:
+        d["depth"][at] = np.nan if what == "nan_depth" else np.inf
+    got, exp = _second_frame(d, cam1, hist0, cam0)
+    other = np.ones(clean[2].shape, bool)
+    other[at] = False
+    for name, g, e, c in zip(OUTPUTS, got, exp, clean):
+        assert same_or_nan(g, e).all(), (what, name, np.argwhere(~same_or_nan(g, e))[0])
+        assert not pixel_differs(g, c)[other].any(), (what, name)
+    if what == "nan_color":
+        assert np.isnan(got[0][at][1]) and got[2][at] == clean[2][at]
+    else:
+        assert got[2][at] == 1 and same(got[0][at], d["color"][at]) and same(got[1][at], d["variance"][at])
+
+
+def test_accumulate_nan_in_the_history_stays_with_its_taps():
+    """A NaN in one history record: the device equals the rule, some pixel takes it, and only pixels whose four taps include
+    the record differ from the clean run -- their landing point, by tests/filters_truth.py's binary64 projection, is less
+    than a pixel and the snap away from it in both axes."""
+    d1, cam1, hist0, cam0 = _slide_33x70()
+    at = (16, 36)
+    clean, _ = _second_frame(d1, cam1, hist0, cam0)
+    hist = hist0.copy()
+    hist[1, at[0], at[1], 0] = np.nan
+    got, exp = _second_frame(d1, cam1, hist, cam0)
+    differs = np.zeros(clean[2].shape, bool)
+    for name, g, e, c in zip(OUTPUTS, got, exp, clean):
+        assert same_or_nan(g, e).all(), (name, np.argwhere(~same_or_nan(g, e))[0])
+        differs |= pixel_differs(g, c)
+    assert differs.any() and np.isnan(got[0][differs]).any()
+    # a tap of the record: the rule's landing point is less than a pixel from it, and the truth within SNAP + m of that
+    fx, fy, _, _ = landing_truth(*differs.shape, cam1, cam0, d1["depth"])
+    reach = 1 + SNAP + LANDING_M
+    assert (np.abs(fx[differs] - at[1]) < reach).all() and (np.abs(fy[differs] - at[0]) < reach).all()
 
 
 def _raw(h, w, t, cam, hist_in, prev, hist_out, out, out_var, out_len, **opts):

@@ -8,7 +8,9 @@ variances of which a fifth are exactly 0, and albedos with exact zeros.  Shapes 
 and borders can go wrong: one pixel; one tile row or column narrower than the stencil; a frame that is ragged against the
 32 x 8 tile in both directions with several tiles; and 16 x 16, where the fifth pass (step 16) has every off-centre tap
 outside the image.  Passes 1-2 run the LDS-staged kernel, 3-5 the global one, and the last pass of every call the
-remodulating one: 1, 3 and 5 iterations put each of the four instantiations in the last position or before it."""
+remodulating one: 1, 3 and 5 iterations put each of the four instantiations in the last position or before it.  Passes 6-8
+run on frames 300 pixels long, the extreme extents 1 x 65535 and 65535 x 1 on their own, and tests/test_gpu_filters_truth.py
+holds the same calls to binary64."""
 import ctypes as C
 import os
 import subprocess
@@ -19,6 +21,7 @@ import pytest
 
 import common
 import rtmi
+from filters_truth import same_or_nan, synthetic
 from test_budget_host import _frame
 from test_denoise_host import denoise_rule, variance_rule
 
@@ -39,34 +42,6 @@ def bits(x):
 
 def same(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def synthetic(h, w, seed=0):
-    """dict of rtmi.denoise's inputs, numpy float32: colours in [0, 4); variances in [0, 1), about a fifth exactly 0; mean
-    normals of length <= 1; depths in [0.5, 20); alpha in {0, 0.25, 1} with patches of background; albedo in [0, 1] with
-    exact zeros."""
-    rng = np.random.default_rng([seed, h, w])
-    I, J = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    patch = ((I // 5) * 3 + J // 7) % 6  # 5 x 7 pixel patches of six kinds; kind 5 is background
-    base_n = np.array([[0, 0, 1], [0, 1, 0], [0.6, 0, 0.8], [0, 0.6, 0.8], [1, 0, 0], [0, 0, 0]], F32)
-    base_z = np.array([2.0, 2.2, 9.0, 9.5, 18.0, 0.0], F32)
-    n = base_n[patch] + rng.normal(0, 0.08, (h, w, 3)).astype(F32)
-    n = n / np.sqrt((n * n).sum(-1, keepdims=True), dtype=F32)
-    n = (n * rng.uniform(0.5, 0.999, (h, w, 1)).astype(F32)).astype(F32)
-    z = np.clip(base_z[patch] * (1 + rng.normal(0, 0.03, (h, w))), 0.5, 19.99).astype(F32)
-    alpha = rng.choice(np.array([0.25, 1.0], F32), (h, w))
-    alpha[(patch == 5) | (rng.random((h, w)) < 0.05)] = 0
-    color = (rng.random((h, w, 3)) * 4).astype(F32)
-    color[..., 1] = color[..., 0] * F32(0.5) + color[..., 1] * F32(0.1)  # (correlated channels: d2 small against vs somewhere)
-    variance = rng.random((h, w, 3)).astype(F32)
-    variance[rng.random((h, w, 3)) < 0.2] = 0
-    albedo = rng.random((h, w, 3)).astype(F32)
-    albedo[rng.random((h, w, 3)) < 0.1] = 0
-    albedo[rng.random((h, w)) < 0.05] = 1
-    d = dict(color=color, variance=variance, normal=n, depth=z, alpha=alpha.astype(F32), albedo=albedo)
-    assert all(v.dtype == F32 for v in d.values())
-    assert 0 <= color.min() and color.max() < 4 and variance.max() < 1 and (n * n).sum(-1).max() <= 1.0001
-    return d
 
 
 def on_gpu(d):
@@ -111,6 +86,48 @@ def test_denoise_equals_the_rule(shape, iterations, demodulate):
         assert (bits(got[0]) != bits(d["color"])).mean() > 0.5
 
 
+# ------------------------------------------------------------------ 1b. the far passes, the extreme extents, non-finite inputs
+@pytest.mark.parametrize("demodulate", [0, 1])
+@pytest.mark.parametrize("iterations", [6, 7, 8])
+@pytest.mark.parametrize("shape", [(9, 300), (300, 9)], ids=lambda s: "%dx%d" % s)
+def test_denoise_far_passes_equal_the_rule(shape, iterations, demodulate):
+    """Steps 32, 64 and 128: their taps at +-2 steps (64, 128, 256 pixels away) land inside a frame 300 pixels long."""
+    d = synthetic(*shape)
+    assert_exact(run(d, demodulate, iterations=iterations), want(d, demodulate, iterations=iterations),
+                 "%dx%d k=%d demodulate=%d" % (shape + (iterations, demodulate)))
+
+
+@pytest.mark.parametrize("iterations", [1, 3])
+@pytest.mark.parametrize("shape", [(1, 65535), (65535, 1)], ids=lambda s: "%dx%d" % s)
+def test_denoise_extreme_extents_equal_the_rule(shape, iterations):
+    """The largest extent either way (2048 tile columns, 8192 tile rows): one staged pass alone, and two before a global one."""
+    d = synthetic(*shape)
+    assert_exact(run(d, 1, iterations=iterations), want(d, 1, iterations=iterations), "%dx%d k=%d" % (shape + (iterations,)))
+
+
+@pytest.mark.parametrize("what", ["nan_color", "inf_depth"])
+def test_denoise_non_finite_input_stays_in_its_footprint(what):
+    """One NaN colour, or one infinite depth, in a 33 x 70 frame under 3 iterations (reach 2 (1 + 2 + 4) = 14 pixels): the
+    call does not fault, equals the rule (a NaN for a NaN), and every pixel further than 14 pixels (Chebyshev) from it
+    has the bits of the clean run."""
+    h, w, at = 33, 70, (16, 36)
+    clean = synthetic(h, w, seed=6)
+    assert clean["alpha"][at] > 0
+    d = {k: v.copy() for k, v in clean.items()}
+    if what == "nan_color":
+        d["color"][at][1] = np.nan
+    else:
+        d["depth"][at] = np.inf
+    got, exp, ref = run(d, 1, iterations=3), want(d, 1, iterations=3), run(clean, 1, iterations=3)
+    I, J = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    far = np.maximum(np.abs(I - at[0]), np.abs(J - at[1])) > 14
+    assert far.any() and not far.all()
+    for name, g, e, r in zip(("out", "out_variance"), got, exp, ref):
+        assert same_or_nan(g, e).all(), (what, name, np.argwhere(~same_or_nan(g, e))[0])
+        assert (bits(g)[far] == bits(r)[far]).all(), (what, name)
+    assert not (bits(got[0])[~far] == bits(ref[0])[~far]).all()  # (and it was seen inside)
+
+
 def test_denoise_in_place_and_without_the_variance():
     """d_out == d_color, with and without d_out_variance: the same bits as out of place."""
     d = synthetic(33, 70, seed=1)
@@ -133,7 +150,9 @@ def test_denoise_in_place_and_without_the_variance():
 def test_denoise_normal_squarings_at_both_ends(squarings):
     d = synthetic(33, 70, seed=2)
     opts = dict(iterations=3, normal_squarings=squarings, sigma_color=2.5, sigma_depth=0.1)
-    assert_exact(run(d, 1, **opts), want(d, 1, **opts), "squarings %d" % squarings)
+    got = run(d, 1, **opts)
+    assert_exact(got, want(d, 1, **opts), "squarings %d" % squarings)
+    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()  # (8 squarings: sums of weights down to 0 and below 2^-32)
 
 
 # ------------------------------------------------------------------ 2. edges are hard
