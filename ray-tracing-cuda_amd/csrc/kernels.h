@@ -70,6 +70,11 @@ constexpr uint32_t kFastCommon = PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED 
                                  PIN_EVERY_LANE | PIN_PRIORITIES;
 constexpr uint32_t kFastChains = kFastCommon | PIN_CHAINS;  // the second launch of a planned frame (C2, a C4 shard)
 constexpr uint32_t kFastQueue = kFastCommon | PIN_QUEUE;    // a first pass, a queued or image-order frame
+// The trace loop of the two kernels above normalises a Lambertian bounce's direction one iteration late, at the site
+// that normalises the new camera rays (render_body.h: kOwesBit).  The M == 0 render kernels and the caller-owned trace,
+// budget and feature kernels keep both sites and compile to what they were: their registers moved both ways with the
+// deferral (NOTES.md, "Deferred normalisation") and no benchmark line runs them long enough to tell a 2 % from noise.
+constexpr bool defers_unit(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
 // Everything the fast kernels take for granted, as the call's plan knows it (capi.hip: plan_render).  One predicate for
 // the plan, which the launch and rtmi_render_mode both read, and for the tests (rtmi_fast_path_kernel).
 struct FastPathFacts {

@@ -304,6 +304,12 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // per-lane path state
   V3 o = splat(0.f), d = splat(0.f);
   int depth = 0;
+  // Bit 31 of depth: d is the raw vector of a new camera ray or of a Lambertian bounce, and normalize(normalize(d)) is
+  // due at the top of the next iteration, which clears the bit before anything reads depth (a mark of its own, a lane
+  // mask or a flag, costs more instructions in every fast kernel: NOTES.md, "Deferred normalisation")
+  // Kernels that do not defer (kernels.h: defers_unit) never set it and normalise at both sites as before.
+  constexpr bool DEFER = defers_unit(M);
+  constexpr int kOwesBit = (int)0x80000000u;
   // Layer stack of ray_tracing.cuh:9-15.  Layer::emitted is 0 for every material that
   // scatters (only DiffuseLight and Sky emit, and neither scatters), so a layer is its
   // attenuation.  Without image textures the attenuation is the material's constant
@@ -663,14 +669,29 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
         o = origin;
-        d = unit3_rn_twice(target - origin);  // RayAt normalises, Ray's constructor normalises again
+        // RayAt normalises, Ray's constructor normalises again (DEFER: both below, with the bounces)
+        d = DEFER ? target - origin : unit3_rn_twice(target - origin);
         k++;
         if ((F & F_BVH) && promote && cls == 1 && k >= lc.promote) {
           const unsigned long long have = (unsigned long long)rays * (unsigned)lc.probe_spp, per = (unsigned long long)k;
           if (have >= thr16 * per) cls = have >= thr64 * per ? 64 : have >= thr32 * per ? 32 : 16;
         }
-        depth = 0;
+        depth = DEFER ? kOwesBit : 0;  // (DEFER: depth 0, normalisation owed)
         active = true;
+      }
+    }
+    // The one site of normalize(normalize(v)): the camera rays formed just above and the Lambertian directions the
+    // last iteration left raw (nothing between its bottom and this line reads d).  A wave pays for a divergent block
+    // once however few lanes are in it, so two sites cost two issues of the same arithmetic per iteration.  Each value
+    // still goes through the operations it went through, in their order: unit3_rn_twice is a pure function of its
+    // argument, and its wave-uniform __all only chooses between two forms that both round correctly, so which other
+    // lanes share the call cannot change a bit.  Metal, dielectric, the caller's rays and take_item's first ray
+    // normalise once, where they are formed, and never set the mark; a lane that owes is active and reaches this line
+    // before the depth limit can end its path, so no mark outlives its ray.
+    if constexpr (DEFER) {
+      if (depth < 0) {
+        d = unit3_rn_twice(d);
+        depth &= ~kOwesBit;
       }
     }
     if (!__any(active)) {
@@ -845,7 +866,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 float sum;
                 V3 s = ball_sample(rng, sum);
                 s = sampler_on_sphere(s, sum);  // l = (float)pow((double)sum, 0.5); vec /= l (lambertian.cu:25-29)
-                nd = unit3_rn_twice(s + nrm);   // normalize(S + n), then Ray's constructor (lambertian.cu:41-42)
+                // normalize(S + n), then Ray's constructor (lambertian.cu:41-42) (DEFER: at the top of the loop)
+                nd = DEFER ? s + nrm : unit3_rn_twice(s + nrm);
                 scattered = true;
               }
             } else if (m.kind == MAT_METAL) {  // metal.cu:12-25
@@ -884,8 +906,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 smem[ids_offset(depth)] = (uint8_t)mat;
               }
               depth++;
+              if (DEFER && m.kind == MAT_LAMBERTIAN) depth |= kOwesBit;  // (every Lambertian bounce that scatters left nd raw)
               o = p;
-              d = nd;  // (normalised by Ray's constructor in its material's branch above)
+              d = nd;  // (normalised by Ray's constructor in its material's branch above; DEFER, Lambertian: owed)
               ended = false;
             }
           }

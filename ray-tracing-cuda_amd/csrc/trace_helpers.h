@@ -124,7 +124,10 @@ __device__ __forceinline__ V3 unit3_rn(V3 v) {
 
 // normalize(normalize(v)) -- Camera::RayAt then Ray's constructor (camera.cu:69, ray.cu:10), Lambertian::Scatter
 // then Ray's constructor (lambertian.cu:41-42) -- with ONE domain check: when v.v passes it the first result has
-// 1 - 2^-22 < u.u < 1 + 2^-22, which is inside both short forms' domains.
+// 1 - 2^-22 < u.u < 1 + 2^-22, which is inside both short forms' domains.  One caller: the top of render_body's loop,
+// for the camera rays it has just formed and the Lambertian directions the iteration before left raw, in one issue.
+// A pure function of v: the wave-uniform check only picks between two forms that both round correctly, so the lanes
+// that share a call do not matter to any of them.
 __device__ __forceinline__ V3 unit3_rn_twice(V3 v) {
 #if RTMI_OPT_SQRT
   const float dd = dot3(v, v);

@@ -20,8 +20,10 @@ for ROUND in $(seq 1 $ROUNDS); do
     LIB=$ROOT/ray-tracing-cuda_amd/lib/librtmi_$LIBN.so
     [ "$LIBN" = base ] && LIB=$ROOT/ray-tracing-cuda_amd/lib/librtmi.so
     ENVS=("${PARTS[@]:1}")
-    env RTMI_LIB_PATH=$LIB "${ENVS[@]}" python3 $ROOT/bench.py $WL 2>/dev/null | python3 -c "
+    # (one run at a time under its own time limit; a run that fails or hangs ends the comparison: nothing more is started)
+    LINE=$(env RTMI_LIB_PATH=$LIB "${ENVS[@]}" timeout -k 10 ${AB_TIMEOUT:-300} python3 $ROOT/bench.py $WL 2>/dev/null) || { echo "$NAME round $ROUND: bench.py ended with status $?"; exit 1; }
+    echo "$LINE" | python3 -c "
 import json,sys
-d=json.loads(sys.stdin.readline()); print('%-14s round $ROUND  kernel_ms %.2f  %.0f Mrays/s' % ('$NAME', d['config']['kernel_ms'], d['value']), flush=True)"
+d=json.loads(sys.stdin.readline()); print('%-14s round $ROUND  kernel_ms %.2f  %.0f Mrays/s' % ('$NAME', d['config']['kernel_ms'], d['value']), flush=True)" || exit 1
   done
 done
