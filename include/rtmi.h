@@ -318,7 +318,12 @@ typedef struct rtmi_render_opts {
   int32_t fast_path;         /* 0 default (1, or RTMI_FAST_PATH).  1 = a launch of a list-triangle scene whose run-time modes are all
                               * the common ones (at most 16 materials, the scene's tables staged in LDS, no signed colour, a
                               * power-of-two frame, every lane taking pixels, wave priorities on) uses a kernel compiled for
-                              * exactly those modes; -1 = every launch uses the general kernel.  Same pixels either way. */
+                              * exactly those modes; -1 = every launch uses the general kernel.  Same pixels either way.
+                              * Those kernels cull the world list against bounds that hold the distance slack of every ray
+                              * origin within 8 x the list's largest |coordinate| (max norm), so the camera must lie within
+                              * that reach (and 9 x that coordinate x 1e30 must be finite in binary32): asked at every launch
+                              * of the scene's current camera -- a camera moved beyond the reach by rtmi_camera_update gets
+                              * the general kernel from then on, at its rate, and rtmi_render_mode_ex reports fast_path 0. */
   void *d_scratch;           /* optional device memory for ALL per-call state (work-queue cursors, ray total,
                               * completion flag, the scheduler's buffers), owned by the caller, at least */
   size_t scratch_bytes;      /* rtmi_render_scratch_bytes(frame) bytes: with it, concurrent renders of one scene
@@ -346,7 +351,7 @@ int rtmi_render_mode_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_ren
 /* The rule behind that field, as a pure function (no device, no scene): which trace kernel a launch with these facts
  * gets -- 0 the general one, 1 the fast kernel that draws from the work queue, 2 the fast kernel that walks planned
  * chains.  facts = {fast path enabled, kernel variant (2: list triangles only), materials, material table staged in LDS,
- * pair records staged in LDS, no signed colour, determinants safe, width, height, lane stride, wave priorities on,
+ * pair records staged in LDS and the camera within the list cull's reach (rtmi_render_opts.fast_path), no signed colour, determinants safe, width, height, lane stride, wave priorities on,
  * planned chains, resumes a first pass, has the probe's tile costs}.  Every fast kernel needs: enabled, variant 2, 1..16
  * materials, both tables staged, no signed colour, safe determinants, width and height powers of two up to 2^20, lane
  * stride 1, priorities on; the chain kernel also a resumed pass with tile costs (else such a launch is the general

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 
 #include "../../include/rtmi.h"
@@ -461,7 +462,14 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   if ((rc = upload(s, s->runs, &d.runs))) return rc;
   if ((rc = upload(s, s->spheres, &d.spheres))) return rc;
   if ((rc = upload(s, s->tris, &d.tris))) return rc;
-  if ((rc = upload(s, s->pair_boxes, &d.pair_boxes))) return rc;
+  {
+    // one allocation: the PairBox records, then the PairSlab table of the same pairs (scene_dev.h: pair_slabs_of)
+    static_assert(sizeof(PairSlab) == sizeof(PairBox) && std::is_trivially_copyable<PairSlab>::value, "PairSlab records travel as PairBox");
+    std::vector<PairBox> both(s->pair_boxes);
+    both.resize(s->pair_boxes.size() + s->pair_slabs.size());
+    if (!s->pair_slabs.empty()) memcpy(both.data() + s->pair_boxes.size(), s->pair_slabs.data(), s->pair_slabs.size() * sizeof(PairSlab));
+    if ((rc = upload(s, both, &d.pair_boxes))) return rc;
+  }
   // (the staging's source: a list beyond kLdsPairs is never staged and gathers from `tris`)
   if ((int)s->pair_pts.size() <= kLdsPairs && (rc = upload(s, s->tri_pts, &d.tri_pts))) return rc;
   if ((rc = upload(s, s->tri_nrm, &d.tri_nrm))) return rc;
@@ -574,6 +582,31 @@ int64_t rtmi_debug_list_records(const rtmi_scene *sp, int64_t cap_pairs, uint32_
     if (corners) memcpy(corners + 12 * i, tmp.pair_pts[i].p0, 12 * sizeof(float));
   }
   return n;
+}
+
+// Diagnostic (as above): the slab table of the same pairs (scene_dev.h: PairSlab), padding record included: returns the
+// number of records, fills the first cap of them (8 words each) and *list_mag (the scene's, which scales the table's
+// widening).  Any output may be null.
+int64_t rtmi_debug_pair_slabs(const rtmi_scene *sp, int64_t cap, uint32_t *slabs, uint32_t *boxes, float *list_mag) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
+  const int64_t n = (int64_t)tmp.pair_slabs.size();
+  for (int64_t i = 0; i < n && i < cap; i++) {
+    if (slabs) memcpy(slabs + 8 * i, &tmp.pair_slabs[i], sizeof(PairSlab));
+    if (boxes) memcpy(boxes + 8 * i, &tmp.pair_boxes[i], sizeof(PairBox));
+  }
+  if (list_mag) *list_mag = tmp.list_mag;
+  return n;
+}
+
+// Diagnostic (as above): 1 when the slab table's reach covers a render from the scene's camera (kernels.hip:
+// slab_reach_covers, a condition of the fast list kernels), else 0.
+int rtmi_debug_slab_reach(const rtmi_scene *sp) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
+  return slab_reach_covers(tmp.list_mag, tmp.cam) ? 1 : 0;
 }
 
 // Diagnostic (as above): bytes of dynamic LDS one workgroup of `threads` lanes asks for when this scene is rendered at

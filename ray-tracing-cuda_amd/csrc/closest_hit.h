@@ -134,15 +134,22 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   // a margin of 1e-5, not 1e-7), and -(o +- delta)/d per axis, delta = the distance slack of the mesh search
   // the culled list scan is on when the wave has its task region (ll) and the scene has pair records; the triangles'
   // records come from LDS when the list was short enough to be staged (s_tris), else from sc.tris in global memory
+  constexpr bool SLAB = culls_by_slab(M);  // (kernels.h) the pair test in centre / half-extent form
   const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
   if ((F & F_TRIS) && cull_list) {
     const float ix = __builtin_amdgcn_rcpf(d.x), iy = __builtin_amdgcn_rcpf(d.y), iz = __builtin_amdgcn_rcpf(d.z);
     cull_inv = mk(fabsf(d.x) < 1e-30f ? copysignf(1e30f, d.x) : ix, fabsf(d.y) < 1e-30f ? copysignf(1e30f, d.y) : iy,
                   fabsf(d.z) < 1e-30f ? copysignf(1e30f, d.z) : iz);
-    const float delta = MESH_DIST_SLACK * (fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) + sc.list_mag);
-    cull_klo = mk(-(o.x + delta) * cull_inv.x, -(o.y + delta) * cull_inv.y, -(o.z + delta) * cull_inv.z);  // lower planes, moved out
-    cull_khi = mk(-(o.x - delta) * cull_inv.x, -(o.y - delta) * cull_inv.y, -(o.z - delta) * cull_inv.z);  // upper planes
+    if (SLAB) {
+      // the kernels of the common list frame: k = -o / d alone.  The slack is in the PairSlab table's half extents, for
+      // every origin within kOriginReach x list_mag (the host has checked the camera: kernels.hip, fast_path_facts)
+      cull_klo = mk(-o.x * cull_inv.x, -o.y * cull_inv.y, -o.z * cull_inv.z);
+    } else {
+      const float delta = MESH_DIST_SLACK * (fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) + sc.list_mag);
+      cull_klo = mk(-(o.x + delta) * cull_inv.x, -(o.y + delta) * cull_inv.y, -(o.z + delta) * cull_inv.z);  // lower planes, moved out
+      cull_khi = mk(-(o.x - delta) * cull_inv.x, -(o.y - delta) * cull_inv.y, -(o.z - delta) * cull_inv.z);  // upper planes
+    }
   }
 
   for (int ri = 0; ri < sc.n_runs; ri++) {
@@ -196,25 +203,45 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
     const float le = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));                                            \
     cull_step(mask, fmaxf(lo0, en), fminf(hi0, le));                                                                            \
   }
-        f32x8 A = load_pair_box(sc.pair_boxes, pair0 + c0), B;
+        // The slab form (SLAB: a PairSlab record, c[3] then h[3]): the centre plane's time tc = c / d - o / d, then
+        // near / far = tc -+ h |1 / d| -- near <= far by construction, so nothing is sorted, and h holds every slack
+        // (scene.hip: pair_slab).  max3 / min3 drop a NaN operand and the compare keeps a NaN as a candidate
+        // (cull_step_nlt): what the arithmetic cannot decide is tested.  An unbounded pair (c = 0, h = inf) gives
+        // tc = k, finite, and -inf / +inf.
+#define RTMI_CULL_SLAB(bx)                                                                                                      \
+  {                                                                                                                             \
+    const float tcx = __builtin_fmaf(bx[0], cull_inv.x, cull_klo.x), tcy = __builtin_fmaf(bx[1], cull_inv.y, cull_klo.y),       \
+                tcz = __builtin_fmaf(bx[2], cull_inv.z, cull_klo.z);                                                            \
+    const float nx = __builtin_fmaf(-bx[3], fabsf(cull_inv.x), tcx), fx = __builtin_fmaf(bx[3], fabsf(cull_inv.x), tcx);        \
+    const float ny = __builtin_fmaf(-bx[4], fabsf(cull_inv.y), tcy), fy = __builtin_fmaf(bx[4], fabsf(cull_inv.y), tcy);        \
+    const float nz = __builtin_fmaf(-bx[5], fabsf(cull_inv.z), tcz), fz = __builtin_fmaf(bx[5], fabsf(cull_inv.z), tcz);        \
+    const float en = fmaxf(fmaxf(nx, ny), nz), le = fminf(fminf(fx, fy), fz);                                                   \
+    cull_step_nlt(mask, fminf(hi0, le), fmaxf(lo0, en));                                                                        \
+  }
+#define RTMI_CULL_ONE(bx)  \
+  if (SLAB) RTMI_CULL_SLAB(bx) else RTMI_CULL_PAIR(bx)
+        const PairBox *const recs = sc.pair_boxes;  // (SLAB: the launch's block points it at the PairSlab table, scene_dev.h)
+        f32x8 A = load_pair_box(recs, pair0 + c0), B;
         int i = 0;
         for (; i + 1 < nc; i += 2) {
           __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): see the plain scan below
           __builtin_amdgcn_sched_barrier(0);
-          B = load_pair_box(sc.pair_boxes, pair0 + c0 + i + 1);
+          B = load_pair_box(recs, pair0 + c0 + i + 1);
           __builtin_amdgcn_sched_barrier(0);
-          RTMI_CULL_PAIR(A)
+          RTMI_CULL_ONE(A)
           __builtin_amdgcn_s_waitcnt(0xc07f);
           __builtin_amdgcn_sched_barrier(0);
-          A = load_pair_box(sc.pair_boxes, pair0 + c0 + i + 2);  // (one inert record of padding at the end)
+          A = load_pair_box(recs, pair0 + c0 + i + 2);  // (one inert record of padding at the end)
           __builtin_amdgcn_sched_barrier(0);
-          RTMI_CULL_PAIR(B)
+          RTMI_CULL_ONE(B)
         }
         if (i < nc) {
           __builtin_amdgcn_s_waitcnt(0xc07f);
           __builtin_amdgcn_sched_barrier(0);
-          RTMI_CULL_PAIR(A)
+          RTMI_CULL_ONE(A)
         }
+#undef RTMI_CULL_ONE
+#undef RTMI_CULL_SLAB
 #undef RTMI_CULL_PAIR
         mask = __brev(mask) >> (32 - nc);  // bit i = pair i of the chunk (1 <= nc <= 32)
         if (!live) mask = 0u;  // a lane without a ray of its own only helps

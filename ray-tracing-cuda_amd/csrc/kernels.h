@@ -75,6 +75,12 @@ constexpr uint32_t kFastQueue = kFastCommon | PIN_QUEUE;    // a first pass, a q
 // budget and feature kernels keep both sites and compile to what they were: their registers moved both ways with the
 // deferral (NOTES.md, "Deferred normalisation") and no benchmark line runs them long enough to tell a 2 % from noise.
 constexpr bool defers_unit(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+// The culled list scan of the same kernels tests each pair in centre / half-extent form against the PairSlab table
+// (scene_dev.h), whose half extents hold the distance slack of every origin within kOriginReach x list_mag: three FMAs
+// per axis, no per-ray slack and no sorting of near and far (closest_hit.h).  The host has checked the reach for this
+// launch's camera (fast_path_facts: pairs_in_lds).  Every other kernel keeps PairBox and the per-ray slack, and
+// compiles to what it was.
+constexpr bool culls_by_slab(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
 // Everything the fast kernels take for granted, as the call's plan knows it (capi.hip: plan_render).  One predicate for
 // the plan, which the launch and rtmi_render_mode both read, and for the tests (rtmi_fast_path_kernel).
 struct FastPathFacts {
@@ -82,7 +88,9 @@ struct FastPathFacts {
   uint32_t variant;      // the kernel variant (pick_variant)
   int n_mats;            // materials of the scene
   int mats_in_lds;       // the material table is staged (LaunchCfg::lds_mats > 0)
-  int pairs_in_lds;      // pair corners and normals are staged and the culled scan shares its tests (pairs_off, nrm_off, list_off >= 0)
+  int pairs_in_lds;      // pair corners and normals are staged, the culled scan shares its tests (pairs_off, nrm_off,
+                         // list_off >= 0), and the slab table's reach covers this camera: |position|inf <= kOriginReach x
+                         // list_mag, with (kOriginReach + 1) x list_mag x 1e30 finite in binary32
   int unsigned_colours;  // SceneDev::unsigned_colours
   int det_safe;          // SceneDev::det_safe
   int width, height;
@@ -97,6 +105,8 @@ uint32_t fast_path_mode(const FastPathFacts &f);
 // The facts that are known before the launch shape is (scene, frame, switch); the plan adds the lane stride and each
 // launch's last four.
 FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled);
+// The slab table's reach covers a render from this camera (part of FastPathFacts::pairs_in_lds; host arithmetic only).
+bool slab_reach_covers(float list_mag, const CameraDev &cam);
 // Dynamic LDS of one workgroup of a render launch (host arithmetic only: the counts of `sc`, fr.max_depth).
 size_t render_lds_bytes(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads);
 // What the scheduler's probe pass leaves for the real pass (device pointers, all optional).

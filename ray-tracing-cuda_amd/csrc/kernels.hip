@@ -46,6 +46,8 @@
 
 #include "kernels.h"
 
+#include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <iterator>
 #include <type_traits>
@@ -697,12 +699,23 @@ uint32_t fast_path_mode(const FastPathFacts &f) {
   if (!f.chains) return kFastQueue;
   return f.resumed && f.tile_cost ? kFastChains : 0u;
 }
+// What the kernels that cull against the PairSlab table (kernels.h: culls_by_slab) assume of every ray they trace:
+// |o|inf <= kOriginReach * list_mag.  A render's origins are the camera position and points on list triangles (variant
+// F_TRIS alone: no lens, no other primitives), so the camera decides; the second condition keeps k = -o / d and
+// tc = fma(c, 1 / d, k) finite under the reciprocals clamped to 1e30 (closest_hit.h).
+bool slab_reach_covers(float list_mag, const CameraDev &cam) {
+  const float reach = kOriginReach * list_mag;
+  const bool cam_in_reach = fabsf(cam.position.x) <= reach && fabsf(cam.position.y) <= reach && fabsf(cam.position.z) <= reach;
+  const bool k_finite = (double)(kOriginReach + 1.0f) * (double)list_mag * 1e30 < (double)FLT_MAX;
+  return cam_in_reach && k_finite;
+}
 FastPathFacts fast_path_facts(uint32_t variant, const SceneDev &sc, const FrameDev &fr, int threads, int enabled) {
   size_t lds = 0;
   const LaunchCfg lc = make_cfg(variant, sc, fr, threads, &lds);
   FastPathFacts f{};
   f.enabled = enabled, f.variant = variant, f.n_mats = sc.n_mats, f.mats_in_lds = lc.lds_mats > 0 && lc.wide_ids == 2;
-  f.pairs_in_lds = lc.pairs_off >= 0 && lc.nrm_off >= 0 && lc.list_off >= 0;
+  // staged, shared tests, and the slab table's reach covers this camera (asked per launch of the scene's current camera)
+  f.pairs_in_lds = lc.pairs_off >= 0 && lc.nrm_off >= 0 && lc.list_off >= 0 && slab_reach_covers(sc.list_mag, sc.cam);
   f.unsigned_colours = sc.unsigned_colours, f.det_safe = sc.det_safe, f.width = fr.width, f.height = fr.height;
   return f;
 }
@@ -814,6 +827,10 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
       const bool chains = fast == kFastChains && !probe && lc.chain_next && lc.tile_cost && fr.k_begin > 0 && d_ray_counts;
       const bool queue = fast == kFastQueue && !lc.chain_next;
       if (fast != 0u && (!lc.prio_tab || lc.lane_stride != 1 || !(chains || queue))) return hipErrorInvalidValue;
+      // the three kernels below cull against the PairSlab table (kernels.h: culls_by_slab) and read it where the others
+      // read the PairBox records (scene_dev.h: PairSlab)
+      static_assert(culls_by_slab(kFastChains) && culls_by_slab(kFastQueue) && !culls_by_slab(0u), "which kernels read the slab table");
+      if (chains || queue) rp.sc.pair_boxes = pair_slabs_of(sc.pair_boxes, sc.n_pairs);
       if (chains) return launch_block<render_kernel<F, kFastChains>>(at, rp, dp);
       if (queue && !probe) return launch_block<render_kernel<F, kFastQueue>>(at, rp, dp);
       if (queue) return launch_block<probe_kernel<F, kFastQueue>>(at, rp, dp);

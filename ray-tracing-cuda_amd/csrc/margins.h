@@ -32,6 +32,18 @@
 //   distance slack (spheres)     kSphDistSlack (|o|inf + mag)   2^-9 >= 7.75e-4 sqrt(3) = 1.34e-3
 //   sphere member box            |r| (1 + kSphRadiusPad)        the binary64 radius against binary32 bounds
 //
+//   slab table of the pinned     h' = half extent + fixed pad   the world-list cull of the kernels compiled for the common list
+//   list kernels (PairSlab)      + delta_c + r_c + |c - c32|,   frame (kernels.h: culls_by_slab) tests centre -+ h' and applies
+//                                rounded up;                    no per-ray slack.  delta_c = kDistSlack (kOriginReach + 1) mag
+//                                every origin within            is the per-ray slack at the edge of the reach and above it
+//                                kOriginReach mag (max norm)    inside.  r_c = kSlabRoundEps eps (kOriginReach + 1) mag covers
+//                                                               the test's own arithmetic: k = -o inv, tc = fma(c, inv, k),
+//                                                               near / far = fma(-+h', |inv|, tc) round once each, at most eps
+//                                                               of (|o| + |c| + h') |inv| <= (kOriginReach + 2.01) mag |inv|,
+//                                                               and v_rcp's 1 ulp scales an axis' times by 2 eps of the same:
+//                                                               5 (kOriginReach + 2.01) eps mag in space, 50 eps mag at a
+//                                                               reach of 8 against the 72 provided (mag: the list's)
+//
 // The first and the last-but-two rows are measurements, not theorems; what holds them to account is the every-query
 // check build (tests/test_gpu_margins.py): every query answered a second time without any of this, 0 disagreements.
 #pragma once
@@ -53,16 +65,26 @@ constexpr float kSphDiscRel = 1e-5f;            // binary32 discriminant below -
 constexpr float kSphDistSlack = 0x1p-9f;        // spheres: per-axis widening as a fraction of (|o|inf + mag)
 constexpr float kSphRadiusPad = 0x1p-10f;       // a member's own box: |radius| (1 + this)
 constexpr float kSqrt3 = 1.7320508f;            // |x|_2 <= sqrt(3) |x|_inf
+constexpr float kOriginReach = 8.0f;            // slab table: ray origins lie within this x the list's largest |coordinate|
+constexpr float kSlabRoundEps = 8.0f;           // slab table: h' carries this x eps x (kOriginReach + 1) mag for the test's rounding
 
 static_assert(kDistSlack >= kReachProvided * kEps32 / kThinSine, "the distance slack must provide 8 eps / sin(theta) down to the thin-face limit");
 static_assert(kReachProvided >= kReachMeasured * kSqrt3, "the provision must cover the measured reach with D taken in the max norm");
 static_assert(kPadOfExtent >= kReachMeasured * kEps32 / kThinSine * 4.0f, "the fixed pad covers the reach at distances of the bounds' own size");
 static_assert(kPadOfMagnitude >= 8.0f * kEps32, "the fixed pad covers the rounding of the slab arithmetic (a reciprocal and an FMA per plane)");
+static_assert(kSlabRoundEps * (kOriginReach + 1.0f) >= 5.0f * (kOriginReach + 2.01f),
+              "the slab table's rounding term covers three roundings and the reciprocal's 2 eps of (|o| + |c| + h') at an origin kOriginReach mag out");
+static_assert(kOriginReach >= 1.0f, "origins on the list's own triangles must be within the slab table's reach");
 static_assert(kSphDistSlack >= kSphReach * kSqrt3, "the sphere groups' slack must cover the binary32 pre-test's reach");
 static_assert(kTimeLo < 1.0f - 64.0f * kEps32 && kTimeHi > 1.0f + 64.0f * kEps32 && kSlabTimeRel > 64.0f * kEps32,
               "the time fudges must be far above the few-eps disagreement of two operation orders");
 
 // The fixed pad of a set of bounds (the same expression wherever bounds are padded).
 inline float fixed_pad(float diag, float mag) { return kPadOfExtent * diag + kPadOfMagnitude * mag + kPadFloor; }
+
+// What a PairSlab's half extent carries beyond its PairBox, in binary64: delta_c + r_c of the table above.
+inline double slab_widening(float list_mag) {
+  return ((double)kDistSlack + (double)kSlabRoundEps * (double)kEps32) * ((double)kOriginReach + 1.0) * (double)list_mag;
+}
 
 }  // namespace rtmi

@@ -67,6 +67,7 @@ struct Scene {
   std::vector<SphereRec> spheres;
   std::vector<HotTri> tris;
   std::vector<PairBox> pair_boxes;
+  std::vector<PairSlab> pair_slabs;  // record for record the same pairs (and padding) in centre / half-extent form
   std::vector<PairPts> pair_pts;  // host only: the pairs' corners (check_margins)
   std::vector<TriPts> tri_pts;    // two per pair
   std::vector<TriNrm> tri_nrm;

@@ -87,6 +87,29 @@ static void push_pair(Scene &s, const V3 *p, int n) {
   s.pair_boxes.push_back(bx);
 }
 
+// A pair's PairSlab (scene_dev.h) from its PairBox, whose corners hold the fixed pad: in binary64, the box widened by the
+// distance slack at the edge of the reach and by the slab test's rounding (margins.h: slab_widening), the centre
+// rounded to binary32 and the half extent measured from the rounded centre, rounded up.
+static PairSlab pair_slab(const PairBox &bx, float list_mag) {
+  PairSlab r{};
+  const double widen = slab_widening(list_mag);
+  for (int a = 0; a < 3; a++) {
+    const double lo = (double)bx.mn[a] - widen, hi = (double)bx.mx[a] + widen;
+    const float c = (float)((lo + hi) / 2);
+    const double h = std::fmax(hi - (double)c, (double)c - lo);
+    float hf = (float)h;
+    if ((double)hf < h) hf = nextafterf(hf, INFINITY);
+    r.c[a] = c, r.h[a] = hf;
+  }
+  // unbounded (push_pair: a thin triangle), or too large for the arithmetic above: a candidate of every ray -- with
+  // c = 0 the slab test's near and far times are -+inf whatever the ray (its k is finite: kernels.hip, fast_path_facts)
+  bool bounded = true;
+  for (int a = 0; a < 3; a++) bounded = bounded && std::isfinite(r.c[a]) && std::isfinite(r.h[a]);
+  if (!bounded)
+    for (int a = 0; a < 3; a++) r.c[a] = 0.f, r.h[a] = INFINITY;
+  return r;
+}
+
 // parallelogram.cu:10-15 + the two triangles of parallelogram.cu:25,33
 static void push_pgram(Scene &s, V3 p0, V3 p1, V3 p2, int mat) {
   std::vector<HotTri> &out = s.tris;
@@ -573,7 +596,7 @@ static int build_bvh_nodes(std::vector<BvhNode> &nodes, std::vector<FacePts> &fp
 }
 
 std::string Scene::flatten() {
-  pair_boxes.clear(), pair_pts.clear(), tri_pts.clear(), tri_nrm.clear(), list_mag = 0.f;
+  pair_boxes.clear(), pair_slabs.clear(), pair_pts.clear(), tri_pts.clear(), tri_nrm.clear(), list_mag = 0.f;
   sph_groups.clear(), sph_members.clear(), sph_mag = 0.f;
   sliver_faces = 0;
   runs.clear(), spheres.clear(), tris.clear(), bvh_recs.clear(), face_of_orig.clear(), nodes.clear(), qnodes.clear(), faces.clear(), leaf_paths.clear(), tops.clear(),
@@ -875,6 +898,9 @@ std::string Scene::flatten() {
     tris.push_back(HotTri{});
     tris.push_back(HotTri{});
     pair_boxes.push_back(PairBox{});
+    // the same pairs for the kernels that cull in centre / half-extent form (list_mag is final here), padding included
+    for (size_t i = 0; i + 1 < pair_boxes.size(); i++) pair_slabs.push_back(pair_slab(pair_boxes[i], list_mag));
+    pair_slabs.push_back(PairSlab{});
   }
   n_spheres = (int)spheres.size();
   if (!spheres.empty()) spheres.push_back(SphereRec{});  // same for the sphere look-ahead
@@ -910,6 +936,17 @@ std::string Scene::check_margins() const {
         return "margin budget: a world-list pair's bounds do not cover what its triangle tests can accept";
     }
     if (!(mag <= list_mag)) return "margin budget: list_mag is below a pair's coordinates";
+    // the pair's PairSlab: unbounded with the box; else [c - h, c + h] contains the box (which holds the fixed pad) widened
+    // by the slack and rounding terms of margins.h (binary64; 2^-40 of the widening for this comparison's own rounding)
+    if (pair_slabs.size() != pair_boxes.size()) return "margin budget: the slab table is out of step with the pair bounds";
+    const PairSlab &sl = pair_slabs[i];
+    const double widen = slab_widening(list_mag) * (1.0 - 0x1p-40);
+    for (int a = 0; a < 3; a++) {
+      if (thin ? !(sl.c[a] == 0.f && sl.h[a] == INFINITY)
+               : !(((double)sl.c[a] - (double)sl.h[a] <= (double)bx.mn[a] - widen && (double)sl.c[a] + (double)sl.h[a] >= (double)bx.mx[a] + widen) ||
+                   (sl.c[a] == 0.f && sl.h[a] == INFINITY)))
+        return "margin budget: a world-list pair's slab record does not cover its bounds at the edge of the origin reach";
+    }
   }
   // a TriPts record is the head of its HotTri, bit for bit: the staged and the gathered scan test the same operands
   if (tri_pts.size() != 2 * pair_pts.size() || tris.size() < tri_pts.size()) return "world list: triangle records out of step";

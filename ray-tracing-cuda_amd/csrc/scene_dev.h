@@ -87,6 +87,20 @@ struct PairBox {  // 32 B
   float mn[3], mx[3];
   int32_t pad[2];
 };
+// The pair's bounds once more for the kernels compiled for the common list frame (kernels.h: culls_by_slab), which test
+// centre -+ half extent and apply no per-ray slack: h holds the PairBox's fixed pad, the distance slack of an origin
+// kOriginReach x list_mag out and the test's own rounding (margins.h; scene.hip: pair_slab), rounded up.  An unbounded
+// pair is c = 0, h = +inf.  The table lies in the allocation of `pair_boxes`, behind its padding record: record i at
+// pair_boxes + n_pairs + 1 + i (pair_slabs_of), one inert record of padding at its end too.  SceneDev, which every
+// kernel's argument block begins with, keeps its layout: a launch of one of those kernels writes the table's address
+// into its block's `pair_boxes` (kernels.hip: launch_render) -- they never read a PairBox, and read the records as they
+// would read those, eight words at a wave-uniform index: no register holds a second base or the pair count.
+struct PairSlab {  // 32 B
+  float c[3], h[3];
+  int32_t pad[2];
+};
+static_assert(sizeof(PairSlab) == sizeof(PairBox), "the slab table is addressed in PairBox records");
+inline const PairBox *pair_slabs_of(const PairBox *boxes, int32_t n_pairs) { return boxes + n_pairs + 1; }
 struct alignas(16) TriPts {  // 48 B
   float p0[3], e1[3], e2[3];
   int32_t flags;
@@ -232,7 +246,8 @@ struct SceneDev {
   const Run *runs;
   const SphereRec *spheres;
   const HotTri *tris;  // one inert record of padding follows the last (prefetch target)
-  const PairBox *pair_boxes;  // per pair of `tris` records (index = tri index / 2), one inert record of padding
+  const PairBox *pair_boxes;  // per pair of `tris` records (index = tri index / 2), one inert record of padding; then
+                              // the PairSlab table of the same pairs
   const SphGroup *sph_groups;  // per grouped sphere run: Run::pad = its first group, (count + 15) / 16 groups
   const SphMember *sph_members;
   float sph_mag;               // largest |coordinate| of the grouped spheres' bounds (scales the distance slack)

@@ -645,6 +645,23 @@ class SceneBuilder:
         _check(fn(self.h, n, tp.ctypes.data_as(_u32p), ht.ctypes.data_as(_u32p), co.ctypes.data_as(_fp)), "rtmi_debug_list_records")
         return tp, ht, co
 
+    def pair_slabs(self):
+        """The pairs' bounds in both forms (rtmi_debug_pair_slabs): (slabs float32 (P + 1, 8): c[3], h[3], two spare
+        words; boxes float32 (P + 1, 8): mn[3], mx[3], two spare words; list_mag) for the P pairs of the world list and
+        the padding record behind them.  Host only."""
+        fn = self.L.rtmi_debug_pair_slabs
+        fn.restype, fn.argtypes = C.c_int64, [C.c_void_p, C.c_int64, _u32p, _u32p, _fp]
+        n = _check(fn(self.h, 0, None, None, None), "rtmi_debug_pair_slabs")
+        sl, bx, mag = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32), np.zeros(1, np.float32)
+        _check(fn(self.h, n, sl.ctypes.data_as(_u32p), bx.ctypes.data_as(_u32p), mag.ctypes.data_as(_fp)), "rtmi_debug_pair_slabs")
+        return sl.view(np.float32), bx.view(np.float32), float(mag[0])
+
+    def slab_reach(self):
+        """Whether the slab table's reach covers a render from this scene's camera (rtmi_debug_slab_reach).  Host only."""
+        fn = self.L.rtmi_debug_slab_reach
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return bool(_check(fn(self.h), "rtmi_debug_slab_reach"))
+
     def render_lds_bytes(self, max_depth, threads=256):
         """Dynamic LDS per workgroup of a render of this scene (rtmi_debug_render_lds_bytes).  Host only."""
         fn = self.L.rtmi_debug_render_lds_bytes
