@@ -225,6 +225,34 @@ int rtmi_last_ray_total(const rtmi_scene *s, uint64_t *out_rays, void *stream);
 int rtmi_debug_counters(const rtmi_scene *s, unsigned long long out[RTMI_COUNTER_WORDS], void *stream);
 int rtmi_debug_counters_ex(const rtmi_scene *s, const void *d_scratch, unsigned long long out[RTMI_COUNTER_WORDS],
                            void *stream);
+/* Diagnostic (added without a version change): the byte offsets of the regions of a frame's render scratch
+ * (rtmi_render_scratch_bytes), in the order the library lays them out; out receives the first min(n,
+ * RTMI_SCRATCH_REGIONS).  Host arithmetic only: no device, no scene.
+ *   [0] states   the probe's RNG states; a resumed frame: the first pass's ray counts, marked (uint32[items])
+ *   [1] rays     a discarded probe's ray counts, marked        [2] cost     per tile: rays of the first pass
+ *   [3] order    tiles, dearest cost bucket first              [4] meta     32 words, see rtmi_debug_schedule
+ *   [5] head     the head list (16384 words)                   [6] work     the probe's work counts per item
+ *   [7] qcost    [8] qsorted   [9] qmap   per quarter tile: cost, dearest bucket first, the queue's order
+ *   [10] qmax    the largest quarter cost                      [11] fut  [12] next  [13] claims   per tile: the chain plan
+ *   [14] first   per chain: its first tile (32768 words)       [15] prio_tab  the wave-priority table
+ *   [16] params  the two kernel-argument blocks                [17] total     the size of the whole */
+#define RTMI_SCRATCH_REGIONS 18
+int rtmi_debug_scratch_regions(const rtmi_frame *f, int64_t out[], int n);
+/* Diagnostic (added without a version change): the scheduler step of a scheduled render -- what rtmi_render_ex runs
+ * between its first pass and the launch that finishes the frame, the same code -- on the caller's own inputs.  d_scratch:
+ * scratch_bytes >= rtmi_render_scratch_bytes(f) of device memory, whose regions receive the plan.  d_ray_counts: device
+ * uint32[64 x local tiles], the first pass's count per work item; with pixel_head != 0 the head's pixels get bit 31 set
+ * IN PLACE.  d_work_counts (nullable): device uint32 per work item; NULL: the queue follows the tile order, else the
+ * quarter tiles are sorted by work + rays and dealt as a snake.  sparse_cap, grid_waves, outlier_x10, head_pct: what a
+ * render derives from its grid and rtmi_render_opts.  simds x rounds chains are planned for a frame of spp samples
+ * after a first pass of probe_spp (simds * rounds == 0: no chain plan; at most 32768).  Leaves in meta: [0] the largest
+ * tile cost; [1] outlier tiles: sparse items -- or, with a pixel head, head entries, [2] [3] the ends of its first two
+ * classes; [16] the largest count, [18..19] the counts' sum, [20..22] the classes' sizes before the limits,
+ * [24..26] the classes' thresholds as used (0xffffffff: class dropped), [28..30] the scatter cursors.
+ * Argument errors are RTMI_ERR_INVALID before any device work.  Asynchronous on `stream`. */
+int rtmi_debug_schedule(const rtmi_frame *f, void *d_scratch, size_t scratch_bytes, uint32_t *d_ray_counts,
+                        const uint32_t *d_work_counts, int pixel_head, uint32_t sparse_cap, int grid_waves, int outlier_x10,
+                        const int32_t head_pct[3], int simds, int rounds, int spp, int probe_spp, void *stream);
 
 /* d_all_tiles holds the tile-major buffers of ranks 0..world_size-1 back to
  * back (what an RCCL gather to the root produces; world_size==1: the buffer

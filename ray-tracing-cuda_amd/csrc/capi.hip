@@ -987,6 +987,41 @@ static Scratch scratch_regions(void *base, const ScratchLayout &l) {
                  at(l.qmap), at(l.qmax), at(l.fut), at(l.claims), at(l.prio_tab), ints(l.next), ints(l.first)};
 }
 
+// The scheduler step: from a first pass's ray counts (and, optionally, its work counts) to what the finishing launch
+// walks -- the tile order, the head, the queue's order per quarter tile and, for planned chains, the chain plan with its
+// claims zeroed.  Which region of the scratch feeds which launcher is decided here and nowhere else: run_plan and
+// rtmi_debug_schedule both call it.
+struct SchedStep {
+  int tiles;                    // local tiles of the frame
+  bool pixel_head;              // the head is made of pixels in weight classes (r.head), not of outlier tiles
+  uint32_t sparse_cap;          // outlier tiles: work items the grid holds at one pixel per sparse stride
+  int waves, outlier_x10;       // waves of the grid; an outlier tile costs this many tenths of the mean
+  const int *head_pct;          // [3]: the weight classes' thresholds in per cent of the largest count
+  int simds, rounds;            // planned chains: SIMDs x waves per SIMD; simds * rounds == 0: no chain plan
+  int spp, probe_spp;           // chains: samples of the frame and of the first pass (chain_fut's scale)
+};
+static int schedule_step(const Scratch &r, uint32_t *rays, const uint32_t *work, const SchedStep &k, SchedPlan *plan,
+                         hipStream_t st) {
+  uint32_t *head = k.pixel_head ? r.head : nullptr;
+  HIP_TRY(launch_tile_order(rays, k.tiles, r.cost, r.meta, r.order, head, k.sparse_cap, k.waves, k.outlier_x10, k.head_pct, st));
+  // (the head's marks in rays are bit 31: quarter_cost_kernel masks them off)
+  HIP_TRY(launch_quarter_order(r.order, work, rays, k.tiles, r.qcost, r.qsorted, r.qmax, r.qmap, st));
+  plan->tile_order = r.qmap;
+  plan->sparse_items = r.meta + 1;
+  plan->head_list = head;
+  plan->probe_marks = head ? rays : nullptr;
+  plan->probe_spp = k.probe_spp;
+  plan->tile_cost = r.cost;
+  if ((int64_t)k.simds * k.rounds > 0) {
+    HIP_TRY(launch_chain_plan(r.order, r.cost, k.tiles, k.simds, k.rounds, k.spp, k.probe_spp, r.first, r.next, r.fut, st));
+    HIP_TRY(hipMemsetAsync(r.claims, 0, (size_t)k.tiles * 4, st));
+    plan->chain_next = r.next, plan->chain_fut = r.fut, plan->chain_first = r.first, plan->claims = r.claims;
+    plan->plan_simds = k.simds, plan->plan_rounds = k.rounds;
+    plan->tile_order = r.order;  // (per tile in this mode: the take-over's order)
+  }
+  return RTMI_OK;
+}
+
 // Executes a plan: resolves the scratch, then memsets, copies and launches in stream order.  Decides nothing.
 static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uint32_t *d_ray_counts, hipStream_t st) {
   const Scene *s = p.s;
@@ -1022,7 +1057,7 @@ static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uin
     HIP_TRY(hipMemsetAsync(plan.prio_tab, 0, kPrioTabBytes, st));
   }
   if (p.scheduled) {
-    const size_t n = (size_t)d.items, nt = (size_t)d.local_tiles;
+    const size_t n = (size_t)d.items;
     uint32_t *first_states = p.resume ? d_states : r.states;
     uint32_t *first_rays = p.resume && d_ray_counts ? d_ray_counts : r.rays;
     if (p.resume) ray_buf = first_rays;
@@ -1053,26 +1088,11 @@ static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uin
     // the head of a mesh frame's queue: pixels in weight classes (the default), or -- when the call names a
     // sparse stride, or RTMI_HEAD_CLASSES=0 -- the outlier tiles at one pixel per that many lanes
     const bool by_pixels = p.tune.head_classes != 0;
-    uint32_t *head = (p.ls.variant & F_BVH) && by_pixels ? r.head : nullptr;
-    HIP_TRY(launch_tile_order(rays, d.local_tiles, r.cost, r.meta, r.order, head, p.sparse_cap, p.waves, p.tune.outlier_x10,
-                              p.tune.head_pct, st));
-    // (the head's marks in rays are bit 31: quarter_cost_kernel masks them off)
-    HIP_TRY(launch_quarter_order(r.order, p.by_cost && by_pixels ? r.work : nullptr, rays, d.local_tiles, r.qcost, r.qsorted,
-                                 r.qmax, r.qmap, st));
-    plan.tile_order = r.qmap;
-    plan.sparse_items = r.meta + 1;
-    plan.head_list = head;
-    plan.probe_marks = head ? rays : nullptr;
-    plan.probe_spp = p.probe_spp;
-    plan.tile_cost = r.cost;
-    if (p.chains) {
-      HIP_TRY(launch_chain_plan(r.order, r.cost, d.local_tiles, p.plan_simds, p.plan_rounds, d.spp, p.probe_spp, r.first, r.next,
-                                r.fut, st));
-      HIP_TRY(hipMemsetAsync(r.claims, 0, nt * 4, st));
-      plan.chain_next = r.next, plan.chain_fut = r.fut, plan.chain_first = r.first, plan.claims = r.claims;
-      plan.plan_simds = p.plan_simds, plan.plan_rounds = p.plan_rounds;
-      plan.tile_order = r.order;  // (per tile in this mode: the take-over's order)
-    }
+    SchedStep k;
+    k.tiles = d.local_tiles, k.pixel_head = (p.ls.variant & F_BVH) && by_pixels;
+    k.sparse_cap = p.sparse_cap, k.waves = p.waves, k.outlier_x10 = p.tune.outlier_x10, k.head_pct = p.tune.head_pct;
+    k.simds = p.chains ? p.plan_simds : 0, k.rounds = p.chains ? p.plan_rounds : 0, k.spp = d.spp, k.probe_spp = p.probe_spp;
+    if (int rc = schedule_step(r, rays, p.by_cost && by_pixels ? r.work : nullptr, k, &plan, st)) return rc;
   }
   // The counter words (render_body.h, mesh_search.h; rtmi_debug_counters) before the launch that finishes the frame:
   //   [0]       work-queue cursor                                   zeroed (per launch)
@@ -1452,6 +1472,46 @@ int rtmi_debug_counters_ex(const rtmi_scene *sp, const void *d_scratch, unsigned
   HIP_TRY(hipMemcpyAsync(out, counters, kCounterBytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return RTMI_OK;
+}
+
+// Diagnostic: where the regions of a frame's render scratch lie (scratch_layout, in ScratchLayout's order).  Host only.
+int rtmi_debug_scratch_regions(const rtmi_frame *f, int64_t out[], int n) {
+  FrameDev d;
+  if (!f || !out || n < 0) return fail(RTMI_ERR_INVALID, "null argument");
+  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
+  const ScratchLayout l = scratch_layout(d);
+  const size_t at[RTMI_SCRATCH_REGIONS] = {l.states, l.rays,   l.cost, l.order, l.meta, l.head,   l.work,     l.qcost,  l.qsorted,
+                                           l.qmap,   l.qmax,   l.fut,  l.next,  l.claims, l.first, l.prio_tab, l.params, l.total};
+  static_assert(sizeof(ScratchLayout) == sizeof(at), "rtmi_debug_scratch_regions reports every region of ScratchLayout");
+  for (int i = 0; i < n && i < RTMI_SCRATCH_REGIONS; i++) out[i] = (int64_t)at[i];
+  return RTMI_OK;
+}
+
+// Diagnostic: the scheduler step of a scheduled render (schedule_step) on the caller's own counts, into the regions of
+// the caller's scratch.  Asynchronous on `stream`.
+int rtmi_debug_schedule(const rtmi_frame *f, void *d_scratch, size_t scratch_bytes, uint32_t *d_ray_counts,
+                        const uint32_t *d_work_counts, int pixel_head, uint32_t sparse_cap, int grid_waves, int outlier_x10,
+                        const int32_t head_pct[3], int simds, int rounds, int spp, int probe_spp, void *stream) {
+  FrameDev d;
+  if (!f || !d_scratch || !d_ray_counts || !head_pct) return fail(RTMI_ERR_INVALID, "null argument");
+  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
+  const ScratchLayout sl = scratch_layout(d);
+  if (scratch_bytes < sl.total) return fail(RTMI_ERR_INVALID, "scratch_bytes < rtmi_render_scratch_bytes(frame)");
+  for (int i = 0; i < 3; i++)
+    if (head_pct[i] < 0 || head_pct[i] > 100) return fail(RTMI_ERR_INVALID, "head_pct outside [0, 100]");
+  if (!(head_pct[0] >= head_pct[1] && head_pct[1] >= head_pct[2]))
+    return fail(RTMI_ERR_INVALID, "head_pct must not increase from the heaviest class to the lightest");
+  if (grid_waves < 0 || outlier_x10 < 0 || simds < 0 || rounds < 0) return fail(RTMI_ERR_INVALID, "negative argument");
+  if ((int64_t)simds * rounds > kMaxChains) return fail(RTMI_ERR_INVALID, "simds * rounds above the chain cap (32768)");
+  if ((int64_t)simds * rounds > 0 && (spp < 1 || probe_spp < 1)) return fail(RTMI_ERR_INVALID, "a chain plan needs spp and probe_spp of at least 1");
+  if (rtmi_device_count() <= 0) return fail(RTMI_ERR_NO_DEVICE, "no HIP device: librtmi has no CPU fallback");
+  const int pct[3] = {head_pct[0], head_pct[1], head_pct[2]};
+  SchedStep k;
+  k.tiles = d.local_tiles, k.pixel_head = pixel_head != 0;
+  k.sparse_cap = sparse_cap, k.waves = grid_waves, k.outlier_x10 = outlier_x10, k.head_pct = pct;
+  k.simds = simds, k.rounds = rounds, k.spp = spp, k.probe_spp = probe_spp;
+  SchedPlan plan;
+  return schedule_step(scratch_regions(d_scratch, sl), d_ray_counts, d_work_counts, k, &plan, (hipStream_t)stream);
 }
 
 #ifdef RTMI_STATS

@@ -179,6 +179,9 @@ SYMBOLS = [
     ("rtmi_last_ray_total", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     ("rtmi_debug_counters", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_void_p]),
     ("rtmi_debug_counters_ex", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong), C.c_void_p]),
+    ("rtmi_debug_scratch_regions", C.c_int, [_frp, C.POINTER(C.c_int64), C.c_int]),
+    ("rtmi_debug_schedule", C.c_int, [_frp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                      C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("rtmi_gather", C.c_int, [C.c_void_p, _frp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtmi_reduce_sum", C.c_int, [C.c_void_p, _frp, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtmi_untile", C.c_int, [_frp, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -259,6 +262,32 @@ def pixel_map(frame):
     _check(lib().rtmi_frame_pixel_map(C.byref(frame), out.ctypes.data_as(C.POINTER(C.c_int64))),
            "rtmi_frame_pixel_map")
     return out
+
+
+SCRATCH_REGIONS = ("states", "rays", "cost", "order", "meta", "head", "work", "qcost", "qsorted", "qmap", "qmax", "fut", "next",
+                   "claims", "first", "prio_tab", "params", "total")  # rtmi_debug_scratch_regions' order (RTMI_SCRATCH_REGIONS)
+
+
+def scratch_regions(frame):
+    """{region: byte offset} of a frame's render scratch, and its ``total`` size (rtmi_debug_scratch_regions; no GPU)."""
+    out = (C.c_int64 * len(SCRATCH_REGIONS))()
+    _check(lib().rtmi_debug_scratch_regions(C.byref(frame), out, len(SCRATCH_REGIONS)), "rtmi_debug_scratch_regions")
+    return dict(zip(SCRATCH_REGIONS, (int(v) for v in out)))
+
+
+def debug_schedule(frame, scratch, ray_counts, work_counts=None, pixel_head=False, sparse_cap=0, grid_waves=0, outlier_x10=20,
+                   head_pct=(50, 25, 12), simds=0, rounds=0, spp=1, probe_spp=1):
+    """The scheduler step of a scheduled render on the caller's own counts (rtmi_debug_schedule): ``scratch``, ``ray_counts``
+    and ``work_counts`` are torch CUDA tensors; the plan is left in ``scratch`` (``scratch_regions``), the head's marks in
+    ``ray_counts``.  On torch's current stream."""
+    import torch
+    with torch.cuda.device(scratch.device):
+        _check(lib().rtmi_debug_schedule(C.byref(frame), C.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size(),
+                                         C.c_void_p(ray_counts.data_ptr()),
+                                         C.c_void_p(work_counts.data_ptr()) if work_counts is not None else None,
+                                         1 if pixel_head else 0, int(sparse_cap), int(grid_waves), int(outlier_x10),
+                                         (C.c_int32 * 3)(*head_pct), int(simds), int(rounds), int(spp), int(probe_spp),
+                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rtmi_debug_schedule")
 
 
 def get_workload(rank, world_size, spp):
