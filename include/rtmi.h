@@ -505,6 +505,79 @@ int rtmi_trace(const rtmi_scene *s, int64_t n, const float *d_origins, const flo
  * Asynchronous on `stream`; n == 0 launches nothing. */
 int rtmi_rng_init_n(uint64_t seed, uint64_t first, int64_t n, void *d_states, void *stream);
 
+/* ------------------------------------------------------------ camera rays --
+ * The render's primary rays as a call of their own, and the fold of a traced sample into the budget buffers.  For every
+ * sample index `sample` = 0, 1, ... the three calls
+ *     rtmi_camera_rays(s, f, NULL, d_budget, sample, d_states, d_o, d_d, stream);
+ *     rtmi_trace(s, items, d_o, d_d, f->max_depth, d_states, d_rad, d_cnt, d_work, stream);
+ *     rtmi_sample_add(f, d_budget, sample, d_rad, d_cnt, d_sum, d_sq, d_samples, d_ray_counts, stream);
+ * compose bit for bit to rtmi_render_budget(s, f, d_budget, ...) -- sums, second moments, sample and ray counts, RNG
+ * states -- and so, from zeroed buffers and a null budget, to rtmi_render with post_process = 0.  Between the first two
+ * the caller holds the very rays of the frame's samples: for rtmi_intersect (object ids, world positions, any AOV), for
+ * rtmi_occluded (a shadow or AO pass on the primary hits), or to bend them.  With another projection the same loop
+ * renders a panoramic or fisheye frame into buffers that rtmi_budget_plan, rtmi_resolve*, rtmi_untile and rtmi_gather
+ * take as they are.  Added without a version change: a caller detects them by the symbol rtmi_camera_rays.
+ *
+ * All buffers are per shard and tile-major over items = rtmi_frame_work_items(f): d_origins, d_dirs, d_radiance, d_sum,
+ * d_sq float[items][3]; d_budget, d_trace_counts, d_samples, d_ray_counts uint32[items]; d_states the render's layout,
+ * RTMI_STATE_WORDS planes of uint32[items] -- which is rtmi_trace's layout with n = items.
+ *
+ * Active items (both entries): work item q is active iff it is a pixel of the shard (rtmi_frame_pixel_of >= 0) and
+ * sample < min(d_budget ? d_budget[q] : f->spp, f->spp) -- rtmi_render_budget's b = min(d_budget[q], f->spp).
+ *
+ * rtmi_camera_rays, inactive item: origin and direction are written as six +0.0f; the state is neither read nor
+ * written.  A zero direction is a ray rtmi_trace leaves out, so the caller never clears or masks anything.
+ * Active item, kind RTMI_PROJ_CAMERA (proj == NULL): exactly what the render kernel does for the next sample of that
+ * pixel from d_states --
+ *   - r1, then r2, each CudaRandomFloat(0, 1);  xf, yf the binary32 results of ray_tracing.cu:68-73 (yf from H - i);
+ *   - target = (llc + xf * horizontal) + yf * vertical;
+ *   - a defocus camera: the two lens draws CudaRandomFloat(0, lens_radius), then origin = position + u * ox + v * oy
+ *     (camera.cu:63-65,74-77); else origin = position;
+ *   - the direction written is normalize(target - origin), normalised ONCE: RayAt's result (camera.cu:69) before Ray's
+ *     constructor normalises again -- the direction rtmi_trace and rtmi_intersect document as reproducing a camera ray,
+ *     since they apply the second normalisation themselves;
+ *   - the state is advanced in place by exactly those 2 or 4 draws.
+ * The camera is read from the scene's host record at enqueue time and passed by value, as every render launch does: a
+ * call enqueued before an rtmi_camera_update keeps the camera it was enqueued with.
+ * The other kinds share r1, r2, xf, yf with CAMERA, make no lens draws, and use the camera's position, llc, horizontal,
+ * vertical and its frame u, v, w (the 21 floats of rtmi_camera_get):
+ *   - ORTHOGRAPHIC: origin = (llc + xf * horizontal) + yf * vertical, direction = normalize(-w); all binary32.
+ *   - EQUIRECT: origin = position.  In binary64 from the binary32 inputs: phi = (xf - 0.5) * 2 pi, theta = (yf - 0.5) * pi,
+ *     D = (cos theta * sin phi) * u + sin theta * v - (cos theta * cos phi) * w per component, each rounded once to
+ *     binary32, then normalised once in binary32.
+ *   - FISHEYE (equidistant): origin = position.  In binary64: sx = 2 xf - 1, sy = 2 yf - 1, r = sqrt(sx sx + sy sy).
+ *     r > 1: the direction is three +0.0f -- the item is still active and has made its two draws, so it receives
+ *     radiance 0 and counts as a sample: the black surround of the image circle.  r == 0: D = -w.  Otherwise
+ *     t = r * fov / 2, D = sin t * (sx / r) * u + sin t * (sy / r) * v - cos t * w; rounded once, normalised once.
+ *
+ * rtmi_sample_add, active item, with x = d_radiance[q][c]: d_sum[q][c] += x;  d_sq[q][c] += x * x (product and sum each
+ * rounded to binary32 on its own, no fused multiply-add);  d_samples[q] += 1;  d_ray_counts[q] += d_trace_counts[q]
+ * where both are non-null.  Inactive item: nothing of it is read or written.
+ *
+ * Both are asynchronous on `stream` and share no device state with any other call.  RTMI_ERR_INVALID before any HIP call
+ * for a null scene, a bad frame, a null required array (d_budget, d_trace_counts, d_sq, d_ray_counts are the optional
+ * ones), a wrong proj->size, non-zero reserved, a kind outside 0..3, a FISHEYE fov that is not finite or outside
+ * (0, 2 pi] (2 pi as binary32), kinds 1..3 on a camera whose u, v, w are not finite and orthonormal (in binary64, each
+ * | |x|^2 - 1 | <= 1e-3 and each pairwise |dot| <= 1e-3: a camera installed by rtmi_camera_raw or rtmi_camera_set may
+ * carry no frame), an uncommitted scene (rtmi_camera_rays); then also when the current device is not the scene's.
+ *
+ * rtmi_trace takes n <= 2^31 - 1.  A shard with more work items than that must be traced in slices: every buffer is a
+ * plain array, but the state planes keep the stride `items`, so such a caller traces each slice with state copies of
+ * its own (stride = the slice's length) and copies them back.  Not enforced here. */
+enum { RTMI_PROJ_CAMERA = 0, RTMI_PROJ_ORTHOGRAPHIC = 1, RTMI_PROJ_EQUIRECT = 2, RTMI_PROJ_FISHEYE = 3 };
+typedef struct rtmi_projection {
+  int32_t size;      /* sizeof(rtmi_projection) of the caller: must match */
+  int32_t kind;      /* RTMI_PROJ_* */
+  float fov;         /* FISHEYE: full angle of the image circle, radians, finite, 0 < fov <= 2 pi; other kinds: ignored */
+  int32_t reserved;  /* 0 */
+} rtmi_projection;
+int rtmi_camera_rays(const rtmi_scene *s, const rtmi_frame *f, const rtmi_projection *proj /* NULL = CAMERA */,
+                     const uint32_t *d_budget /* nullable */, uint32_t sample, void *d_states, float *d_origins,
+                     float *d_dirs, void *stream);
+int rtmi_sample_add(const rtmi_frame *f, const uint32_t *d_budget /* nullable */, uint32_t sample,
+                    const float *d_radiance, const uint32_t *d_trace_counts /* nullable */, float *d_sum,
+                    float *d_sq /* nullable */, uint32_t *d_samples, uint32_t *d_ray_counts /* nullable */, void *stream);
+
 /* ----------------------------------------------------------------- budget --
  * A render whose sample count is per pixel, a per-pixel error statistic to decide it from, and the two small kernels
  * that turn them into an adaptive render (plan a pass, render it, ... , resolve).  Added without a version change: a
@@ -576,8 +649,10 @@ int rtmi_resolve(const rtmi_frame *f, const float *d_sum, const uint32_t *d_samp
 /* --------------------------------------------------------------- features --
  * First-hit feature buffers for a denoiser or compositor: albedo, normal, depth and coverage of the primary hit,
  * summed over THE VERY SAMPLES that made the pixel's colour (their camera rays are made inside the kernel from the
- * pixel's RNG stream, so no caller could ask rtmi_intersect for them).  Added without a version change: a caller detects
- * it by the symbol rtmi_render_features.
+ * pixel's RNG stream; a caller who wants more of those rays than these four buffers renders the frame by the three-call
+ * loop of "camera rays" above instead, whose rtmi_camera_rays hands out each sample's rays for rtmi_intersect or
+ * rtmi_occluded before rtmi_trace follows them).  Added without a version change: a caller detects it by the symbol
+ * rtmi_render_features.
  *
  * rtmi_render_features is rtmi_render_budget in every respect stated above -- which samples are rendered and the order
  * of the additions; what padding and budget-0 items leave alone (everything, the feature buffers included); the cap

@@ -1348,6 +1348,62 @@ int rtmi_resolve_variance(const rtmi_frame *f, const float *d_sum, const float *
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ camera rays
+// u, v, w finite and orthonormal, in binary64: | |x|^2 - 1 | <= 1e-3 each, |dot| <= 1e-3 pairwise.  A camera installed by
+// rtmi_camera_raw (or rtmi_camera_set with no frame) carries none.
+static bool camera_frame_orthonormal(const V3 &u, const V3 &v, const V3 &w) {
+  const double a[3][3] = {{u.x, u.y, u.z}, {v.x, v.y, v.z}, {w.x, w.y, w.z}};
+  for (int i = 0; i < 3; i++)
+    for (int j = i; j < 3; j++) {
+      const double dot = a[i][0] * a[j][0] + a[i][1] * a[j][1] + a[i][2] * a[j][2];
+      if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;  // (a NaN or an infinity fails)
+    }
+  return true;
+}
+
+int rtmi_camera_rays(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_projection *proj, const uint32_t *d_budget,
+                     uint32_t sample, void *d_states, float *d_origins, float *d_dirs, void *stream) {
+  static_assert(sizeof(rtmi_projection) == 16, "rtmi_projection is 16 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  FrameDev d;
+  int rc = budget_frame(f, d_states && d_origins && d_dirs, "null state, origin or direction array", &d);
+  if (rc) return rc;
+  int kind = RTMI_PROJ_CAMERA;
+  float fov = 0.f;
+  if (proj) {
+    if (proj->size != (int32_t)sizeof(rtmi_projection) || proj->reserved != 0)
+      return fail(RTMI_ERR_INVALID, "rtmi_projection.size does not match this library, or reserved is not 0");
+    if (proj->kind < RTMI_PROJ_CAMERA || proj->kind > RTMI_PROJ_FISHEYE)
+      return fail(RTMI_ERR_INVALID, "rtmi_projection.kind is not one of RTMI_PROJ_*");
+    kind = proj->kind, fov = proj->fov;
+    // (2 pi as the binary32 nearest to it, which lies above: the fov a caller writes as (float)(2 * M_PI) is accepted)
+    if (kind == RTMI_PROJ_FISHEYE && !(std::isfinite(fov) && fov > 0.f && fov <= 6.283185307179586f))
+      return fail(RTMI_ERR_INVALID, "rtmi_projection.fov of a fisheye must be finite, above 0 and at most 2 pi");
+  }
+  const Scene *s = S(sp);
+  if (kind != RTMI_PROJ_CAMERA && !(s->has_camera && camera_frame_orthonormal(s->cam.u, s->cam.v, s->cam_w)))
+    return fail(RTMI_ERR_INVALID, "this projection needs a camera whose u, v, w are finite and orthonormal "
+                                  "(rtmi_camera_raw installs none)");
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if ((rc = scene_device(s, nullptr))) return rc;
+  // the camera is the scene's host record now, by value: a later rtmi_camera_update does not reach this launch
+  const float w[3] = {s->cam_w.x, s->cam_w.y, s->cam_w.z};
+  HIP_TRY(launch_camera_rays(d, s->dev.cam, w, kind, fov, d_budget, sample, reinterpret_cast<uint32_t *>(d_states), d_origins,
+                             d_dirs, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_sample_add(const rtmi_frame *f, const uint32_t *d_budget, uint32_t sample, const float *d_radiance,
+                    const uint32_t *d_trace_counts, float *d_sum, float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts,
+                    void *stream) {
+  FrameDev d;
+  const int rc = budget_frame(f, d_radiance && d_sum && d_samples, "null radiance, sum or sample-count array", &d);
+  if (rc) return rc;
+  HIP_TRY(launch_sample_add(d, d_budget, sample, d_radiance, d_trace_counts, d_sum, d_sq, d_samples, d_ray_counts,
+                            (hipStream_t)stream));
+  return RTMI_OK;
+}
+
 // ------------------------------------------------------------------ denoise
 static bool denoise_extent(int height, int width) {
   return height >= 1 && height <= RTMI_MAX_EXTENT && width >= 1 && width <= RTMI_MAX_EXTENT;

@@ -233,6 +233,15 @@ struct AccumulateCall {
 };
 size_t history_bytes(int height, int width);
 hipError_t launch_accumulate(const AccumulateCall &c, hipStream_t stream);
+// The render's primary rays of one sample (rtmi_camera_rays; camera_body.h): kind = RTMI_PROJ_*, w = the camera frame's
+// third axis, d_budget nullable.  Inactive items get six +0.0f and keep their state.
+hipError_t launch_camera_rays(const FrameDev &fr, const CameraDev &cam, const float w[3], int kind, float fov,
+                              const uint32_t *d_budget, uint32_t sample, uint32_t *d_states, float *d_origins,
+                              float *d_dirs, hipStream_t stream);
+// One traced sample folded into the budget buffers (rtmi_sample_add): d_budget, d_trace_counts, d_sq, d_ray_counts nullable.
+hipError_t launch_sample_add(const FrameDev &fr, const uint32_t *d_budget, uint32_t sample, const float *d_radiance,
+                             const uint32_t *d_trace_counts, float *d_sum, float *d_sq, uint32_t *d_samples,
+                             uint32_t *d_ray_counts, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

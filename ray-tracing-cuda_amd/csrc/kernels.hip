@@ -1152,5 +1152,6 @@ hipError_t launch_resolve_variance(const FrameDev &fr, const float *d_sum, const
 
 #include "denoise_body.h"
 #include "accumulate_body.h"
+#include "camera_body.h"
 
 }  // namespace rtmi

@@ -92,6 +92,22 @@ def feature_bufs(albedo=None, normal=None, depth=None, coverage=None):
     return Features(C.sizeof(Features), 0, ptr(albedo), ptr(normal), ptr(depth), ptr(coverage))
 
 
+class Projection(C.Structure):
+    """rtmi_projection of include/rtmi.h (how rtmi_camera_rays turns a pixel's jitter into a ray)."""
+    _fields_ = [("size", C.c_int32), ("kind", C.c_int32), ("fov", C.c_float), ("reserved", C.c_int32)]
+
+
+PROJECTIONS = {"camera": 0, "orthographic": 1, "equirect": 2, "fisheye": 3}  # RTMI_PROJ_*
+
+
+def projection(kind="camera", fov=0.0):
+    """An rtmi_projection: ``kind`` "camera" (the scene's own, the render's), "orthographic", "equirect" or "fisheye";
+    ``fov``: a fisheye's full angle of the image circle in radians, in (0, 2 pi]."""
+    if kind not in PROJECTIONS:
+        raise RtmiError("projection kind must be one of %s" % ", ".join(sorted(PROJECTIONS)))
+    return Projection(C.sizeof(Projection), PROJECTIONS[kind], float(fov), 0)
+
+
 class DenoiseOpts(C.Structure):
     """rtmi_denoise_opts of include/rtmi.h."""
     _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
@@ -214,6 +230,10 @@ SYMBOLS = [
     ("rtmi_history_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("rtmi_accumulate", C.c_int, [C.c_int, C.c_int, C.POINTER(AccumulateOpts), C.c_void_p, C.POINTER(DenoiseGuides), _fp,
                                   C.c_void_p, _fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_camera_rays", C.c_int, [C.c_void_p, _frp, C.POINTER(Projection), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    ("rtmi_sample_add", C.c_int, [_frp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -951,6 +971,102 @@ class Renderer:
             self.budget_abandoned += self.d_work[0]  # (stream-ordered: the next call resets d_work)
         return self
 
+    # -------------------------------------------------------------- camera rays
+    def _budget_arg(self, budget):
+        if budget is not None and not _is_buffer(budget, (self.items,), self.device, self.torch.int32):
+            raise RtmiError("budget must be a contiguous CUDA int32 tensor of shape (items,) on the renderer's device")
+        return C.c_void_p(budget.data_ptr()) if budget is not None else None
+
+    def camera_rays(self, sample, budget=None, projection=None, out=None):
+        """The primary rays of sample index ``sample`` of every pixel of this shard (rtmi_camera_rays), enqueued on torch's
+        current stream: what the render makes from ``states`` for each pixel's next sample, the states advanced in place
+        by the jitter and lens draws.  ``budget``: None (every pixel has the frame's spp) or a contiguous (items,) int32
+        CUDA tensor; an item with no sample ``sample`` left, and padding, gets a zero ray and keeps its state.
+        ``projection``: an ``rtmi.projection(...)`` (None: the scene's camera).  ``out``: an optional pair of (items, 3)
+        float32 CUDA tensors to write into.  Returns (origins, directions), tile-major; the directions are normalised once
+        (``SceneBuilder.trace`` and ``intersect`` normalise once more, as Ray's constructor does)."""
+        torch = self.torch
+        if projection is not None and not isinstance(projection, Projection):
+            raise RtmiError("projection must be an rtmi.projection(...)")
+        d_budget = self._budget_arg(budget)
+        shape = (self.items, 3)
+        if out is None:
+            out = (None, None)
+        elif not (isinstance(out, (tuple, list)) and len(out) == 2):
+            raise RtmiError("out must be a pair of (items, 3) float32 CUDA tensors: (origins, directions)")
+        origins = _out_buffer(out[0], "float32 tensor of shape (items, 3)", shape, self.device, torch.float32)
+        dirs = _out_buffer(out[1], "float32 tensor of shape (items, 3)", shape, self.device, torch.float32)
+        with torch.cuda.device(self.device):
+            _check(self.L.rtmi_camera_rays(self.scene.h, C.byref(self.frame), C.byref(projection) if projection is not None else None,
+                                           d_budget, int(sample), C.c_void_p(self.states.data_ptr()),
+                                           C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()), self._stream()),
+                   "rtmi_camera_rays")
+        return origins, dirs
+
+    def sample_add(self, sample, radiance, trace_counts=None, budget=None):
+        """Fold the traced sample ``sample`` into ``sum``, ``sq``, ``samples`` and -- with ``trace_counts`` --
+        ``budget_rays`` (rtmi_sample_add; the buffers of ``render_budget``, zeroed on first use), on torch's current stream.
+        ``radiance``: (items, 3) float32, ``trace_counts``: (items,) int32 or None, as ``SceneBuilder.trace`` returns them;
+        ``budget`` as for ``camera_rays``: only the items active in this sample are touched."""
+        torch = self.torch
+        if not _is_buffer(radiance, (self.items, 3), self.device, torch.float32):
+            raise RtmiError("radiance must be a contiguous CUDA float32 tensor of shape (items, 3) on the renderer's device")
+        if trace_counts is not None and not _is_buffer(trace_counts, (self.items,), self.device, torch.int32):
+            raise RtmiError("trace_counts must be a contiguous CUDA int32 tensor of shape (items,) on the renderer's device")
+        d_budget = self._budget_arg(budget)
+        self._budget_buffers()
+        with torch.cuda.device(self.device):
+            _check(self.L.rtmi_sample_add(C.byref(self.frame), d_budget, int(sample), C.c_void_p(radiance.data_ptr()),
+                                          C.c_void_p(trace_counts.data_ptr()) if trace_counts is not None else None,
+                                          C.c_void_p(self.sum.data_ptr()), C.c_void_p(self.sq.data_ptr()),
+                                          C.c_void_p(self.samples.data_ptr()),
+                                          C.c_void_p(self.budget_rays.data_ptr()) if trace_counts is not None else None,
+                                          self._stream()), "rtmi_sample_add")
+        return self
+
+    def render_rays(self, budget=None, projection=None, count_rays=True, each=None):
+        """``render_budget(budget)`` as the composed loop -- for every sample index: ``camera_rays``, ``SceneBuilder.trace``,
+        ``sample_add`` -- on torch's current stream, bit for bit the same sums, moments, counts and states with the scene's
+        camera.  ``budget``: None for the frame's spp everywhere; the largest active budget is read back once (a
+        synchronisation).  ``projection``: an ``rtmi.projection(...)``.  ``each(sample, origins, directions)``: called
+        between the generation of a sample's rays and their tracing -- the place to run ``intersect`` or ``occluded`` on
+        the very rays of the frame (or to change them in place).  Adds each trace's closest-hit queries to ``rays_total``
+        and its abandoned mesh searches to ``budget_abandoned`` (``check()`` raises on them).  The frame must have been
+        made with ``post=False``."""
+        torch = self.torch
+        if self.frame.post_process:
+            raise RtmiError("render_rays needs a frame made with post=False: per-pixel sample counts have no uniform division (resolve)")
+        self._budget_arg(budget)
+        self._budget_buffers()
+        if getattr(self, "rays_total", None) is None:
+            self.rays_total = torch.zeros((), dtype=torch.int64, device=self.device)
+        spp = int(self.frame.spp)
+        n_samples = spp
+        if budget is not None:  # (the budget words are uint32: a negative int32 is a large one)
+            n_samples = min(spp, int((budget.to(torch.int64) & 0xffffffff).max().item())) if self.items else 0
+        with torch.cuda.device(self.device):
+            origins = torch.empty((self.items, 3), dtype=torch.float32, device=self.device)
+            dirs = torch.empty((self.items, 3), dtype=torch.float32, device=self.device)
+            radiance = torch.empty((self.items, 3), dtype=torch.float32, device=self.device)
+            counts = torch.empty((self.items,), dtype=torch.int32, device=self.device) if count_rays else None
+            work = torch.zeros((TRACE_WORK_WORDS,), dtype=torch.int64, device=self.device)  # one d_work, reused in stream order
+            stream = self._stream()
+            for sample in range(n_samples):
+                self.camera_rays(sample, budget, projection, out=(origins, dirs))
+                if each is not None:
+                    each(sample, origins, dirs)
+                _check(self.L.rtmi_trace(self.scene.h, self.items, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
+                                         int(self.frame.max_depth), C.c_void_p(self.states.data_ptr()),
+                                         C.c_void_p(radiance.data_ptr()), C.c_void_p(counts.data_ptr()) if count_rays else None,
+                                         C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
+                self.budget_abandoned += work[0]  # (stream-ordered: the next trace resets d_work)
+                self.rays_total += work[1]
+                self.sample_add(sample, radiance, counts, budget)
+            n = int(self.budget_abandoned.item())  # (waits for the loop, as Trace.check does)
+        if n:
+            raise RtmiError("rtmi_trace abandoned %d mesh search(es): the sums are incomplete" % n)
+        return self
+
     def resolve_features(self):
         """``ResolvedFeatures`` (albedo, normal, depth, alpha) of the feature sums so far, tile-major
         (rtmi_resolve_features; the rule is in include/rtmi.h): 0 where a pixel has no samples and for padding."""
@@ -1031,14 +1147,16 @@ class Renderer:
         return img
 
     def new_frame(self):
-        """Start the next frame of a sequence: zero ``sum``, ``sq``, ``samples``, ``budget_rays``, ``budget_abandoned`` and the
-        four feature sums on torch's current stream.  The RNG states go on, so every frame draws new samples."""
+        """Start the next frame of a sequence: zero ``sum``, ``sq``, ``samples``, ``budget_rays``, ``budget_abandoned``, the
+        four feature sums and ``render_rays``' ``rays_total`` on torch's current stream.  The RNG states go on, so every frame draws new samples."""
         self._budget_buffers()
         self._feature_buffers()
         with self.torch.cuda.device(self.device):
             for t in (self.sum, self.sq, self.samples, self.budget_rays, self.budget_abandoned, self.albedo, self.normal,
                       self.depth, self.coverage):
                 t.zero_()
+            if getattr(self, "rays_total", None) is not None:
+                self.rays_total.zero_()
         return self
 
     def accumulate(self, acc):
