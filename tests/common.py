@@ -1,4 +1,6 @@
-"""Shared helpers: build one named scene on either implementation and render it; read a built library's kernel metadata."""
+"""Shared helpers: build one named scene on either implementation and render it (through tests/parity.py); the oracle's
+golden files; read a built library's kernel metadata."""
+import glob
 import os
 import re
 import subprocess
@@ -44,32 +46,22 @@ def scene_seed(name):
 
 def oracle_render(name, h, w, spp, depth, post=True, seed=None, threads=None, **kw):
     import oraclelib
+    import parity
     seed = scene_seed(name) if seed is None else seed
     b = build_scene(oraclelib.OracleBuilder(seed), name, w / h, **kw)
-    rgb, rays, states, total = b.render(h, w, spp, depth, post=post, threads=threads)
-    return rgb, rays, states, total, b
+    f = parity.oracle_frame(b, h, w, spp, depth, post, threads)
+    return f.image, f.counts, f.states, f.total, b
 
 
 def gpu_render(name, h, w, spp, depth, post=True, seed=None, world_size=1, **kw):
     """Render through librtmi (C ABI) on cuda:0; world_size > 1 renders every shard on the
-    one GPU and assembles them as an RCCL gather would."""
-    import torch
+    one GPU and assembles them as an RCCL gather would.  The states are the ranks' tile-major planes."""
+    import parity
     import rtmi
     seed = scene_seed(name) if seed is None else seed
     b = build_scene(rtmi.SceneBuilder(seed), name, w / h, **kw).commit()
-    tiles, counts, states = [], [], []
-    total = 0
-    for r in range(world_size):
-        R = rtmi.Renderer(b, h, w, spp, depth, post, rank=r, world_size=world_size)
-        R.init_rng()
-        R.render()
-        total += R.total_rays()
-        tiles.append(R.tiles)
-        counts.append(R.ray_counts)
-        states.append(R.states)
-    img, cnt = R.untile(torch.cat(tiles, 0).contiguous(), torch.cat(counts, 0).contiguous())
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), states, total, b
+    img, cnt, states, total, _ = parity.render_shards(b, h, w, spp, depth, post, world=world_size)
+    return img, cnt, states, total, b
 
 
 def rel_l2(a, b):
@@ -91,3 +83,16 @@ def kernel_notes(lib):
                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
         notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
     return {re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]}
+
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+# the oracle's own goldens; ref_*.npz, the reference renderer's records, are read by test_ref_golden.py
+FILES = sorted(f for f in glob.glob(os.path.join(HERE, "golden", "*.npz")) if not os.path.basename(f).startswith("ref_"))
+PAT = re.compile(r"(?P<name>[a-z_]+)_(?P<h>\d+)x(?P<w>\d+)_s(?P<spp>\d+)_d(?P<depth>\d+)_(?P<mode>post|raw)\.npz$")
+
+
+def parse_case(path):
+    m = PAT.search(os.path.basename(path))
+    assert m, path
+    kw = {"k_min": 64} if m["name"] == "bunny" else {}
+    return m["name"], int(m["h"]), int(m["w"]), int(m["spp"]), int(m["depth"]), m["mode"] == "post", kw

@@ -1,6 +1,6 @@
 """What rtmi_denoise and rtmi_accumulate are held to beyond their own restatements: binary64 truth.
 
-tests/test_denoise_host.py and tests/test_accumulate_host.py restate the two rules in binary32 (``denoise_rule``,
+tests/filter_rules.py restates the two rules in binary32 (``denoise_rule``,
 ``accumulate_rule``) and the GPU tests hold the device to them bit for bit; that proves "kernel == rule" and says nothing
 about whether the rule computes what include/rtmi.h claims.  The checks here ask that, of anything that filters or
 accumulates -- a callable.  tests/test_filters_truth_host.py passes the numpy rules, tests/test_gpu_filters_truth.py the
@@ -16,8 +16,7 @@ functions on exactly these inputs (``measure()``; DESIGN.md 2.8 and 2.9 record t
 import numpy as np
 
 import rtmi
-from test_accumulate_host import accumulate_rule, camera_of, room
-from test_denoise_host import MIN_WEIGHT_SUM, denoise_rule
+from filter_rules import MIN_WEIGHT_SUM, accumulate_rule, camera_of, denoise_rule, room
 
 F32 = np.float32
 F64 = np.float64

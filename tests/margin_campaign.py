@@ -28,7 +28,7 @@ import rtmi
 from rtmi import scenes
 from rtmi.scenes import v3, PI_D
 import bench
-import test_gpu_round3 as t3
+import worlds as t3
 
 assert "check" in os.path.basename(rtmi.LIB_PATH), "run with RTMI_LIB_PATH=.../librtmi_check.so"
 L = rtmi.lib()

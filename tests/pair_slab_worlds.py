@@ -21,6 +21,15 @@ PLANNED = dict(lane_stride=1, schedule=2, plan=2, probe_spp=32)  # 32 samples fr
 LAUNCHES = {"queue": (40, QUEUE), "planned": (64, PLANNED)}
 
 
+def assert_launch(mode, launch, fast=1):
+    assert mode["fast_path"] == fast and mode["lane_stride"] == 1 and mode["wave_priority_every"] > 0, mode
+    if launch == "queue":
+        assert mode["scheduled"] == 0 and mode["planned_chains"] == 0, mode
+    else:
+        assert mode["scheduled"] == 1 and mode["first_pass_resumed"] == 1 and mode["planned_chains"] == 1, mode
+        assert mode["first_pass_samples"] == 32, mode
+
+
 def widening(list_mag):
     """delta_c + r_c: what a slab's half extent carries beyond the pair's padded bounds (binary64)."""
     return (DIST_SLACK + SLAB_ROUND_EPS * EPS32) * (ORIGIN_REACH + 1.0) * float(list_mag)

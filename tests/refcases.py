@@ -358,3 +358,8 @@ def run_camera(b, xy, states):
     after = states.copy()
     rays = np.stack([b.probe_camera_ray(xy[i, 0], xy[i, 1], after[i]) for i in range(xy.shape[0])])
     return b.camera_get()[:4].copy(), rays, after
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a

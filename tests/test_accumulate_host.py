@@ -1,5 +1,5 @@
-"""rtmi_accumulate / rtmi_camera_update on the host side: the accumulation rule restated in numpy (``accumulate_rule``,
-which tests/test_gpu_accumulate.py holds the device against bit for bit), a synthetic room seen from two cameras
+"""rtmi_accumulate / rtmi_camera_update on the host side: the accumulation rule restated in numpy
+(tests/filter_rules.py: ``accumulate_rule``, which tests/test_gpu_accumulate.py holds the device against bit for bit), a synthetic room seen from two cameras
 (``room``, ``MOVES``) whose frames reach every branch of the rule, hand-worked cases, the exported symbols, the struct
 against the C compiler, the argument checks that come before any HIP call, and the code-object facts of the new kernel in
 both builds of the library.  No GPU involved."""
@@ -15,180 +15,12 @@ import pytest
 import common
 import rtmi
 from rtmi import AccumulateOpts, DenoiseGuides
-from test_budget_host import DUMMY, ERR_INVALID, LIBS
+from abi_host import DUMMY, LIBS, ROOT, _refused
+from filter_rules import BRANCHES, FOV, MOVES, SHAPES, accumulate_rule, camera_of, camera_terms, room
+from parity import same
 
 ENTRIES = ("rtmi_camera_update", "rtmi_history_bytes", "rtmi_accumulate")
 F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BRANCHES = ("background", "behind", "off_screen", "refused", "snapped", "taps_1_3", "taps_4")
-SHAPES = [(1, 1), (3, 70), (70, 3), (16, 16), (33, 70)]
-
-
-# ------------------------------------------------------------------ the rule, restated
-def camera_terms(cur, prev):
-    """The host part of the rule in Python floats (binary64) from the cameras' binary32 values: (e, R, singular)."""
-    cur = np.asarray(cur, dtype=F32).reshape(-1)
-    e = np.array([float(cur[3 + k]) - float(cur[k]) for k in range(3)]).astype(F32)
-    if prev is None:
-        return e, None, False
-    prev = np.asarray(prev, dtype=F32).reshape(-1)
-    a = [float(prev[6 + k]) for k in range(3)]
-    b = [float(prev[9 + k]) for k in range(3)]
-    c = [float(prev[3 + k]) - float(prev[k]) for k in range(3)]
-    cross = lambda x, y: [x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]]
-    rows = [cross(b, c), cross(c, a), cross(a, b)]
-    det = (a[0] * rows[0][0] + a[1] * rows[0][1]) + a[2] * rows[0][2]
-    if det == 0.0 or not np.isfinite(det):
-        return e, None, True
-    return e, np.array([[x / det for x in row] for row in rows]).astype(F32), False
-
-
-def accumulate_rule(color, variance, normal, depth, alpha, camera, history=None, prev_camera=None,
-                    normal_min=rtmi.ACCUMULATE_DEFAULTS["normal_min"], depth_tolerance=rtmi.ACCUMULATE_DEFAULTS["depth_tolerance"],
-                    min_blend=rtmi.ACCUMULATE_DEFAULTS["min_blend"]):
-    """rtmi_accumulate in numpy, operation by operation as include/rtmi.h states it: float32 throughout on the device side,
-    vectorised over the image, the four taps in the stated order.  color, variance, normal (H, W, 3), depth, alpha (H, W);
-    history (3, H, W, 4) float32 -- the planes G, C, V of the device's history, byte for byte -- or None.  Returns (out,
-    out_variance, out_length, history_out, shares): shares maps each name of BRANCHES to the share of pixels that took
-    it (all 0 but background without a history)."""
-    Cp, Vp, N, Z, A = (np.asarray(x, dtype=F32) for x in (color, variance, normal, depth, alpha))
-    H, W = Z.shape
-    assert (history is None) == (prev_camera is None)
-    surf = A > 0
-    I, J = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    out, var, length = Cp.copy(), Vp.copy(), np.ones((H, W), F32)
-    which = np.where(surf, "none", "background")
-    if history is not None:
-        hist = np.asarray(history, dtype=F32).reshape(3, H, W, 4)
-        cur = np.asarray(camera, dtype=F32).reshape(-1)
-        e, R, singular = camera_terms(camera, prev_camera)
-        assert not singular
-        p, h, v, pp = cur[0:3], cur[6:9], cur[9:12], np.asarray(prev_camera, dtype=F32).reshape(-1)[0:3]
-        nm, dt, mb = F32(normal_min), F32(depth_tolerance), F32(min_blend)
-        Wf, Hf = F32(W), F32(H)
-        with np.errstate(all="ignore"):
-            xf = (J.astype(F32) + F32(0.5)) / Wf
-            yf = ((H - I).astype(F32) + F32(0.5)) / Hf
-            D = [(e[k] + xf * h[k]) + yf * v[k] for k in range(3)]
-            l = np.sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2])
-            d = [(p[k] + (D[k] / l) * Z) - pp[k] for k in range(3)]
-            al, be, ga = ((R[r][0] * d[0] + R[r][1] * d[1]) + R[r][2] * d[2] for r in range(3))
-            ze = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
-            fx = (al / ga) * Wf - F32(0.5)
-            fy = (Hf + F32(0.5)) - (be / ga) * Hf
-            for x in D + d + [xf, yf, l, al, be, ga, ze, fx, fy]:
-                assert x.dtype == F32
-            front = ga > 0
-            inside = (fx > -1) & (fx < Wf) & (fy > -1) & (fy < Hf)
-            seen = surf & front & inside
-            fx, fy = np.where(seen, fx, F32(0)), np.where(seen, fy, F32(0))
-            rx, ry = np.rint(fx), np.rint(fy)
-            snap = (np.abs(fx - rx) <= F32(1 / 64)) & (np.abs(fy - ry) <= F32(1 / 64))
-            fx, fy = np.where(snap, rx, fx), np.where(snap, ry, fy)
-            flx, fly = np.floor(fx), np.floor(fy)
-            j0, i0 = flx.astype(np.int64), fly.astype(np.int64)
-            tx, ty = fx - flx, fy - fly
-            zlim = dt * ze
-            sw, sl = np.zeros((H, W), F32), np.zeros((H, W), F32)
-            sc, sv = np.zeros((H, W, 3), F32), np.zeros((H, W, 3), F32)
-            positive = np.zeros((H, W), np.int64)
-            for di in (0, 1):
-                for dj in (0, 1):
-                    qi, qj = i0 + di, j0 + dj
-                    ok = (qi >= 0) & (qi < H) & (qj >= 0) & (qj < W)
-                    ci, cj = np.clip(qi, 0, H - 1), np.clip(qj, 0, W - 1)  # (gathered, then not taken)
-                    G, Cq, Vq = hist[0][ci, cj], hist[1][ci, cj], hist[2][ci, cj]
-                    b = (ty if di else F32(1) - ty) * (tx if dj else F32(1) - tx)
-                    dot = (N[..., 0] * G[..., 0] + N[..., 1] * G[..., 1]) + N[..., 2] * G[..., 2]
-                    take = ok & (Vq[..., 3] > 0) & (dot >= nm) & (np.abs(G[..., 3] - ze) <= zlim)
-                    for x in (b, dot, zlim):
-                        assert x.dtype == F32
-                    sw = np.where(take, sw + b, sw)
-                    sl = np.where(take, sl + b * Cq[..., 3], sl)
-                    sc = np.where(take[..., None], sc + b[..., None] * Cq[..., :3], sc)
-                    sv = np.where(take[..., None], sv + b[..., None] * Vq[..., :3], sv)
-                    positive += take & (b > 0)
-            taken = seen & (sw > 0)
-            Lp = sl / sw + F32(1)
-            a = np.fmax(F32(1) / Lp, mb)
-            o = F32(1) - a
-            Cn = o[..., None] * (sc / sw[..., None]) + a[..., None] * Cp
-            Vn = (o * o)[..., None] * (sv / sw[..., None]) + (a * a)[..., None] * Vp
-            for x in (sw, sl, sc, sv, Lp, a, o, Cn, Vn):
-                assert x.dtype == F32
-        out = np.where(taken[..., None], Cn, Cp)
-        var = np.where(taken[..., None], Vn, Vp)
-        length = np.where(taken, Lp, F32(1))
-        which = np.where(~surf, "background", np.where(~front, "behind", np.where(~inside, "off_screen", np.where(
-            ~taken, "refused", np.where(snap, "snapped", np.where(positive == 4, "taps_4", "taps_1_3"))))))
-    hist_out = np.empty((3, H, W, 4), F32)
-    hist_out[0, ..., :3], hist_out[0, ..., 3] = N, Z
-    hist_out[1, ..., :3], hist_out[1, ..., 3] = out, length
-    hist_out[2, ..., :3], hist_out[2, ..., 3] = var, surf.astype(F32)
-    for x in (out, var, length):
-        assert x.dtype == F32
-    shares = {k: float((which == k).mean()) for k in BRANCHES}
-    return out, var, length, hist_out, shares
-
-
-# ------------------------------------------------------------------ a synthetic room seen from two cameras
-FOV = 40.0 * np.pi / 180.0
-HOME = ((278, 273, -800), (278, 273, 0))
-MOVES = {"static": HOME, "slide": ((318, 283, -780), (278, 273, 0)), "pan": ((278, 273, -800), (600, 273, 0)),
-         "about": ((278, 273, 200), (278, 273, -800))}
-
-
-def look_at(pos, target, aspect, fov=FOV):
-    """The 21 floats of the library's own pinhole camera: rtmi_camera_pinhole + rtmi_camera_get on a throw-away scene
-    (neither touches the device)."""
-    L = rtmi.lib()
-    s = C.c_void_p(L.rtmi_scene_create())
-    try:
-        v = lambda x: np.asarray(x, dtype=F32).ctypes.data_as(C.POINTER(C.c_float))
-        assert L.rtmi_camera_pinhole(s, v(pos), v(target), v((0, 1, 0)), fov, float(aspect)) == 0
-        out = np.zeros(21, F32)
-        assert L.rtmi_camera_get(s, out.ctypes.data_as(C.POINTER(C.c_float))) == 0
-    finally:
-        L.rtmi_scene_destroy(s)
-    return out
-
-
-def camera_of(move, h, w):
-    return look_at(*MOVES[move], aspect=w / h)
-
-
-def room(h, w, camera, seed=0):
-    """A frame of a room seen from `camera`, analytic in binary64 and rounded to binary32: the planes z = 559, y = 0,
-    x = 555 and y = 555, the plane x = 0 turned into background (alpha 0, depth 0, normal 0, like whatever a ray misses),
-    and a box face at z = 300 for 100 < x < 300, y < 330.  Depth is t along the unit centre ray, the normals are axis unit
-    vectors, colour and variance are random in [0, 1).  Returns a dict of accumulate_rule's first five arguments."""
-    cam = np.asarray(camera, dtype=np.float64).reshape(-1)
-    p, llc, hh, vv = cam[0:3], cam[3:6], cam[6:9], cam[9:12]
-    I, J = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    xf, yf = (J + 0.5) / w, ((h - I) + 0.5) / h
-    D = (llc - p)[None, None] + xf[..., None] * hh + yf[..., None] * vv
-    D = D / np.sqrt((D * D).sum(-1, keepdims=True))
-    best = np.full((h, w), np.inf)
-    normal = np.zeros((h, w, 3))
-    surface = np.zeros((h, w), bool)
-    planes = ((2, 559.0, (0, 0, -1), True), (1, 0.0, (0, 1, 0), True), (0, 555.0, (-1, 0, 0), True), (1, 555.0, (0, -1, 0), True),
-              (0, 0.0, (0, 0, 0), False), (2, 300.0, (0, 0, -1), "box"))
-    with np.errstate(all="ignore"):
-        for axis, at, nrm, kind in planes:
-            t = (at - p[axis]) / D[..., axis]
-            hit = np.isfinite(t) & (t > 1e-9) & (t < best)
-            if kind == "box":
-                P = p + D * t[..., None]
-                hit &= (P[..., 0] > 100) & (P[..., 0] < 300) & (P[..., 1] < 330)
-            best = np.where(hit, t, best)
-            normal[hit] = nrm
-            surface = np.where(hit, bool(kind), surface)
-    rng = np.random.default_rng([seed, h, w])
-    d = dict(color=rng.random((h, w, 3)).astype(F32), variance=rng.random((h, w, 3)).astype(F32),
-             normal=np.where(surface[..., None], normal, 0).astype(F32), depth=np.where(surface, best, 0).astype(F32),
-             alpha=surface.astype(F32))
-    assert all(x.dtype == F32 for x in d.values())
-    return d
 
 
 def first_frame(h, w, seed=0):
@@ -202,14 +34,6 @@ def moved(move, h, w, **opts):
     cam0, _, hist = first_frame(h, w)
     cam1 = camera_of(move, h, w)
     return accumulate_rule(**room(h, w, cam1, seed=1), camera=cam1, history=hist, prev_camera=cam0, **opts)
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=F32).view(np.uint32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------ every branch is reached
@@ -373,14 +197,6 @@ def test_sizeof_accumulate_opts_agrees_with_the_header():
     assert got == [C.sizeof(AccumulateOpts)] + [getattr(AccumulateOpts, f[0]).offset for f in AccumulateOpts._fields_]
     assert C.sizeof(AccumulateOpts) == 20
     assert rtmi.ACCUMULATE_DEFAULTS == dict(normal_min=0.8, depth_tolerance=0.05, min_blend=0.1)
-
-
-# ------------------------------------------------------------------ refusals before any HIP call
-def _refused(rc, word):
-    assert rc == ERR_INVALID, rc
-    msg = rtmi.lib().rtmi_last_error()
-    assert msg and word in msg, msg
-    return True
 
 
 def _opts(**kw):

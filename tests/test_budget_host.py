@@ -1,6 +1,6 @@
 """rtmi_render_budget / rtmi_budget_plan / rtmi_resolve on the host side: the exported symbols, the argument checks that
 come before any HIP call, the budget kernels in both builds of the library, and the stopping rule restated in numpy
-(``plan_rule``, which tests/test_gpu_budget.py holds the device against).  No GPU involved.
+(tests/budgetlib.py: ``plan_rule``, which tests/test_gpu_budget.py holds the device against).  No GPU involved.
 
 The refusals that need a COMMITTED scene (max_depth, post_process, spp x depth) cannot be reached without a device,
 because committing a scene uploads it: tests/test_gpu_budget.py::test_budget_argument_checks_on_a_committed_scene."""
@@ -13,53 +13,11 @@ import pytest
 
 import common
 import rtmi
+from abi_host import DUMMY, F_DEFOCUS, LIBS, QUERY_VARIANTS, _frame, _refused
+from budgetlib import moments, plan_rule
 
-QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
-F_DEFOCUS = 32      # scene_dev.h
-OK, ERR_INVALID, ERR_DEPTH = 0, -1, -5  # include/rtmi.h
-LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
 ENTRIES = ("rtmi_render_budget", "rtmi_budget_plan", "rtmi_resolve")
 F32 = np.float32
-
-
-# ------------------------------------------------------------------ the stopping rule, restated
-def plan_rule(n, S, Q, min_n, max_n, step, tolerance, floor, pixel=None):
-    """rtmi_budget_plan in numpy, operation by operation as include/rtmi.h states it.  n (N,) uint32, S, Q (N, 3)
-    float32, pixel (N,) bool (False: padding).  Returns the (N,) uint32 budgets."""
-    n = np.asarray(n, dtype=np.uint32)
-    S, Q = np.asarray(S, dtype=F32), np.asarray(Q, dtype=F32)
-    T, Fl = F32(tolerance), F32(floor)
-    with np.errstate(all="ignore"):
-        nf = n.astype(F32)[:, None]
-        a = nf * Q
-        b = S * S
-        c = a - b
-        d = nf - F32(1.0)
-        lhs = c / d
-        e = T * T
-        g = nf * nf
-        h = Fl * Fl
-        i = g * h
-        j = b + i
-        rhs = e * j
-        converged = (lhs <= rhs).all(axis=1)  # (a NaN compares false)
-    for x in (a, b, c, d, lhs, g, i, j, rhs):
-        assert x.dtype == F32
-    n64 = n.astype(np.int64)
-    more = np.minimum(step, max_n - n64)
-    out = np.where(n64 < min_n, min_n - n64, np.where(n64 >= max_n, 0, np.where(converged, 0, more)))
-    if pixel is not None:
-        out = np.where(pixel, out, 0)
-    return out.astype(np.uint32)
-
-
-def moments(samples):
-    """(n, S, Q) of one pixel whose three channels all saw `samples`, accumulated in binary32 as the kernel does."""
-    s = q = F32(0)
-    for x in samples:
-        x = F32(x)
-        s, q = F32(s + x), F32(q + F32(x * x))
-    return len(samples), [s] * 3, [q] * 3
 
 
 def test_stopping_rule_on_hand_worked_cases():
@@ -107,25 +65,6 @@ def test_budget_entries_are_exported_by_both_builds():
             assert hasattr(lib, e), (path, e)
     assert rtmi.BUDGET_WORK_WORDS >= 4
     assert C.sizeof(rtmi.AdaptiveOpts) == 24
-
-
-# ------------------------------------------------------------------ refusals before any HIP call
-DUMMY = C.c_void_p(16)  # never dereferenced: argument checks come first
-
-
-def _frame(**kw):
-    f = dict(height=20, width=28, spp=4, max_depth=8, post=False)
-    f.update(kw)
-    return rtmi.make_frame(f["height"], f["width"], f["spp"], f["max_depth"], f["post"], f.get("rank", 0), f.get("world", 1))
-
-
-def _refused(rc, word=None):
-    assert rc == ERR_INVALID, rc
-    msg = rtmi.lib().rtmi_last_error()
-    assert msg, "a refusal says why"
-    if word:
-        assert word in msg, msg
-    return True
 
 
 def test_render_budget_argument_checks_before_any_hip_call():

@@ -13,24 +13,15 @@ import numpy as np
 
 import common
 import rtmi
+from abi_host import DUMMY, LIBS, OK, _refused
 
-OK, ERR_INVALID = 0, -1  # include/rtmi.h
-LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
 ENTRIES = ("rtmi_camera_rays", "rtmi_sample_add")
-DUMMY = C.c_void_p(16)  # never dereferenced: argument checks come first
 
 
 def _frame(**kw):
     f = dict(height=20, width=28, spp=4, max_depth=8)
     f.update(kw)
     return rtmi.make_frame(f["height"], f["width"], f["spp"], f["max_depth"], False, f.get("rank", 0), f.get("world", 1))
-
-
-def _refused(rc, word):
-    assert rc == ERR_INVALID, rc
-    msg = rtmi.lib().rtmi_last_error()
-    assert msg and word in msg, msg
-    return True
 
 
 def _scene(camera="pinhole"):

@@ -11,18 +11,9 @@ with x and y, so its largest values sit in the pixel of the last column and the 
 """
 import numpy as np
 
-F32 = np.float32
-SIDE = 64
-# v.v / A^2 = x^2 + y^2 is at most 1 + (65 / 64)^2 = 2.0315 in the corner pixel and at most (63 / 64)^2 + (65 / 64)^2 =
-# 2.0004 or 1 + 1 = 2 outside it: 2^100 / A^2 = 2.004 lies between, about 0.39 of the corner pixel's area beyond it
-SLOW_A = F32(2.0 ** 50 / np.sqrt(2.004))
-SLOW_ORIGIN = np.array([278, 278, 100], dtype=F32)  # inside the Cornell box, looking along +x / +y at two of its walls
+from worlds import F32, SIDE, slow_camera
+
 DOMAIN_HI = F32(2.0 ** 100)
-
-
-def slow_camera():
-    """(position, lower-left corner, horizontal, vertical) of the raw camera."""
-    return SLOW_ORIGIN, SLOW_ORIGIN.copy(), np.array([SLOW_A, 0, 0], dtype=F32), np.array([0, SLOW_A, 0], dtype=F32)
 
 
 def dot_of_camera_ray(col, row, r1, r2, side=SIDE):

@@ -1,6 +1,6 @@
 """rtmi_denoise / rtmi_resolve_variance on the host side: the filter and the variance rule restated in numpy
-(``denoise_rule``, ``variance_rule``, which tests/test_gpu_denoise.py holds the device against bit for bit), the exported
-symbols, the two structs against the C compiler, the argument checks that come before any HIP call, and the code-object
+(tests/filter_rules.py: ``denoise_rule``, ``variance_rule``, which tests/test_gpu_denoise.py holds the device against bit
+for bit), the exported symbols, the two structs against the C compiler, the argument checks that come before any HIP call, and the code-object
 facts of the new kernels in both builds of the library.  No GPU involved."""
 import ctypes as C
 import os
@@ -13,101 +13,12 @@ import numpy as np
 import common
 import rtmi
 from rtmi import DenoiseGuides, DenoiseOpts
-from test_budget_host import DUMMY, ERR_INVALID, LIBS, _frame
+from abi_host import DUMMY, LIBS, ROOT, _frame, _refused
+from filter_rules import denoise_rule, falloff, variance_rule
 
 ENTRIES = ("rtmi_resolve_variance", "rtmi_denoise_scratch_bytes", "rtmi_denoise")
 KERNELS = {"atrous_kernel": 4, "denoise_prepare_kernel": 1, "resolve_variance_kernel": 1}  # name part -> how many
 F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H5 = [F32(1) / F32(16), F32(1) / F32(4), F32(3) / F32(8), F32(1) / F32(4), F32(1) / F32(16)]
-MIN_WEIGHT_SUM = F32(2.0 ** -32)  # a pass filters a pixel only from this sum of weights on: below it sw * sw leaves the normals
-
-
-# ------------------------------------------------------------------ the rules, restated
-def falloff(x):
-    m = np.fmax(F32(1) - F32(0.25) * x, F32(0))
-    m2 = m * m
-    return m2 * m2
-
-
-def variance_rule(n, S, Q, pixel=None):
-    """rtmi_resolve_variance in numpy, operation by operation as include/rtmi.h states it.  n (N,) uint32, S, Q (N, 3)
-    float32, pixel (N,) bool (False: padding).  Returns (N, 3) float32."""
-    n = np.asarray(n, dtype=np.uint32)
-    S, Q = np.asarray(S, dtype=F32), np.asarray(Q, dtype=F32)
-    if pixel is not None:
-        n = np.where(np.asarray(pixel, dtype=bool), n, 0).astype(np.uint32)
-    with np.errstate(all="ignore"):
-        nf = n.astype(F32)[:, None]
-        a = nf * Q
-        b = S * S
-        c = np.fmax(a - b, F32(0))
-        d = nf * nf
-        e = nf - F32(1)
-        many = c / (d * e)
-    for x in (a, b, c, d, e, many):
-        assert x.dtype == F32
-    n = n[:, None]
-    return np.where(n == 0, F32(0), np.where(n == 1, b, many)).astype(F32)
-
-
-def denoise_rule(color, variance, normal, depth, alpha, albedo=None, iterations=rtmi.DENOISE_DEFAULTS["iterations"],
-                 sigma_color=rtmi.DENOISE_DEFAULTS["sigma_color"], sigma_depth=rtmi.DENOISE_DEFAULTS["sigma_depth"],
-                 normal_squarings=rtmi.DENOISE_DEFAULTS["normal_squarings"], demodulate=None, decisions=None):
-    """rtmi_denoise in numpy, operation by operation as include/rtmi.h states it: float32 throughout, vectorised over the
-    image, the 25 taps in the stated order.  color, variance, normal, albedo (H, W, 3), depth, alpha (H, W).  Returns
-    (out, out_variance), both (H, W, 3) float32.  decisions: a list that receives, per pass, the (H, W) bool array of the
-    pixels the pass filtered (the others kept their value)."""
-    C0, V0, N, Z, A = (np.asarray(x, dtype=F32) for x in (color, variance, normal, depth, alpha))
-    demodulate = (albedo is not None) if demodulate is None else bool(demodulate)
-    H, W = Z.shape
-    sc2 = F32(sigma_color) * F32(sigma_color)
-    sz = F32(sigma_depth)
-    with np.errstate(all="ignore"):
-        if demodulate:
-            ad = np.fmax(np.asarray(albedo, dtype=F32), F32(0.01))
-            Cc, V = C0 / ad, V0 / (ad * ad)
-        else:
-            Cc, V = C0.copy(), V0.copy()
-        surf = A > 0
-        I, J = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-        zden = sz * Z + F32(1e-6)
-        for k in range(iterations):
-            s = 1 << k
-            vsum = (V[..., 0] + V[..., 1]) + V[..., 2]
-            sw = np.zeros((H, W), F32)
-            sc, sv = np.zeros((H, W, 3), F32), np.zeros((H, W, 3), F32)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    qi, qj = I + dy * s, J + dx * s
-                    inside = (qi >= 0) & (qi < H) & (qj >= 0) & (qj < W)
-                    ci, cj = np.clip(qi, 0, H - 1), np.clip(qj, 0, W - 1)  # (gathered, then not taken)
-                    Nq, Zq, Cq, Vq, surf_q = N[ci, cj], Z[ci, cj], Cc[ci, cj], V[ci, cj], surf[ci, cj]
-                    take = inside & (surf == surf_q)
-                    d = np.fmax((N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]) + N[..., 2] * Nq[..., 2], F32(0))
-                    wn = d
-                    for _ in range(normal_squarings):
-                        wn = wn * wn
-                    wz = falloff(np.abs(Z - Zq) / zden)
-                    wn, wz = np.where(surf, wn, F32(1)), np.where(surf, wz, F32(1))
-                    diff = Cc - Cq
-                    d2 = (diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]
-                    vs = vsum + vsum[ci, cj]
-                    wc = falloff(d2 / (sc2 * vs + F32(1e-10)))
-                    w = (((H5[dy + 2] * H5[dx + 2]) * wn) * wz) * wc
-                    for x in (d, wn, wz, d2, vs, wc, w):
-                        assert x.dtype == F32
-                    sw = np.where(take, sw + w, sw)
-                    sc = np.where(take[..., None], sc + w[..., None] * Cq, sc)
-                    sv = np.where(take[..., None], sv + (w * w)[..., None] * Vq, sv)
-            ok = (sw >= MIN_WEIGHT_SUM)[..., None]
-            if decisions is not None:
-                decisions.append(ok[..., 0])
-            Cc, V = np.where(ok, sc / sw[..., None], Cc), np.where(ok, sv / (sw * sw)[..., None], V)
-            assert Cc.dtype == F32 and V.dtype == F32
-        if demodulate:
-            Cc, V = Cc * ad, V * (ad * ad)
-    return Cc.astype(F32), V.astype(F32)
 
 
 def test_falloff_on_hand_worked_values():
@@ -190,14 +101,6 @@ def test_sizeof_denoise_structs_agrees_with_the_header():
         got = [int(x) for x in line.split()]
         assert got == [C.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_], cname
     assert C.sizeof(DenoiseOpts) == 24 and C.sizeof(DenoiseGuides) == 48
-
-
-# ------------------------------------------------------------------ refusals before any HIP call
-def _refused(rc, word):
-    assert rc == ERR_INVALID, rc
-    msg = rtmi.lib().rtmi_last_error()
-    assert msg and word in msg, msg
-    return True
 
 
 def _opts(**kw):

@@ -12,7 +12,7 @@ import pytest
 
 import common
 import rtmi
-from test_budget_host import LIBS
+from abi_host import LIBS
 
 GENERAL, QUEUE, CHAINS = 0, 1, 2
 NAMES = ("enabled", "variant", "n_mats", "mats_in_lds", "pairs_in_lds", "unsigned_colours", "det_safe", "width", "height",

@@ -1,6 +1,6 @@
 """rtmi_render_features / rtmi_resolve_features on the host side: the exported symbols, sizeof(rtmi_features), the argument
 checks that come before any HIP call, the feature kernels in both builds of the library, and the resolve rule restated in
-numpy (``resolve_rule``, which tests/test_gpu_features.py holds the device against).  No GPU involved."""
+numpy (tests/budgetlib.py: ``resolve_rule``, which tests/test_gpu_features.py holds the device against).  No GPU involved."""
 import ctypes as C
 import os
 import re
@@ -11,29 +11,11 @@ import numpy as np
 
 import common
 import rtmi
-from test_budget_host import DUMMY, ERR_DEPTH, ERR_INVALID, F_DEFOCUS, LIBS, QUERY_VARIANTS, _frame
+from abi_host import DUMMY, ERR_DEPTH, F_DEFOCUS, LIBS, QUERY_VARIANTS, ROOT, _frame, _refused
+from budgetlib import resolve_rule
 
 ENTRIES = ("rtmi_render_features", "rtmi_resolve_features")
 F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-# ------------------------------------------------------------------ the resolve rule, restated
-def resolve_rule(n, albedo, normal, depth, coverage, pixel=None):
-    """rtmi_resolve_features in numpy, operation by operation as include/rtmi.h states it.  n, coverage (N,) uint32,
-    albedo, normal (N, 3) float32, depth (N,) float32, pixel (N,) bool (False: padding).  Returns (albedo, normal,
-    depth, alpha), all float32: everything 0 where n == 0 and for padding."""
-    n, c = np.asarray(n, dtype=np.uint32), np.asarray(coverage, dtype=np.uint32)
-    live = n > 0 if pixel is None else (n > 0) & np.asarray(pixel, dtype=bool)
-    nf, cf = n.astype(F32), c.astype(F32)
-    with np.errstate(all="ignore"):
-        a = np.where(live[:, None], np.asarray(albedo, dtype=F32) / nf[:, None], F32(0))
-        m = np.where(live[:, None], np.asarray(normal, dtype=F32) / nf[:, None], F32(0))
-        d = np.where(live & (c > 0), np.asarray(depth, dtype=F32) / cf, F32(0))
-        alpha = np.where(live, cf / nf, F32(0))
-    for x in (a, m, d, alpha):
-        assert x.dtype == F32
-    return a, m, d, alpha
 
 
 def test_resolve_rule_on_hand_worked_cases():
@@ -86,13 +68,6 @@ def _feat(size=None, reserved=0, **bufs):
     for k in bufs:
         setattr(f, "d_" + k, DUMMY.value)
     return f
-
-
-def _refused(rc, word, code=ERR_INVALID):
-    assert rc == code, rc
-    msg = rtmi.lib().rtmi_last_error()
-    assert msg and word in msg, msg
-    return True
 
 
 def test_render_features_argument_checks_before_any_hip_call():

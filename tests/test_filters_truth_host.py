@@ -6,9 +6,9 @@ import pytest
 
 import common
 import filters_truth as T
+import filter_rules
 import oraclelib
-import test_denoise_host
-from test_accumulate_host import accumulate_rule
+from filter_rules import accumulate_rule
 
 F32 = np.float32
 ids = lambda s: "%dx%d" % s
@@ -26,7 +26,7 @@ def test_denoise_rule_against_binary64(shape, squarings, iterations, demodulate)
 def test_the_threshold_is_what_keeps_the_rule_finite(monkeypatch):
     """The same check on the rule as it was, sw > 0: with 6 squarings a pass divides by the square of a subnormal sum and
     the variance is infinite or NaN out of finite inputs.  (The smallest subnormal as the threshold is sw > 0.)"""
-    monkeypatch.setattr(test_denoise_host, "MIN_WEIGHT_SUM", np.nextafter(F32(0), F32(1)))
+    monkeypatch.setattr(filter_rules, "MIN_WEIGHT_SUM", np.nextafter(F32(0), F32(1)))
     with pytest.raises(AssertionError, match="not finite"):
         T.check_denoise_truth(T.rule_denoise, (33, 70), 6, 1, 0)
 

@@ -1,25 +1,12 @@
 """Oracle vs the committed golden vectors (tests/golden/*.npz, made by make_golden.py):
 pins the oracle's determinism across machines and compilers."""
-import glob
 import os
-import re
 
 import numpy as np
 import pytest
 
 import common
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-# the oracle's own goldens; ref_*.npz, the reference renderer's records, are read by test_ref_golden.py
-FILES = sorted(f for f in glob.glob(os.path.join(HERE, "golden", "*.npz")) if not os.path.basename(f).startswith("ref_"))
-PAT = re.compile(r"(?P<name>[a-z_]+)_(?P<h>\d+)x(?P<w>\d+)_s(?P<spp>\d+)_d(?P<depth>\d+)_(?P<mode>post|raw)\.npz$")
-
-
-def parse_case(path):
-    m = PAT.search(os.path.basename(path))
-    assert m, path
-    kw = {"k_min": 64} if m["name"] == "bunny" else {}
-    return m["name"], int(m["h"]), int(m["w"]), int(m["spp"]), int(m["depth"]), m["mode"] == "post", kw
+from common import FILES, parse_case
 
 
 def test_fixtures_exist():

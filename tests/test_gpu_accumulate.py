@@ -1,5 +1,5 @@
 """rtmi_accumulate / rtmi_camera_update / Renderer.accumulate on the GPU: bit for bit against the numpy restatement of
-tests/test_accumulate_host.py (``accumulate_rule``) on its synthetic room, over chains of three frames so that the history
+tests/filter_rules.py (``accumulate_rule``) on its synthetic room, over chains of three frames so that the history
 records are held to the rule too; a camera moved on a committed scene against a scene committed with that camera; and
 the one thing no restatement can say: that accumulating a moving sequence lowers the error of its last frame.
 
@@ -16,16 +16,16 @@ import pytest
 
 import common
 import rtmi
+from abi_host import CHECK_LIB, ROOT
+from filter_rules import FOV, MOVES, SHAPES, accumulate_rule, camera_of, look_at, room
 from filters_truth import LANDING_M, SNAP, landing_truth, same_or_nan
-from test_accumulate_host import FOV, MOVES, SHAPES, accumulate_rule, bits, camera_of, look_at, room, same
+from parity import bits, same
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK_LIB = os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")
 INPUTS = ("color", "variance", "normal", "depth", "alpha")
 OTHER = dict(normal_min=-1.0, depth_tolerance=0.01, min_blend=0.0)
 

@@ -13,7 +13,8 @@ import pytest
 import common
 import oraclelib
 import rtmi
-from test_gpu_trace import bits, glm_normalize
+from parity import bits
+from querylib import glm_normalize
 
 pytestmark = pytest.mark.gpu
 

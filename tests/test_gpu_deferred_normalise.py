@@ -20,13 +20,11 @@ import functools
 import numpy as np
 import pytest
 
-import common
-import oraclelib
-import rtmi
+from budgetlib import OracleReplay, Shards
+from pair_slab_worlds import LAUNCHES, assert_launch
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
 from rtmi import scenes
-from test_deferred_normalise_host import SIDE, slow_camera
-from test_gpu_budget import OracleReplay, Shards
-from test_gpu_fast_path import random_list
+from worlds import SIDE, random_list, slow_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -56,65 +54,32 @@ WORLDS = {"cornell_box": (cornell, scenes.SCENE_SEEDS.get("cornell_box", 1024)),
 
 
 @functools.lru_cache(maxsize=None)
-def oracle(world, spp, depth):
-    """(image, ray counts, final states (H*W, 6), ray total): computed once per frame, read by every case of it."""
+def pair(world):
     fill, seed = WORLDS[world]
-    b = oraclelib.OracleBuilder(seed)
-    fill(b, W / H)
-    rgb, rays, states, total = b.render(H, W, spp, depth, post=True)
-    for a in (rgb, rays, states):
-        a.setflags(write=False)
-    return rgb, rays, states, total
+    return build_pair(lambda b: fill(b, W / H), seed)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(world, spp, depth):
+    """Computed once per frame, read by every case of it."""
+    return oracle_frame(pair(world)[0], H, W, spp, depth)
 
 
 def gpu(world, spp, depth, **opts):
     """The same through rtmi_render_ex, and what rtmi_render_mode says of the call."""
-    fill, seed = WORLDS[world]
-    b = rtmi.SceneBuilder(seed)
-    fill(b, W / H)
-    b.commit()
-    R = rtmi.Renderer(b, H, W, spp, depth, True).init_rng()
-    ro = rtmi.render_opts(**opts) if opts else None
-    R.render(opts=ro)
-    R.check()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    pm = rtmi.pixel_map(R.frame)
-    st = np.ascontiguousarray(R.states.cpu().numpy().view(np.uint32).T)
-    states = np.zeros((H * W, 6), dtype=np.uint32)
-    states[pm[pm >= 0]] = st[pm >= 0]
-    return img.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), states, R.total_rays(), R.mode(ro)
+    return gpu_frame(pair(world)[1], H, W, spp, depth, opts=opts or None)
 
 
 def assert_is_the_oracles(got, want, what):
-    assert got[3] == want[3], "%s: ray totals %d vs %d" % (what, got[3], want[3])
-    assert got[3] > H * W, what  # the world is in view
-    assert np.array_equal(got[1], want[1]), "%s: %d pixels with other ray counts" % (what, (got[1] != want[1]).sum())
-    assert np.array_equal(got[2], want[2]), "%s: final RNG states differ" % what
-    assert got[0].shape == want[0].shape and not np.isnan(want[0]).any(), what
-    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)), \
-        "%s: %d values differ, max abs %g" % (what, (got[0] != want[0]).sum(), np.abs(got[0] - want[0]).max())
+    assert got.total > H * W, what  # the world is in view
+    assert_same_frame(got, want, what)
 
 
 # ------------------------------------------------------------------ the Cornell box, 64 x 64, depth 50
-QUEUE = dict(lane_stride=1)  # one launch from the queue
-PLANNED = dict(lane_stride=1, schedule=2, plan=2, probe_spp=32)  # 32 samples from the queue, the rest as planned chains
-LAUNCHES = {"queue": (40, QUEUE), "planned": (64, PLANNED)}
-
-
-def assert_launch(mode, launch, fast=1):
-    assert mode["fast_path"] == fast and mode["lane_stride"] == 1 and mode["wave_priority_every"] > 0, mode
-    if launch == "queue":
-        assert mode["scheduled"] == 0 and mode["planned_chains"] == 0, mode
-    else:
-        assert mode["scheduled"] == 1 and mode["first_pass_resumed"] == 1 and mode["planned_chains"] == 1, mode
-        assert mode["first_pass_samples"] == 32, mode
-
-
 def test_frame_with_no_option_named():
     """40 samples as a caller gets them: whatever kernel the library picks, the oracle's frame."""
     g = gpu("cornell_box", 40, 50)
-    print("mode", g[4])
+    print("mode", g.mode)
     assert_is_the_oracles(g, oracle("cornell_box", 40, 50), "default options")
 
 
@@ -123,17 +88,17 @@ def test_fast_kernels(launch):
     """queue: kFastQueue alone.  planned: both launches, kFastQueue then kFastChains on the pass it left."""
     spp, opts = LAUNCHES[launch]
     g = gpu("cornell_box", spp, 50, **opts)
-    print("mode", g[4])
-    assert_launch(g[4], launch)
+    print("mode", g.mode)
+    assert_launch(g.mode, launch)
     assert_is_the_oracles(g, oracle("cornell_box", spp, 50), launch)
 
 
 def test_scheduled_frame_resumed_from_the_queue():
     """40 samples with a schedule forced on them: two first samples, the rest by kFastQueue on a resumed pass."""
     g = gpu("cornell_box", 40, 50, lane_stride=1, schedule=2)
-    print("mode", g[4])
-    assert g[4]["fast_path"] == 1 and g[4]["scheduled"] == 1 and g[4]["first_pass_resumed"] == 1, g[4]
-    assert g[4]["planned_chains"] == 0, g[4]
+    print("mode", g.mode)
+    assert g.mode["fast_path"] == 1 and g.mode["scheduled"] == 1 and g.mode["first_pass_resumed"] == 1, g.mode
+    assert g.mode["planned_chains"] == 0, g.mode
     assert_is_the_oracles(g, oracle("cornell_box", 40, 50), "resumed queue")
 
 
@@ -141,7 +106,7 @@ def test_scheduled_frame_resumed_from_the_queue():
 def test_general_kernel_is_the_guard(launch):
     spp, opts = LAUNCHES[launch]
     g = gpu("cornell_box", spp, 50, fast_path=-1, **opts)
-    assert_launch(g[4], launch, fast=0)
+    assert_launch(g.mode, launch, fast=0)
     assert_is_the_oracles(g, oracle("cornell_box", spp, 50), "general kernel, " + launch)
 
 
@@ -149,7 +114,7 @@ def test_general_kernel_is_the_guard(launch):
 def test_image_order_frame_is_one_launch(fast_path):
     """8 samples: no schedule, one launch that draws from the queue (fast: kFastQueue alone)."""
     g = gpu("cornell_box", 8, 50, lane_stride=1, fast_path=fast_path)
-    assert g[4]["scheduled"] == 0 and g[4]["fast_path"] == (1 if fast_path == 1 else 0), g[4]
+    assert g.mode["scheduled"] == 0 and g.mode["fast_path"] == (1 if fast_path == 1 else 0), g.mode
     assert_is_the_oracles(g, oracle("cornell_box", 8, 50), "image order")
 
 
@@ -160,7 +125,7 @@ def test_depth_limit_cuts_paths_that_owe(depth, launch):
     where the debt is paid, before that hit is looked at, so the lane's next sample starts at depth 0 without it."""
     spp, opts = LAUNCHES[launch]
     g = gpu("cornell_box", spp, depth, **opts)
-    assert_launch(g[4], launch)
+    assert_launch(g.mode, launch)
     assert_is_the_oracles(g, oracle("cornell_box", spp, depth), "depth %d, %s" % (depth, launch))
 
 
@@ -168,7 +133,7 @@ def test_depth_limit_cuts_paths_that_owe(depth, launch):
 def test_spheres_metal_and_dielectric_never_defer():
     """Metal with and without fuzz and dielectric beside Lambertian (a sphere scene: the general kernel)."""
     g = gpu("spheres", 16, 8)
-    assert g[4]["fast_path"] == 0, g[4]
+    assert g.mode["fast_path"] == 0, g.mode
     assert_is_the_oracles(g, oracle("spheres", 16, 8), "spheres")
 
 
@@ -176,7 +141,7 @@ def test_fast_kernels_mix_lanes_that_owe_with_lanes_that_do_not():
     """The same materials on list triangles, where the fast kernels run: a wave holds Lambertian lanes that owe, metal
     and dielectric lanes that normalised once in their branch, and new camera rays."""
     g = gpu("mixed_list", 16, 8, lane_stride=1)
-    assert g[4]["fast_path"] == 1, g[4]
+    assert g.mode["fast_path"] == 1, g.mode
     assert_is_the_oracles(g, oracle("mixed_list", 16, 8), "mixed list")
 
 
@@ -187,9 +152,9 @@ def test_one_camera_ray_sends_the_wave_through_the_ieee_forms(launch):
     those iterations the whole wave, its Lambertian lanes that owe included, normalises by division and sqrtf."""
     spp, opts = LAUNCHES[launch]
     g = gpu("slow_camera", spp, 50, **opts)
-    assert_launch(g[4], launch)
+    assert_launch(g.mode, launch)
     want = oracle("slow_camera", spp, 50)
-    assert want[1].min() >= spp * 2, "every path of this camera bounces off a wall"
+    assert want.counts.min() >= spp * 2, "every path of this camera bounces off a wall"
     assert_is_the_oracles(g, want, "slow form, " + launch)
 
 

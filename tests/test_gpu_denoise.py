@@ -1,5 +1,5 @@
 """rtmi_denoise / rtmi_resolve_variance / Renderer.denoise on the GPU, bit for bit against the numpy restatements of
-tests/test_denoise_host.py (``denoise_rule``, ``variance_rule``), and the one thing no restatement can say: that the
+tests/filter_rules.py (``denoise_rule``, ``variance_rule``), and the one thing no restatement can say: that the
 filter lowers the error of a low-sample frame.
 
 The exactness inputs are synthetic (``synthetic``): patches of a few surface orientations and depths with noise on both,
@@ -22,40 +22,17 @@ import pytest
 import common
 import rtmi
 from filters_truth import same_or_nan, synthetic
-from test_budget_host import _frame
-from test_denoise_host import denoise_rule, variance_rule
+from abi_host import CHECK_LIB, ROOT, _frame
+from filter_rules import denoise_rule, on_gpu, run, variance_rule
+from parity import bits, same
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK_LIB = os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")
 GUIDES = ("variance", "normal", "depth", "alpha", "albedo")
 SHAPES = [(1, 1), (3, 70), (70, 3), (33, 70), (16, 16)]
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=F32).view(np.uint32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def on_gpu(d):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
-
-
-def run(d, demodulate, **opts):
-    """rtmi.denoise on the inputs of dict d (numpy) -> (out, out_variance) as numpy."""
-    t = on_gpu(d)
-    if not demodulate:
-        t.pop("albedo")
-    out, var = rtmi.denoise(**t, return_variance=True, **opts)
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), var.cpu().numpy()
 
 
 def want(d, demodulate, **opts):

@@ -7,34 +7,19 @@ import pytest
 
 import oraclelib
 import rtmi
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
 from rtmi.scenes import v3, PI_D
 
 pytestmark = pytest.mark.gpu
 
 
-def both(fill, seed=5):
-    out = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-        b = make(seed)
-        b.camera_pinhole(v3(0, 0.5, 3), v3(0, 0.3, 0), v3(0, 1, 0), PI_D / 3, 1.25)
-        fill(b)
-        out.append(b)
-    return out
-
-
 def render_both(fill, h=24, w=30, spp=3, depth=10, post=True):
-    import torch
-    o, p = both(fill)
-    o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth, post=post)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth, post).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb)
-    return o_rgb, o_rays
+    def camera(b):
+        b.camera_pinhole(v3(0, 0.5, 3), v3(0, 0.3, 0), v3(0, 1, 0), PI_D / 3, 1.25)
+    ob, pb = build_pair(fill, 5, camera)
+    o = oracle_frame(ob, h, w, spp, depth, post)
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth, post), o, "edge case")
+    return o.image, o.counts
 
 
 def test_world_without_sky_misses_are_black():
@@ -165,12 +150,10 @@ def test_tiny_faces_seen_from_far_away(dist, mode):
     an entered leaf, reports those hits.  The search boxes are widened in proportion to the ray
     origin's distance (MESH_DIST_SLACK), so the mesh search must still find every face the test
     accepts: image, ray counts and ray total equal the oracle's."""
-    import torch
     faces = _tiny_sheet()
     h, w, spp, depth = 28, 36, 2, 4
-    res = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-        b = make(9)
+
+    def fill(b):
         grey = b.lambertian(v3(0.8, 0.8, 0.8))
         if mode == "mirror":
             # camera just above the sheet looking up at a mirror `dist` away: the rays come back down
@@ -182,15 +165,7 @@ def test_tiny_faces_seen_from_far_away(dist, mode):
             b.camera_pinhole(pos, v3(0.0031, 0, 0.0017), v3(0, 1, 0), float(2.0 * np.arctan(0.03 / dist)), w / h)
         b.bvh(faces, grey, k_min=64)
         b.sky()
-        res.append(b)
-    o, p = res
-    o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert o_total > h * w * spp * (2.2 if mode == "mirror" else 1.0)  # the sheet is hit at all
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb)
+    ob, pb = build_pair(fill, 9)
+    o = oracle_frame(ob, h, w, spp, depth)
+    assert o.total > h * w * spp * (2.2 if mode == "mirror" else 1.0)  # the sheet is hit at all
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth), o, "%s from %g" % (mode, dist))

@@ -29,9 +29,10 @@ import common
 import oraclelib
 import rtmi
 from rtmi import scenes
-from test_features_host import resolve_rule
-from test_gpu_budget import CHECK_LIB, H, ROOT, W, OracleReplay, Shards, assert_same_results, random_budget, same
-from test_gpu_trace import glm_normalize
+from abi_host import CHECK_LIB, ROOT
+from budgetlib import ADAPTIVE, H, W, OracleReplay, Shards, assert_same_results, plan_rule, random_budget, resolve_rule
+from parity import same
+from querylib import glm_normalize
 
 pytestmark = pytest.mark.gpu
 
@@ -465,8 +466,6 @@ def test_resolve_features_matches_the_numpy_rule():
 
 # ------------------------------------------------------------------ 9. adaptive
 def test_render_adaptive_carries_the_features():
-    from test_gpu_budget import ADAPTIVE
-    from test_budget_host import plan_rule
     name, depth = "cornell_box", 10
     plain = FShards(name, depth, 64)
     res0 = plain.R[0].render_adaptive(**ADAPTIVE)

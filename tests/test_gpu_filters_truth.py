@@ -7,7 +7,7 @@ import pytest
 import common
 import filters_truth as T
 import rtmi
-from test_gpu_denoise import run as device_denoise
+from filter_rules import run as device_denoise
 
 pytestmark = pytest.mark.gpu
 

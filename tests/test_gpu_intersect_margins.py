@@ -4,7 +4,7 @@ The query kernel answers through the render's closest-hit engine, whose culled l
 mesh search are exact only because padded bounds and distance slacks cover the binary32 tests' reach.
 Caller-made rays can aim straight at that budget, so `librtmi_check1.so` (-DRTMI_CHECK_MARGINS: every query answered
 a second time without any cull; meshes by the reference's own tree walk) is run on adversarial query batches -- far
-origins, grazing sheets, needle meshes, needle lists, far sphere clouds (the worlds of test_gpu_round3.py) -- through
+origins, grazing sheets, needle meshes, needle lists, far sphere clouds (tests/worlds.py) -- through
 rtmi_intersect_check_counts, which exists only in that build.  A diagnostic build, so it runs in a process of its own
 (this file, run as a script, with RTMI_LIB_PATH pointing at it)."""
 import json
@@ -45,7 +45,7 @@ def _campaign():
     sys.path.insert(0, os.path.join(ROOT, "ray-tracing-cuda_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import rtmi
-    import test_gpu_round3 as t3
+    import worlds as t3
 
     assert os.path.samefile(rtmi.LIB_PATH, CHECK_LIB), rtmi.LIB_PATH
     L = rtmi.lib()

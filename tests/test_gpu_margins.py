@@ -18,8 +18,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK_LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib", "librtmi_check1.so")
+from abi_host import CHECK_LIB, ROOT
+
 # the campaign's tags on the scheduled paths (tests/margin_campaign.py): plain scenes, then the adversarial families
 PLAIN_SCHEDULED = {s + "@" + m for s in ("cornell_box_256x256x64_d50", "spheres_256x256x16_d8", "birthday_128x128x16_d10",
                                          "bunny_128x128x8_d10") for m in ("resumed", "probe_discarded")} | \

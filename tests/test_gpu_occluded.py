@@ -12,55 +12,12 @@ import pytest
 
 import oraclelib
 import rtmi
-from test_gpu_intersect import CUSTOM_WORLDS, SCENE_WORLDS, build, make_rays, textured_mesh, v3
+from querylib import (CUSTOM_WORLDS, F32_INF, SCENE_WORLDS, agree, build, filtered, gpu_filtered, gpu_occluded, make_rays, oracle_t,
+                      textured_mesh, v3)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-F32_INF = np.float32(np.inf)
-
-
-def oracle_t(ob, O, D):
-    """float32(t) of the oracle's closest hit per ray, +inf where there is none."""
-    t = np.full(len(O), F32_INF, dtype=np.float32)
-    for i in range(len(O)):
-        h, out, _ = ob.probe_hit(O[i], D[i])
-        if h:
-            t[i] = np.float32(out[0])
-    return t
-
-
-def filtered(t, tm):
-    """The definition: a hit, and float32(t) <= t_max (NaN t_max: clear; None: no limit)."""
-    if tm is None:
-        return np.isfinite(t)
-    with np.errstate(invalid="ignore"):
-        return np.isfinite(t) & (t <= tm)
-
-
-def gpu_occluded(b, O, D, tm=None, out=None):
-    o, d = torch.from_numpy(np.ascontiguousarray(O)).cuda(), torch.from_numpy(np.ascontiguousarray(D)).cuda()
-    t = None if tm is None else torch.from_numpy(np.ascontiguousarray(tm, dtype=np.float32)).cuda()
-    r = b.occluded(o, d, t, out=out).check()  # d_counts[0] (abandoned searches) stays 0
-    return r.mask.cpu().numpy(), r.fallback_rays()
-
-
-def gpu_filtered(b, O, D, tm=None):
-    o, d = torch.from_numpy(np.ascontiguousarray(O)).cuda(), torch.from_numpy(np.ascontiguousarray(D)).cuda()
-    t = None if tm is None else torch.from_numpy(np.ascontiguousarray(tm, dtype=np.float32)).cuda()
-    return (b.intersect(o, d, t).check().kind != rtmi.RTMI_HIT_NONE).cpu().numpy()
-
-
-def agree(b, O, D, tm, want, what):
-    """The occlusion answer equals `want` (the oracle's) and rtmi_intersect's filtered answer; returns fallback rays."""
-    got, fb = gpu_occluded(b, O, D, tm)
-    ref = gpu_filtered(b, O, D, tm)
-    bad = np.nonzero(got != want)[0]
-    assert len(bad) == 0, (what, len(bad), [(int(i), O[i].tolist(), D[i].tolist(), None if tm is None else float(tm[i]))
-                                             for i in bad[:8]])
-    assert np.array_equal(ref, want), (what, "rtmi_intersect disagrees with the oracle", np.nonzero(ref != want)[0][:8])
-    return fb
 
 
 def t_max_families(t, rng):
@@ -80,7 +37,7 @@ def t_max_families(t, rng):
     return fam
 
 
-# ------------------------------------------------------------------ worlds of test_gpu_intersect.py
+# ------------------------------------------------------------------ the query worlds (tests/querylib.py)
 @pytest.mark.parametrize("name", SCENE_WORLDS + sorted(CUSTOM_WORLDS))
 def test_occluded_matches_the_oracle(name):
     b, rec, ob, seed = build(name)

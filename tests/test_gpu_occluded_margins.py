@@ -51,7 +51,7 @@ def _campaign():
     sys.path.insert(0, os.path.join(ROOT, "ray-tracing-cuda_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import rtmi
-    import test_gpu_round3 as t3
+    import worlds as t3
 
     assert os.path.samefile(rtmi.LIB_PATH, CHECK_LIB), rtmi.LIB_PATH
     L = rtmi.lib()

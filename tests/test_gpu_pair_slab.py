@@ -18,48 +18,38 @@ import sys
 import numpy as np
 import pytest
 
-import oraclelib
 import rtmi
 import pair_slab_worlds as psw
-from test_gpu_deferred_normalise import assert_is_the_oracles, assert_launch
+from abi_host import CHECK_LIB, ROOT
+from pair_slab_worlds import assert_launch
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK_LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib", "librtmi_check1.so")
 H = W = psw.SIDE
 
 
 @functools.lru_cache(maxsize=None)
+def pair(world):
+    fill, seed, _ = psw.WORLDS[world]
+    return build_pair(lambda b: fill(b, W / H), seed)
+
+
+@functools.lru_cache(maxsize=None)
 def oracle(world, spp):
-    """(image, ray counts, final states (H*W, 6), ray total): computed once per frame, read by every case of it."""
-    fill, seed, depth = psw.WORLDS[world]
-    b = oraclelib.OracleBuilder(seed)
-    fill(b, W / H)
-    rgb, rays, states, total = b.render(H, W, spp, depth, post=True)
-    for a in (rgb, rays, states):
-        a.setflags(write=False)
-    return rgb, rays, states, total
+    """Computed once per frame, read by every case of it."""
+    return oracle_frame(pair(world)[0], H, W, spp, psw.WORLDS[world][2])
 
 
 def gpu(world, spp, **opts):
-    fill, seed, depth = psw.WORLDS[world]
-    b = rtmi.SceneBuilder(seed)
-    fill(b, W / H)
-    b.commit()
-    R = rtmi.Renderer(b, H, W, spp, depth, True).init_rng()
-    ro = rtmi.render_opts(**opts)
-    R.render(opts=ro)
-    R.check()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    pm = rtmi.pixel_map(R.frame)
-    st = np.ascontiguousarray(R.states.cpu().numpy().view(np.uint32).T)
-    states = np.zeros((H * W, 6), dtype=np.uint32)
-    states[pm[pm >= 0]] = st[pm >= 0]
-    return img.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), states, R.total_rays(), R.mode(ro)
+    return gpu_frame(pair(world)[1], H, W, spp, psw.WORLDS[world][2], opts=opts)
+
+
+def assert_is_the_oracles(got, want, what):
+    assert got.total > H * W, what  # the world is in view
+    assert_same_frame(got, want, what)
 
 
 FAST_WORLDS = ["cornell_box", "mixed_list", "sheets_4_light", "thin_pair", "axis_aligned", "inside_reach"]
@@ -71,8 +61,8 @@ def test_fast_kernels_cull_by_slab(world, launch):
     """queue: kFastQueue alone.  planned: kFastQueue for 32 samples, then kFastChains on the pass it left."""
     spp, opts = psw.LAUNCHES[launch]
     g = gpu(world, spp, **opts)
-    print("mode", g[4])
-    assert_launch(g[4], launch)
+    print("mode", g.mode)
+    assert_launch(g.mode, launch)
     assert_is_the_oracles(g, oracle(world, spp), "%s, %s" % (world, launch))
 
 
@@ -82,8 +72,8 @@ def test_camera_beyond_the_reach_gets_the_general_kernel(launch):
     say so (fast_path == 0) and the general kernel, with its per-ray slack, renders the oracle's frame."""
     spp, opts = psw.LAUNCHES[launch]
     g = gpu("beyond_reach", spp, **opts)
-    print("mode", g[4])
-    assert_launch(g[4], launch, fast=0)
+    print("mode", g.mode)
+    assert_launch(g.mode, launch, fast=0)
     assert_is_the_oracles(g, oracle("beyond_reach", spp), "beyond reach, " + launch)
 
 
@@ -110,7 +100,7 @@ def test_camera_update_across_the_reach_changes_the_kernel():
 def test_the_worlds_are_what_the_cases_say():
     """Every pair of the sheets is a candidate of every camera ray; the thin pair's record is unbounded; the axis-aligned
     camera's rays have a y direction component of exactly zero; the far cameras see the box."""
-    assert (oracle("sheets_4_light", 40)[1] >= 40 * 5).all()
+    assert (oracle("sheets_4_light", 40).counts >= 40 * 5).all()
     fill, seed, _ = psw.WORLDS["thin_pair"]
     b = rtmi.SceneBuilder(seed)
     fill(b, 1.0)
@@ -129,7 +119,7 @@ def test_the_worlds_are_what_the_cases_say():
         assert (d[..., 1] == 0).all() and (d[..., 2] == 800).all()
         assert np.abs(d[W // 2, :, 0]).max() <= 560.0 / W
     for world in ("inside_reach", "beyond_reach"):
-        assert oracle(world, 40)[1].min() >= 2 * 40, world  # every path of these cameras bounces off a wall
+        assert oracle(world, 40).counts.min() >= 2 * 40, world  # every path of these cameras bounces off a wall
 
 
 def test_the_check_build_agrees_on_every_query():

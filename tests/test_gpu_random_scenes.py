@@ -7,98 +7,19 @@ both sides of the uint8/uint16 id-stack switch."""
 import numpy as np
 import pytest
 
-import oraclelib
 import rtmi
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
 from rtmi.scenes import v3, PI_D
+from worlds import SCHEDULER_PATHS, random_case, scheduler_mesh_world
 
 pytestmark = pytest.mark.gpu
 
 
-def random_world(b, rng, n_objects, many_materials=False):
-    def col(lo=0.05, hi=0.95):
-        return v3(*rng.uniform(lo, hi, 3))
-
-    mats = []
-    n_mats = 300 if many_materials else int(rng.integers(3, 9))
-    for _ in range(n_mats):
-        k = rng.integers(0, 10)
-        if k < 5:
-            mats.append(b.lambertian(col()))
-        elif k < 7:
-            mats.append(b.metal(col(0.3, 1.0), float(rng.choice([0.0, rng.uniform(0.05, 0.9), 1.7]))))
-        elif k < 9:
-            mats.append(b.dielectric(col(0.7, 1.0), float(rng.uniform(1.1, 2.0))))
-        else:
-            mats.append(b.diffuse_light(b.constant_texture(col(1.0, 6.0))))
-    light = b.diffuse_light(b.constant_texture(v3(5, 5, 5)))
-
-    def pick():
-        return mats[int(rng.integers(0, len(mats)))]
-
-    b.sphere(v3(0, -100.5, -1), 100.0, mats[0])
-    sky_at = int(rng.integers(0, n_objects))
-    for i in range(n_objects):
-        if i == sky_at:
-            b.sky()
-        c = rng.uniform(-2.5, 2.5, 3)
-        c[1] = abs(c[1]) * 0.6
-        c[2] -= 2.0
-        k = rng.integers(0, 6)
-        if k == 0:
-            b.sphere(v3(*c), float(rng.uniform(0.15, 0.6)), pick())
-        elif k == 1:
-            e1, e2 = rng.uniform(-0.8, 0.8, 3), rng.uniform(-0.8, 0.8, 3)
-            b.parallelogram([v3(*c), v3(*(c + e1)), v3(*(c + e2))], pick())
-        elif k == 2:
-            e = rng.uniform(0.2, 0.7, 3)
-            b.parallelepiped([v3(*c), v3(c[0] + e[0], c[1], c[2]), v3(c[0], c[1] + e[1], c[2]),
-                              v3(c[0], c[1], c[2] + e[2])], pick())
-        elif k == 3:
-            b.triangle([v3(*c), v3(*(c + rng.uniform(-0.9, 0.9, 3))), v3(*(c + rng.uniform(-0.9, 0.9, 3)))], pick())
-        elif k == 4:
-            ang = np.float32(rng.uniform(0, 3.0))
-            off = v3(*c)
-            from rtmi.scenes import rotate_y
-            b.parallelepiped_lengths(v3(*rng.uniform(0.2, 0.7, 3)), pick(), lambda p, a=ang, o=off: rotate_y(p, a) + o)
-        else:
-            n = int(rng.integers(1, 40))
-            base = rng.uniform(-0.4, 0.4, (n, 1, 3)) + c
-            faces = (base + rng.uniform(-0.25, 0.25, (n, 3, 3))).astype(np.float32)
-            b.bvh(faces, pick(), k_min=int(rng.choice([2, 8, 2048])))
-    b.parallelogram([v3(-1, 3.5, -3), v3(1, 3.5, -3), v3(-1, 3.5, -1)], light)
-
-
 @pytest.mark.parametrize("seed", list(range(12)))
 def test_random_world_bit_exact(seed):
-    import torch
-    rng = np.random.default_rng(1000 + seed)
-    h, w = int(rng.integers(9, 41)), int(rng.integers(9, 57))
-    spp, depth = int(rng.integers(1, 7)), int(rng.choice([1, 3, 10, 25, 64]))
-    post = bool(rng.integers(0, 2))
-    n_objects = int(rng.integers(3, 14))
-    many = seed % 6 == 5
-    defocus = seed % 4 == 3
-    state = rng.bit_generator.state
-    results = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-        rng.bit_generator.state = state  # both builders see the same random stream
-        b = make(77 + seed)
-        if defocus:
-            b.camera_defocus(v3(0, 1.0, 2.5), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h, 0.2, 4.0)
-        else:
-            b.camera_pinhole(v3(0, 1.0, 2.5), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h)
-        random_world(b, rng, n_objects, many)
-        results.append(b)
-    o, p = results
-    o_rgb, o_rays, o_states, o_total = o.render(h, w, spp, depth, post=post)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth, post).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb), np.abs(img.cpu().numpy() - o_rgb).max()
+    fill, h, w, spp, depth, post, _ = random_case(seed)
+    ob, pb = build_pair(fill, 77 + seed)
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth, post), oracle_frame(ob, h, w, spp, depth, post), "seed %d" % seed)
 
 
 def _layer_stack(n_layers, rng, jitter):
@@ -127,13 +48,11 @@ def test_many_hit_leaves_along_one_ray(case):
     """Mesh rays that hold hits in tens of reference leaves at once (more than kHitSlots):
     the search defers the leaves beyond its list to further passes; the result must still be
     the reference's in-order walk, bit for bit."""
-    import torch
     n_layers, k_min, kind, jitter, floor = case
     h, w, spp, depth = 24, 40, 3, 30
-    results = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
+
+    def fill(b):
         rng = np.random.default_rng(4242)
-        b = make(5)
         # the camera looks along +x through the whole stack
         b.camera_pinhole(v3(-4.5, 0.2, -1.9), v3(0, 0.15, -1.9), v3(0, 1, 0), PI_D / 4, w / h)
         if kind == "dielectric":
@@ -148,18 +67,10 @@ def test_many_hit_leaves_along_one_ray(case):
         else:
             b.parallelogram([v3(-50, -0.7, -50), v3(50, -0.7, -50), v3(-50, -0.7, 50)], b.lambertian(v3(0.5, 0.5, 0.5)))
         b.sky()
-        results.append(b)
-    o, p = results
-    o_rgb, o_rays, o_states, o_total = o.render(h, w, spp, depth, post=False)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth, False).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert o_total > h * w * spp * (2 if kind == "dielectric" else 1)  # paths do continue through the stack
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb), np.abs(img.cpu().numpy() - o_rgb).max()
+    ob, pb = build_pair(fill, 5)
+    o = oracle_frame(ob, h, w, spp, depth, post=False)
+    assert o.total > h * w * spp * (2 if kind == "dielectric" else 1)  # paths do continue through the stack
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth, post=False), o, str(case))
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
@@ -170,45 +81,14 @@ def test_scheduler_paths_agree_on_random_mesh_worlds(seed):
     helper-wave rule -- must give the same image, ray counts and ray total bit for bit.  (The oracle
     comparison of such worlds is test_random_world_bit_exact; this one is large enough for the
     scheduler to matter: 192x256 at 64 spp.)"""
-    import torch
-    from rtmi.scenes import procedural_bunny_mesh
-    rng = np.random.default_rng(500 + seed)
-    h, w, spp, depth = 192, 256, 64, int(rng.choice([6, 12, 30]))
-    b = rtmi.SceneBuilder(90 + seed)
-    b.camera_pinhole(v3(0.0, 0.16, -0.55), v3(0.0, 0.1, 0.0), v3(0, 1, 0), PI_D / 4, w / h)
-    mats = [b.lambertian(v3(1, 1, 1)), b.metal(v3(0.9, 0.85, 0.8), 0.05), b.dielectric(v3(0.95, 0.95, 1.0), 1.4)]
-    mesh = procedural_bunny_mesh(int(rng.integers(10, 24)))
-    for k in range(int(rng.integers(1, 4))):
-        off = np.array([0.17 * (k - 1), 0.0, 0.05 * k], dtype=np.float32)
-        b.bvh((mesh + off).astype(np.float32), mats[int(rng.integers(0, 3))], k_min=int(rng.choice([4, 64, 2048])))
-    if seed % 2:
-        b.sphere(v3(0, -100.0 + 0.03, 0), 100.0, b.lambertian(v3(0.5, 0.6, 0.5)))
-    else:
-        b.parallelogram([v3(-5, 0.03, -5), v3(5, 0.03, -5), v3(-5, 0.03, 5)], b.lambertian(v3(0.5, 0.6, 0.5)))
-    b.sky()
-    b.commit()
-
-    def run(world, **opts):
-        tiles, counts, total = [], [], 0
-        o = rtmi.render_opts(**opts)
-        for r in range(world):
-            R = rtmi.Renderer(b, h, w, spp, depth, True, rank=r, world_size=world).init_rng()
-            R.render(opts=o)
-            total += R.total_rays()
-            tiles.append(R.tiles), counts.append(R.ray_counts)
-        img, cnt = R.untile(torch.cat(tiles, 0).contiguous(), torch.cat(counts, 0).contiguous())
-        torch.cuda.synchronize()
-        return img.cpu().numpy(), cnt.cpu().numpy(), total
-
-    plain = run(1, schedule=0)
-    forced = run(1, schedule=2)
-    sharded = run(2, schedule=2)
-    solo = run(1, schedule=2, sparse_stride=1)    # outlier pixels packed 64 to a wave
-    few = run(1, schedule=2, sparse_stride=64)    # ... or one to a wave
-    shared = run(1, schedule=2, exclusive=0)      # ... or sharing their wave with ordinary pixels
-    for other in (forced, sharded, solo, few, shared):
-        assert np.array_equal(plain[0], other[0]) and np.array_equal(plain[1], other[1]) and plain[2] == other[2]
-    assert plain[2] > h * w * spp * 1.2
+    fill, h, w, spp, depth = scheduler_mesh_world(seed)
+    pb = rtmi.SceneBuilder(90 + seed)
+    fill(pb)
+    pb.commit()
+    plain = gpu_frame(pb, h, w, spp, depth, opts=SCHEDULER_PATHS[0][1])
+    for world, opts in SCHEDULER_PATHS[1:]:
+        assert_same_frame(gpu_frame(pb, h, w, spp, depth, opts=opts, world=world), plain, "%d shard(s), %s" % (world, opts))
+    assert plain.total > h * w * spp * 1.2
 
 
 def _nested_world(b, rng):
@@ -251,25 +131,13 @@ def test_nested_lists_match_the_nested_oracle(seed):
     """The library inlines nested HitableLists; the oracle builds them as real nested objects whose
     Hit() calls recurse (hitable_list.cu:7-25).  Image, ray counts and ray total must agree bit for
     bit -- including where coincident surfaces of different nesting levels tie."""
-    import torch
     h, w, spp, depth = 40, 52, 4, 12
-    res = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-        rng = np.random.default_rng(900 + seed)
-        b = make(31 + seed)
+
+    def fill(b):
         b.camera_pinhole(v3(0, 0.8, 2.2), v3(0, 0.6, -1), v3(0, 1, 0), PI_D / 3, w / h)
-        _nested_world(b, rng)
-        res.append(b)
-    o, p = res
-    o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb)
+        _nested_world(b, np.random.default_rng(900 + seed))
+    ob, pb = build_pair(fill, 31 + seed)
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth), oracle_frame(ob, h, w, spp, depth), "seed %d" % seed)
 
 
 def _clump(n, rng, spread):
@@ -289,27 +157,17 @@ def test_sparse_waves_start_from_the_top_table(case):
     """Waves with a handful of rays (tiny frames) on deep, clumped meshes with small reference leaves:
     the search starts from the mesh's table of sub-trees, runs in its four- and two-lanes-per-entry
     modes, and the replay reads leaf-path rows of 8, 16 and 32 words, from LDS and from global memory."""
-    import torch
     h, w, spp, depth, n_faces, k_min, n_meshes = case
-    results = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
+
+    def fill(b):
         rng = np.random.default_rng(977)
-        b = make(31)
         b.camera_pinhole(v3(0.1, 0.4, 1.2), v3(0, 0.3, -2.0), v3(0, 1, 0), PI_D / 5, w / h)
         mats = [b.dielectric(v3(0.95, 0.97, 0.99), 1.2), b.metal(v3(0.9, 0.85, 0.8), 0.2), b.lambertian(v3(0.8, 0.7, 0.6))]
         for i in range(n_meshes):
             b.bvh(_clump(n_faces, rng, 0.05 if i == 0 else 1.0), mats[i % 3], k_min=k_min)
         b.parallelogram([v3(-50, -0.7, -50), v3(50, -0.7, -50), v3(-50, -0.7, 50)], b.lambertian(v3(0.5, 0.5, 0.5)))
         b.sky()
-        results.append(b)
-    o, p = results
-    o_rgb, o_rays, o_states, o_total = o.render(h, w, spp, depth, post=False)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth, False).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert o_total > h * w * spp  # the meshes are in view
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy(), o_rgb), np.abs(img.cpu().numpy() - o_rgb).max()
+    ob, pb = build_pair(fill, 31)
+    o = oracle_frame(ob, h, w, spp, depth, post=False)
+    assert o.total > h * w * spp  # the meshes are in view
+    assert_same_frame(gpu_frame(pb, h, w, spp, depth, post=False), o, str(case))

@@ -11,22 +11,13 @@ import pytest
 
 import common
 import refcases as rc
-from test_gpu_parity import REL_L2_TOL, gpu_states_rowmajor
+import rtmi
+from parity import Frame, assert_same_frame, gpu_frame
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def gpu_frame(name, h, w, spp, post, seed):
-    import torch
-    import rtmi
-    b = rc.build_frame_scene(rtmi.SceneBuilder(seed), name, w / h).commit()
-    R = rtmi.Renderer(b, h, w, spp, rc.DEPTH, post).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), gpu_states_rowmajor([R.states], h, w), R.total_rays()
+REL_L2_TOL = 1e-3  # as tests/test_gpu_parity.py: "image within 1e-3 relative L2 of reference"
 
 
 @pytest.mark.parametrize("post", [True, False], ids=["post", "raw"])
@@ -34,12 +25,10 @@ def gpu_frame(name, h, w, spp, post, seed):
 def test_render_matches_reference_frame(name, h, w, spp, post):
     g = np.load(os.path.join(GOLDEN, rc.frame_file(name, h, w, spp, post)))
     for k, seed in enumerate(rc.SEEDS):
-        rgb, rays, states, total = gpu_frame(name, h, w, spp, post, seed)
-        assert total == int(g["total"][k])
-        assert np.array_equal(rays, g["rays"][k])
-        assert np.array_equal(states, g["states"][k])
-        if name == "birthday":
-            assert common.rel_l2(rgb, g["rgb"][k]) <= REL_L2_TOL
-        else:
-            assert np.array_equal(rgb.view(np.uint32), g["rgb"][k].view(np.uint32)), "%s seed %d: %d values differ" % (
-                name, seed, int((rgb != g["rgb"][k]).sum()))
+        pb = rc.build_frame_scene(rtmi.SceneBuilder(seed), name, w / h).commit()
+        got = gpu_frame(pb, h, w, spp, rc.DEPTH, post)
+        want = Frame(g["rgb"][k], g["rays"][k], g["states"][k], int(g["total"][k]), None)
+        if name == "birthday":  # the image within the tolerance; everything else exact
+            assert common.rel_l2(got.image, want.image) <= REL_L2_TOL
+            got = got._replace(image=want.image)
+        assert_same_frame(got, want, "%s seed %d" % (name, seed))

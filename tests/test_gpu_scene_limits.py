@@ -5,14 +5,14 @@
   * sphere runs at the grouping limit (65,535 spheres grouped, 65,536 scanned one by one), one material per sphere;
   * worlds of many meshes: per-mesh top tables, list-order ties between meshes, nested lists, and the LDS staging of
     reference nodes (kLdsNodes) and leaf paths (kLdsPaths) running out inside a later mesh.
-Renders compare image, per-pixel ray counts and the ray total; rtmi_intersect / rtmi_occluded compare every answer."""
+Renders compare image, per-pixel ray counts, final RNG states and the ray total; rtmi_intersect / rtmi_occluded compare
+every answer."""
 import numpy as np
 import pytest
 
-import oraclelib
+import querylib as ql
 import rtmi
-import test_gpu_intersect as ti
-import test_gpu_occluded as to
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
 from rtmi.scenes import v3, PI_D, procedural_bunny_mesh
 
 pytestmark = pytest.mark.gpu
@@ -26,60 +26,33 @@ LANES_16 = dict(schedule=2, lane_stride=16)
 
 
 # ------------------------------------------------------------------ rendering both sides
-def pair(fill, seed=5):
+def pair(fill):
     """The same world on the oracle and on the product (committed), the product's behind a Recorder."""
-    ob = oraclelib.OracleBuilder(seed)
-    fill(ob)
-    rec = ti.Recorder(rtmi.SceneBuilder(seed))
-    fill(rec)
-    rec.b.commit()
-    return ob, rec
-
-
-def oracle(ob, h, w, spp, depth):
-    rgb, rays, _, total = ob.render(h, w, spp, depth)
-    return rgb, rays, total
-
-
-def product(pb, h, w, spp, depth, opts=None, world=1):
-    o = rtmi.render_opts(**opts) if opts is not None else None
-    tiles, counts, total = [], [], 0
-    for r in range(world):
-        R = rtmi.Renderer(pb, h, w, spp, depth, True, rank=r, world_size=world).init_rng()
-        R.render(opts=o)
-        if o is not None:
-            R.check()
-        total += R.total_rays()
-        tiles.append(R.tiles), counts.append(R.ray_counts)
-    img, cnt = R.untile(torch.cat(tiles, 0).contiguous(), torch.cat(counts, 0).contiguous())
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), total
+    return build_pair(fill, 5, record=True)
 
 
 def assert_same(g, o, what):
-    assert g[2] == o[2], "%s: ray totals %d vs %d" % (what, g[2], o[2])
-    assert np.array_equal(g[1], o[1]), "%s: %d pixels with different ray counts" % (what, (g[1] != o[1]).sum())
-    bad = ~((g[0] == o[0]) | (np.isnan(g[0]) & np.isnan(o[0])))
-    assert not bad.any(), "%s: %d pixel channels differ (max abs %g)" % (what, bad.sum(), np.nanmax(np.abs(g[0] - o[0])))
+    """NaN-tolerant, as this file always compared: a NaN must sit in the same pixel channel of both frames."""
+    assert_same_frame(g, o, what, nan_ok=True)
 
 
 def queries_agree(ob, rec, seed, n_family=200, identities=True):
     """rtmi_intersect (kind, t, normal, material, u, v, entry) and rtmi_occluded with t_max just below and just above
     each hit, against the oracle; no abandoned search in either."""
-    O, D = ti.make_rays(ob, seed, n_family)
-    raw = ti.gpu_intersect(rec.b, O, D).raw.cpu().numpy()
-    bad = ti.compare(raw, ob, O, D, rec)
+    O, D = ql.make_rays(ob, seed, n_family)
+    raw = ql.gpu_intersect(rec.b, O, D).raw.cpu().numpy()
+    bad = ql.compare(raw, ob, O, D, rec)
     assert not bad, bad[:4]
     # `entry` / `element` on a sample: a world of just that hitable (or face) gives the same t for the same ray
     if identities:  # (replays the recorded scene once per sample: not for tables of 65536 materials)
-        bad = ti.check_identities(rec.b, rec, seed, O, D, raw, np.random.default_rng(seed))
+        bad = ql.check_identities(rec.b, rec, seed, O, D, raw, np.random.default_rng(seed))
         assert not bad, bad[:4]
-    t = to.oracle_t(ob, O, D)
+    t = ql.oracle_t(ob, O, D)
     fin = np.isfinite(t)
     below = np.where(fin, np.nextafter(t, np.float32(0)), np.float32(1e30)).astype(np.float32)
     above = np.where(fin, np.nextafter(t, np.float32(np.inf)), np.float32(1e30)).astype(np.float32)
     for tm, what in ((below, "t_max below the hits"), (above, "t_max above the hits")):
-        to.agree(rec.b, O, D, tm, to.filtered(t, tm), what)
+        ql.agree(rec.b, O, D, tm, ql.filtered(t, tm), what)
     return raw
 
 
@@ -172,31 +145,31 @@ def test_material_table_widths(n):
     ob, rec = pair(lambda b: material_world(b, n))
     assert rec.b.stats()["materials"] == n
     for depth in DEPTHS:
-        o = oracle(ob, H, W, SPP, depth)
-        assert depth < 2 or o[2] > H * W * SPP * 1.5  # paths bounce
-        assert_same(product(rec.b, H, W, SPP, depth), o, "%d materials, depth %d" % (n, depth))
+        o = oracle_frame(ob, H, W, SPP, depth)
+        assert depth < 2 or o.total > H * W * SPP * 1.5  # paths bounce
+        assert_same(gpu_frame(rec.b, H, W, SPP, depth), o, "%d materials, depth %d" % (n, depth))
 
 
 @pytest.mark.parametrize("n", WIDTHS)
 def test_material_table_widths_signed_colour(n):
     ob, rec = pair(lambda b: material_world(b, n, signed=True))
     for depth in (2, 63):
-        assert_same(product(rec.b, H, W, SPP, depth), oracle(ob, H, W, SPP, depth),
+        assert_same(gpu_frame(rec.b, H, W, SPP, depth), oracle_frame(ob, H, W, SPP, depth),
                     "%d materials, signed, depth %d" % (n, depth))
 
 
 def test_image_textured_parallelogram_above_65535():
     ob, rec = pair(lambda b: material_world(b, 70000, textured=66000))
     for depth in (2, 64):
-        assert_same(product(rec.b, H, W, SPP, depth), oracle(ob, H, W, SPP, depth), "textured, depth %d" % depth)
+        assert_same(gpu_frame(rec.b, H, W, SPP, depth), oracle_frame(ob, H, W, SPP, depth), "textured, depth %d" % depth)
 
 
 @pytest.mark.parametrize("n", (65537, 70000))
 def test_material_ids_above_65535_resumed_and_sharded(n):
     ob, rec = pair(lambda b: material_world(b, n))
-    o = oracle(ob, H, W, SPP, 10)
-    assert_same(product(rec.b, H, W, SPP, 10, opts=RESUMED), o, "%d materials, resumed" % n)
-    assert_same(product(rec.b, H, W, SPP, 10, world=3), o, "%d materials, 3 shards" % n)
+    o = oracle_frame(ob, H, W, SPP, 10)
+    assert_same(gpu_frame(rec.b, H, W, SPP, 10, opts=RESUMED), o, "%d materials, resumed" % n)
+    assert_same(gpu_frame(rec.b, H, W, SPP, 10, world=3), o, "%d materials, 3 shards" % n)
 
 
 @pytest.mark.parametrize("n", (256, 257, 65536, 65537, 70000))
@@ -239,9 +212,9 @@ def test_sphere_runs_at_the_grouping_limit(n_run, short_run):
     s = rec.b.stats()
     assert s["spheres"] == n_run + short_run and s["materials"] == n_run + 1 + short_run
     assert (s["materials"] > 65536) == (n_run > 65535)  # the ungrouped runs also hold material ids above 65535
-    o = oracle(ob, 16, 16, 2, 3)
-    assert o[2] > 16 * 16 * 2 * 1.5
-    assert_same(product(rec.b, 16, 16, 2, 3), o, "%d + %d spheres" % (n_run, short_run))
+    o = oracle_frame(ob, 16, 16, 2, 3)
+    assert o.total > 16 * 16 * 2 * 1.5
+    assert_same(gpu_frame(rec.b, 16, 16, 2, 3), o, "%d + %d spheres" % (n_run, short_run))
 
 
 # ------------------------------------------------------------------ 3. many meshes
@@ -323,10 +296,10 @@ def test_many_meshes(n_meshes, k_min, mesh_n):
         assert per < 512 < s["bvh_nodes"]
         assert leaf_path_words_at_least(per) < 1024 < n_bvh * leaf_path_words_at_least(per)
     depth = 6
-    o = oracle(ob, H, W, 2, depth)
-    assert o[2] > H * W * 2 * 1.2
+    o = oracle_frame(ob, H, W, 2, depth)
+    assert o.total > H * W * 2 * 1.2
     for opts, what in ((None, "default"), (SPARSE_1, "sparse_stride=1"), (LANES_16, "lane_stride=16")):
-        assert_same(product(rec.b, H, W, 2, depth, opts=opts), o, "%d meshes, %s" % (n_meshes, what))
+        assert_same(gpu_frame(rec.b, H, W, 2, depth, opts=opts), o, "%d meshes, %s" % (n_meshes, what))
     raw = queries_agree(ob, rec, seed=n_meshes, n_family=300)
     kinds = raw[:, 7]
     assert (kinds == rtmi.RTMI_HIT_MESH).sum() >= 5

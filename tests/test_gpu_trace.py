@@ -14,7 +14,9 @@ import pytest
 import common
 import oraclelib
 import rtmi
-from test_gpu_intersect import CUSTOM_WORLDS, SCENE_WORLDS, build, make_rays
+from abi_host import ERR_DEPTH, ERR_INVALID, OK
+from parity import bits
+from querylib import CUSTOM_WORLDS, SCENE_WORLDS, build, glm_normalize, make_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -22,15 +24,6 @@ torch = pytest.importorskip("torch")
 
 DEPTHS = (0, 1, 8, 50)
 F0 = np.float32(0)
-OK, ERR_INVALID, ERR_DEPTH = 0, -1, -5  # include/rtmi.h
-
-
-def glm_normalize(v):
-    """glm::normalize in binary32: v * (1 / sqrt((x*x + y*y) + z*z)) (vecmath.hpp:40-53)."""
-    v = np.asarray(v, dtype=np.float32)
-    x, y, z = v[..., 0], v[..., 1], v[..., 2]
-    s = np.sqrt((x * x + y * y) + z * z).astype(np.float32)
-    return (v * (np.float32(1) / s)[..., None]).astype(np.float32)
 
 
 def raw_camera(ob, o):
@@ -83,10 +76,6 @@ def gpu_trace(b, O, D, states, depth, count_rays=True, stream=None):
     tr.check()
     rays = None if tr.rays is None else tr.rays.cpu().numpy().view(np.uint32)
     return tr.rgb.cpu().numpy(), rays, np.ascontiguousarray(st.cpu().numpy().view(np.uint32).T), tr
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
 
 
 def usable(O, D):

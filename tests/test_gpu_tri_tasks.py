@@ -13,38 +13,24 @@ import sys
 import numpy as np
 import pytest
 
-import oraclelib
 import rtmi
 import tri_tasks_worlds as worlds
-from test_gpu_intersect import Recorder, check_identities, compare, gpu_intersect, make_rays
-from test_gpu_occluded import filtered, gpu_filtered, gpu_occluded, oracle_t
-from test_gpu_parity import gpu_states_rowmajor
+from abi_host import CHECK_LIB, ROOT
+from parity import assert_same_frame, build_pair, gpu_frame, oracle_frame
+from querylib import check_identities, compare, filtered, gpu_filtered, gpu_intersect, gpu_occluded, make_rays, oracle_t
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK_LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib", "librtmi_check1.so")
 SEED = 7
 
 
 def render_both(fill, side, spp=4, depth=8):
-    o = oraclelib.OracleBuilder(SEED)
-    fill(o)
-    o_rgb, o_rays, o_states, o_total = o.render(side, side, spp, depth)
-    p = rtmi.SceneBuilder(SEED)
-    fill(p)
-    p.commit()
-    R = rtmi.Renderer(p, side, side, spp, depth).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    assert R.total_rays() == o_total
-    assert np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays)
-    assert np.array_equal(img.cpu().numpy().view(np.uint32), o_rgb.view(np.uint32))
-    assert np.array_equal(gpu_states_rowmajor([R.states], side, side), o_states), "final RNG states differ"
-    return p, o_rays
+    ob, pb = build_pair(fill, SEED)
+    o = oracle_frame(ob, side, side, spp, depth)
+    assert_same_frame(gpu_frame(pb, side, side, spp, depth), o, "%d x %d" % (side, side))
+    return pb, o.counts
 
 
 @pytest.mark.parametrize("light", [False, True])
@@ -83,11 +69,7 @@ def test_long_lists_gather_their_records(n_pairs):
 
 
 def _query_world(fill):
-    rec = Recorder(rtmi.SceneBuilder(SEED))
-    ob = oraclelib.OracleBuilder(SEED)
-    fill(rec)
-    fill(ob)
-    rec.b.commit()
+    ob, rec = build_pair(fill, SEED, record=True)
     return rec.b, rec, ob
 
 

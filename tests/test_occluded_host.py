@@ -9,11 +9,9 @@ import pytest
 
 import common
 import rtmi
-from test_query_host import QUERY_VARIANTS
+from abi_host import CHECK_LIB, QUERY_VARIANTS, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib")
-CHECK_LIB = os.path.join(LIB, "librtmi_check1.so")
+LIB = os.path.dirname(CHECK_LIB)
 
 
 def test_occluded_is_exported_by_both_builds():

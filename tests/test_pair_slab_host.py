@@ -12,8 +12,7 @@ import common
 import rtmi
 import pair_slab_worlds as psw
 import tri_tasks_worlds as worlds
-from test_budget_host import LIBS
-from test_tri_tasks_host import _count, _waves
+from abi_host import LIBS, _count, _waves
 
 F32, F64 = np.float32, np.float64
 

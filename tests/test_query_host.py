@@ -9,10 +9,9 @@ import pytest
 
 import common
 import rtmi
+from abi_host import QUERY_VARIANTS, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib")
-QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
 
 
 def test_intersect_is_exported():

@@ -9,13 +9,9 @@ import pytest
 
 import oraclelib
 import refcases as rc
+from refcases import bits
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
 
 
 def load(name):

@@ -23,14 +23,10 @@ import pytest
 
 import oraclelib
 import refcases as rc
+from refcases import bits
 import reflib
 
 pytestmark = pytest.mark.skipif(not reflib.available(), reason=reflib.SKIP_REASON)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
 
 
 def assert_same_bits(a, b, what):

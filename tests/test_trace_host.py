@@ -1,17 +1,15 @@
 """rtmi_trace / rtmi_rng_init_n on the host side: the argument checks that come before any HIP call, the Python
 binding's refusals, and the trace kernels in both builds of the library.  No GPU involved."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
 import common
 import rtmi
+from abi_host import ERR_INVALID, LIBS, OK, QUERY_VARIANTS
 
-QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
-OK, ERR_INVALID, ERR_NO_DEVICE, ERR_DEPTH = 0, -1, -2, -5  # include/rtmi.h
-LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]
+ERR_NO_DEVICE = -2  # include/rtmi.h
 
 
 def test_trace_entries_are_exported_and_bound():

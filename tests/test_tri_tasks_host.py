@@ -8,7 +8,7 @@ import pytest
 import common
 import rtmi
 import tri_tasks_worlds as worlds
-from test_budget_host import LIBS
+from abi_host import LIBS, _count, _waves
 
 TRIPTS_ABSENT = 1  # scene_dev.h
 TRI_SECOND = 1
@@ -57,15 +57,6 @@ def test_c2_still_fits_six_workgroups_per_cu():
     assert 0 < lds and 6 * lds <= 160 * 1024, lds
     # the records are staged: two of 48 bytes per pair more than a launch without the culled scan would ask for
     assert _builder(worlds.long_list(130)).render_lds_bytes(50, 256) < _builder(worlds.long_list(128)).render_lds_bytes(50, 256)
-
-
-def _count(blk, key):
-    return int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
-
-
-def _waves(vgprs):
-    """Waves per SIMD that a kernel's VGPR count allows on gfx950: 512 registers in granules of 8, eight waves at most."""
-    return min(8, 512 // (-(-vgprs // 8) * 8))
 
 
 # (vgpr_count, vgpr_spill_count, sgpr_spill_count) of the fast list kernels before the per-triangle tasks

@@ -35,7 +35,7 @@ def main():
     import numpy as np
     import torch
     import rtmi
-    from test_accumulate_host import camera_of, room
+    from filter_rules import camera_of, room
 
     h = w = a.size
     n = h * w

@@ -1,45 +1,28 @@
-"""One-off campaign: many seeded random worlds (tests/test_gpu_random_scenes.py's generator), each
-rendered by the oracle and through the C ABI, compared bit for bit.  usage: gpu_fuzz.py <first> <count>"""
+"""One-off campaigns: seeded worlds of tests/worlds.py, each rendered by the oracle and through the C ABI and compared
+bit for bit (tests/parity.py).  usage: gpu_fuzz.py <first> <count> [<soups> [<far views>]]"""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ray-tracing-cuda_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np, torch
-import oraclelib, rtmi
+import parity
 from rtmi.scenes import v3, PI_D
-from test_gpu_random_scenes import random_world
+from worlds import far_view_world, random_case, soup_world
+
+
+def differs(fill, seed, h, w, spp, depth, post, camera=None, nan_ok=False):
+    ob, pb = parity.build_pair(fill, seed, camera)
+    try:
+        parity.assert_same_frame(parity.gpu_frame(pb, h, w, spp, depth, post), parity.oracle_frame(ob, h, w, spp, depth, post),
+                                 "seed %d" % seed, nan_ok)
+    except AssertionError as e:
+        return str(e)
+
 
 first, count = int(sys.argv[1]), int(sys.argv[2])
 bad = 0
 t0 = time.time()
 for seed in range(first, first + count):
-    rng = np.random.default_rng(1000 + seed)
-    h, w = int(rng.integers(9, 41)), int(rng.integers(9, 57))
-    spp, depth = int(rng.integers(1, 7)), int(rng.choice([1, 3, 10, 25, 64]))
-    post = bool(rng.integers(0, 2))
-    n_objects = int(rng.integers(3, 14))
-    many = seed % 6 == 5
-    defocus = seed % 4 == 3
-    state = rng.bit_generator.state
-    res = []
-    for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-        rng.bit_generator.state = state
-        b = make(77 + seed)
-        if defocus:
-            b.camera_defocus(v3(0, 1.0, 2.5), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h, 0.2, 4.0)
-        else:
-            b.camera_pinhole(v3(0, 1.0, 2.5), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h)
-        random_world(b, rng, n_objects, many)
-        res.append(b)
-    o, p = res
-    o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth, post=post)
-    p.commit()
-    R = rtmi.Renderer(p, h, w, spp, depth, post).init_rng()
-    R.render()
-    img, cnt = R.untile()
-    torch.cuda.synchronize()
-    ok = R.total_rays() == o_total and np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays) and \
-        np.array_equal(img.cpu().numpy(), o_rgb)
-    if not ok:
+    fill, h, w, spp, depth, post, n_objects = random_case(seed)
+    if differs(fill, 77 + seed, h, w, spp, depth, post):
         bad += 1
         print("MISMATCH seed", seed, h, w, spp, depth, post, n_objects, flush=True)
 print("seeds %d..%d: %d mismatches, %.1fs" % (first, first + count - 1, bad, time.time() - t0), flush=True)
@@ -49,64 +32,24 @@ if len(sys.argv) > 3:
     bad = 0
     t0 = time.time()
     for seed in range(first, first + int(sys.argv[3])):
-        rng = np.random.default_rng(50000 + seed)
-        h, w = int(rng.integers(16, 49)), int(rng.integers(16, 65))
-        spp, depth = int(rng.integers(1, 5)), int(rng.choice([2, 8, 20, 50]))
-        n_mesh = int(rng.integers(1, 4))
-        soups = []
-        for _ in range(n_mesh):
-            n = int(rng.choice([1, 5, 40, 300, 1500]))
-            c = rng.uniform(-1.2, 1.2, 3); c[1] = abs(c[1]) * 0.5 + 0.2; c[2] -= 2.0
-            spread = float(rng.choice([0.05, 0.4, 1.0]))
-            base = rng.uniform(-spread, spread, (n, 1, 3)) + c
-            size = float(rng.choice([0.05, 0.3, 0.9]))
-            f = (base + rng.uniform(-size, size, (n, 3, 3))).astype(np.float32)
-            if rng.integers(0, 3) == 0:  # duplicated faces: equal t, ties by reference index
-                f = np.concatenate([f, f[: max(1, n // 3)]], 0)
-            soups.append((f, int(rng.choice([1, 2, 3, 8, 64, 2048])), int(rng.integers(0, 4))))
-        floor_sphere = bool(rng.integers(0, 2))
-        res = []
-        for make in (oraclelib.OracleBuilder, rtmi.SceneBuilder):
-            b = make(300 + seed)
-            b.camera_pinhole(v3(0, 0.8, 1.8), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h)
-            ms = [b.lambertian(v3(0.8, 0.7, 0.6)), b.metal(v3(0.9, 0.9, 0.8), 0.1), b.dielectric(v3(1, 1, 1), 1.0),
-                  b.dielectric(v3(0.9, 1, 0.9), 1.5)]
-            for f, kmin, mi in soups:
-                b.bvh(f, ms[mi], k_min=kmin)
-            if floor_sphere:
-                b.sphere(v3(0, -100.5, -1), 100.0, ms[0])
-            else:
-                b.parallelogram([v3(-30, -0.5, -30), v3(30, -0.5, -30), v3(-30, -0.5, 30)], ms[0])
-            b.sky()
-            res.append(b)
-        o, p = res
-        o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth, post=False)
-        p.commit()
-        R = rtmi.Renderer(p, h, w, spp, depth, False).init_rng()
-        R.render()
-        img, cnt = R.untile()
-        torch.cuda.synchronize()
-        ok = R.total_rays() == o_total and np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays) and \
-            np.array_equal(img.cpu().numpy(), o_rgb, equal_nan=True)
-        if not ok:
+        fill, h, w, spp, depth, what = soup_world(seed)
+        cam = lambda b: b.camera_pinhole(v3(0, 0.8, 1.8), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h)
+        if differs(fill, 300 + seed, h, w, spp, depth, False, cam, nan_ok=True):
             bad += 1
-            print("SOUP MISMATCH seed", seed, h, w, spp, depth, [(s[0].shape[0], s[1], s[2]) for s in soups], flush=True)
+            print("SOUP MISMATCH seed", seed, h, w, spp, depth, what, flush=True)
     print("soup seeds %d..%d: %d mismatches, %.1fs" % (first, first + int(sys.argv[3]) - 1, bad, time.time() - t0), flush=True)
 
-# ---- third campaign: small meshes seen from far away (tests/test_gpu_round3.py: far_view_world), the regime of
-# binary32 false accepts outside the leaves' exact boxes; worlds with faces thinner than 1.8 degrees (their nodes widen the search boxes for them: scene.hip face_slack_exponent)
-# (rtmi_scene_sliver_faces) are counted apart
+# ---- third campaign: small meshes seen from far away (far_view_world), the regime of binary32 false accepts outside the
+# leaves' exact boxes; worlds with faces thinner than 1.8 degrees (their nodes widen the search boxes for them: scene.hip
+# face_slack_exponent; rtmi_scene_sliver_faces) are counted apart
 if len(sys.argv) > 4:
-    import test_gpu_round3 as t3
     bad = bad_sliver = n_sliver = 0
     t0 = time.time()
     for seed in range(first, first + int(sys.argv[4])):
-        fill, cam, h, w, spp, depth, what = t3.far_view_world(seed)
-        g, o = t3.render_pair(fill, h, w, spp, depth, post=False, seed=500 + seed, camera=cam)
+        fill, cam, h, w, spp, depth, what = far_view_world(seed)
         slivers = what["slivers"]
         n_sliver += slivers > 0
-        ok = g[2] == o[2] and np.array_equal(g[1], o[1]) and np.array_equal(g[0], o[0], equal_nan=True)
-        if not ok:
+        if differs(fill, 500 + seed, h, w, spp, depth, False, cam, nan_ok=True):
             if slivers:
                 bad_sliver += 1
             else:

@@ -1,5 +1,5 @@
-"""One-off campaign (GPU box): the scheduling modes of round 4 on seeded random list worlds (tests/test_gpu_random_scenes.py's
-generator) at frames large enough to be scheduled (the fuzz worlds of tools/gpu_fuzz.py are a few hundred pixels: thin
+"""One-off campaign (GPU box): the scheduling modes of round 4 on seeded random list worlds (tests/worlds.py:
+random_world) at frames large enough to be scheduled (the fuzz worlds of tools/gpu_fuzz.py are a few hundred pixels: thin
 frames, no probe).  Every world is rendered by the plain queue in image order and then under every other mode -- longest-
 first queue, wave priorities, planned chains (also with one workgroup per CU: long chains and many take-overs), thin
 frames -- and all results must agree bit for bit (image, per-pixel ray counts, final RNG states, ray total); every
@@ -12,11 +12,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ray-tracing-cuda_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import torch
-import oraclelib
-import rtmi
+import parity
 from rtmi.scenes import v3, PI_D
-from test_gpu_random_scenes import random_world
+from worlds import random_world
+
+
+def differs(got, want, what):
+    try:
+        parity.assert_same_frame(got, want, what, nan_ok=True)
+    except AssertionError as e:
+        return str(e)
 
 first, count = int(sys.argv[1]), int(sys.argv[2])
 oracle_every = int(sys.argv[3]) if len(sys.argv) > 3 else 8
@@ -41,34 +46,21 @@ for seed in range(first, first + count):
     many = seed % 3 == 2
     state = rng.bit_generator.state
 
-    def world(make):
+    def fill(b):
         rng.bit_generator.state = state
-        b = make(77 + seed)
         b.camera_pinhole(v3(0, 1.0, 2.5), v3(0, 0.4, -2), v3(0, 1, 0), PI_D / 3, w / h)
         random_world(b, rng, n_objects, many)
-        return b
 
-    p = world(rtmi.SceneBuilder).commit()
+    ob, pb = parity.build_pair(fill, 77 + seed)
     want = None
     for kw in MODES:
-        R = rtmi.Renderer(p, h, w, spp, depth, post).init_rng()
-        R.render(opts=rtmi.render_opts(**kw))
-        R.check()
-        got = (R.tiles.cpu().numpy(), R.ray_counts.cpu().numpy(), R.states.cpu().numpy(), R.total_rays())
-        if want is None:
-            want = got
-        elif got[3] != want[3] or not all(np.array_equal(x, y, equal_nan=True) for x, y in zip(got[:3], want[:3])):
+        got = parity.gpu_frame(pb, h, w, spp, depth, post, kw)
+        want = want or got
+        if differs(got, want, "seed %d, %s" % (seed, kw)):
             bad += 1
             print("MISMATCH seed", seed, kw, flush=True)
     if oracle_every and seed % oracle_every == 0:
-        o = world(oraclelib.OracleBuilder)
-        o_rgb, o_rays, _, o_total = o.render(h, w, spp, depth, post=post)
-        R = rtmi.Renderer(p, h, w, spp, depth, post).init_rng()
-        R.render()
-        img, cnt = R.untile()
-        torch.cuda.synchronize()
-        if not (R.total_rays() == o_total and np.array_equal(cnt.cpu().numpy().astype(np.uint32), o_rays) and
-                np.array_equal(img.cpu().numpy(), o_rgb, equal_nan=True)):
+        if differs(parity.gpu_frame(pb, h, w, spp, depth, post), parity.oracle_frame(ob, h, w, spp, depth, post), "seed %d" % seed):
             bad += 1
             print("ORACLE MISMATCH seed", seed, flush=True)
 print("mode seeds %d..%d (%d modes each, oracle every %d): %d mismatches, %.1fs" % (first, first + count - 1, len(MODES), oracle_every, bad, time.time() - t0), flush=True)
