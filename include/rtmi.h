@@ -505,6 +505,55 @@ int rtmi_trace(const rtmi_scene *s, int64_t n, const float *d_origins, const flo
  * Asynchronous on `stream`; n == 0 launches nothing. */
 int rtmi_rng_init_n(uint64_t seed, uint64_t first, int64_t n, void *d_states, void *stream);
 
+/* ----------------------------------------------------------------- bounce --
+ * One iteration of Trace's loop as a call, for a wavefront of paths: between two steps the caller holds every path's
+ * vertex -- for a shadow ray to a light (rtmi_occluded), a termination rule of its own, per-bounce outputs.  max_depth
+ * calls of rtmi_bounce and one rtmi_path_fold compose bit for bit to rtmi_trace (below).  Added without a version change:
+ * a caller detects them by the symbol rtmi_bounce.
+ *
+ * rtmi_bounce.  Rays d_origins, d_dirs and outputs d_emitted, d_attenuation are float[n][3] (device), n <= 2^31 - 1;
+ * d_states is rtmi_trace's layout (RTMI_STATE_WORDS planes of uint32[n]); d_hits (nullable) rtmi_hit[n], 16-byte aligned;
+ * d_steps (nullable) uint32[n]; d_work is rtmi_trace's (RTMI_TRACE_WORK_WORDS words, reset on `stream`; afterwards [0]
+ * holds the abandoned mesh searches and [1] the paths this call stepped).
+ *   - A ray (o, d) means Ray(o, d) as in rtmi_intersect and rtmi_trace: the step normalises d once (ray.cu:8-10).
+ *   - A bad ray -- a non-finite origin or direction, or a direction that does not normalise, the zero direction among
+ *     them -- is SKIPPED: nothing of the path is written and its state is not read.  So a path that has ended (below) and
+ *     an inactive item of rtmi_camera_rays flow through further steps untouched.
+ *   - Any other path gets exactly what one iteration of Trace does below its depth test (ray_tracing.cu:22-47):
+ *     rec = world->Hit(Ray(o, d), 1e-3, INFINITY); d_hits[i] = the record exactly as rtmi_intersect reports it for (o, d)
+ *     with no t_max; d_steps[i] += 1.
+ *     Nothing hit: d_emitted[i], d_attenuation[i] and d_dirs[i] become three +0.0f each; origin and state are untouched.
+ *     A hit: d_emitted[i] = material->Emit(rec.u, rec.v, hit_point) (Sky's gradient counts; +0.0f for a material that
+ *     does not emit); Scatter runs with the path's state, which advances in place by exactly its draws, in the
+ *     reference's order.  Where it scatters, d_attenuation[i] = Scatter's attenuation, d_origins[i] = the scattered ray's
+ *     origin (the material's p) and d_dirs[i] = THE VECTOR SCATTER HANDS TO RAY'S CONSTRUCTOR: normalize(S + n), normalised
+ *     once, for Lambertian; reflected [+ fuzz * r] and the refracted vector as they are for Metal and Dielectric -- so the
+ *     next step's one normalisation reproduces Trace's ray exactly (the convention of rtmi_camera_rays' directions).
+ *     Where it does not scatter, d_attenuation[i] and d_dirs[i] become three +0.0f and the origin is untouched.
+ *   - The step knows no depth: the caller decides how many run.  Trace's last query, at depth == max_depth, only counts
+ *     and returns 0; so after max_depth steps of a good ray, rtmi_trace's ray count is d_steps[i] + (d_dirs[i] still
+ *     non-zero ? 1 : 0) and its final state is the path's state.  With max_depth == 0 no step is made.
+ *   - One difference from rtmi_trace: a scattered ray can itself be bad -- a Lambertian sample that is exactly the reversed
+ *     normal, a Metal fuzz vector that cancels the reflection to within the normalisation's underflow.  The next step
+ *     skips such a ray (the path counts as alive, with the steps it has); Trace would follow its NaN direction.
+ *
+ * rtmi_path_fold is Trace's return expression (ray_tracing.cu:50-52).  d_emitted and d_attenuation are stacks
+ * float[layers][n][3]: layer k is what step k wrote (the caller passes base + k * n * 3 to step k).  With
+ * c = min(d_steps[i], layers):  c == 0: radiance 0.  d_dirs[i] the zero vector (the path ended): r = E[c-1], then for
+ * k = c-2 .. 0: r = E[k] + A[k] * r.  Otherwise (the path is alive: Trace would cut it): r = 0, then for k = c-1 .. 0 the
+ * same.  Product and sum are each rounded to binary32 on their own, per channel (no fused multiply-add).  Layers >= c are
+ * never read, so the caller never clears the stacks.  The fold uses no scene and no d_work.
+ *
+ * Both are asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call for a null or uncommitted scene (rtmi_bounce),
+ * n < 0, n above 2^31 - 1, a null required array with n > 0 (d_hits and d_steps of rtmi_bounce are the optional ones),
+ * layers outside 1..RTMI_MAX_DEPTH; then also (rtmi_bounce) when the current device is not the one the scene was committed
+ * on.  n == 0 launches nothing. */
+int rtmi_bounce(const rtmi_scene *s, int64_t n, float *d_origins, float *d_dirs, void *d_states, float *d_emitted,
+                float *d_attenuation, rtmi_hit *d_hits /* nullable */, uint32_t *d_steps /* nullable */,
+                unsigned long long *d_work, void *stream);
+int rtmi_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                   const float *d_attenuation, float *d_radiance, void *stream);
+
 /* ------------------------------------------------------------ camera rays --
  * The render's primary rays as a call of their own, and the fold of a traced sample into the budget buffers.  For every
  * sample index `sample` = 0, 1, ... the three calls

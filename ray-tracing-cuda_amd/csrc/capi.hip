@@ -1243,6 +1243,34 @@ int rtmi_trace(const rtmi_scene *sp, int64_t n, const float *d_origins, const fl
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ one step of the trace loop
+int rtmi_bounce(const rtmi_scene *sp, int64_t n, float *d_origins, float *d_dirs, void *d_states, float *d_emitted,
+                float *d_attenuation, rtmi_hit *d_hits, uint32_t *d_steps, unsigned long long *d_work, void *stream) {
+  const Scene *s;
+  int n_cu;
+  const int no_depth = 0;  // (the step knows none; handed over for rtmi_trace's bound on n)
+  const int rc = batch_prologue(sp, n, d_origins && d_dirs && d_states && d_emitted && d_attenuation && d_work,
+                                "null ray, state, emitted, attenuation or work array", &no_depth, &s, &n_cu);
+  if (rc || n == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
+  HIP_TRY(launch_bounce(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_origins, d_dirs,
+                        reinterpret_cast<uint32_t *>(d_states), d_emitted, d_attenuation, reinterpret_cast<int32_t *>(d_hits),
+                        d_steps, d_work, st));
+  return RTMI_OK;
+}
+
+int rtmi_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                   const float *d_attenuation, float *d_radiance, void *stream) {
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
+  if (layers < 1 || layers > RTMI_MAX_DEPTH) return fail(RTMI_ERR_INVALID, "layers outside 1..RTMI_MAX_DEPTH");
+  if (n > 0 && !(d_dirs && d_steps && d_emitted && d_attenuation && d_radiance))
+    return fail(RTMI_ERR_INVALID, "null direction, step, emitted, attenuation or radiance array");
+  HIP_TRY(launch_path_fold(n, layers, d_dirs, d_steps, d_emitted, d_attenuation, d_radiance, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
 // ------------------------------------------------------------------ per-pixel sample budgets
 // What the three entries below check of their frame, in the other entries' order: the arguments first, without a HIP call.
 static int budget_frame(const rtmi_frame *f, bool arrays, const char *null_arrays, FrameDev *d) {

@@ -187,6 +187,15 @@ constexpr size_t kCallParamsOffset = 256;  // (a 128-byte line of its own, away 
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
+// One iteration of Trace's loop per ray (rtmi_bounce; kernels.hip: bounce_kernel), on the query variants: rays and states
+// are read and written in place; d_hits (n x 12 words, rtmi_hit) and d_steps nullable; d_work as launch_trace's, [1] = the
+// paths stepped.
+hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, float *d_o, float *d_d,
+                         uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
+                         unsigned long long *d_work, hipStream_t stream);
+// Trace's return expression over the first min(d_steps[i], layers) layers of the stacks float[layers][n][3] (rtmi_path_fold).
+hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                            const float *d_attenuation, float *d_radiance, hipStream_t stream);
 // Per-pixel sample budgets (rtmi_render_budget; kernels.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).

@@ -199,6 +199,14 @@ __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F & ~(uint32_t)
   render_body<F, false, true, true>(rp.sc, rp.fr, rp.lc, rp.states, rp.out, rp.ray_counts, rp.counters, nullptr, nullptr,
                                     ex.tex_layers != 0, ex.px.budget, ex.px.sq, ex.px.samples, &ex.feat);
 }
+// rtmi_bounce: the same body in its caller-ray mode, one iteration per item (STEP).
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void bounce_kernel(const CallParams *p) {
+  const RenderParams &rp = in_constant(p).rp;
+  const CallExtras &ex = in_constant(p).ex;
+  render_body<F, true, false, false, 0, true>(rp.sc, rp.fr, rp.lc, rp.states, nullptr, nullptr, rp.counters, nullptr, nullptr, false,
+                                              nullptr, nullptr, nullptr, nullptr, &ex.step);
+}
 
 // ------------------------------------------------------------------ untile / post
 template <typename E, int C>
@@ -954,13 +962,13 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
 template <uint32_t F, auto Kernel>
 static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_layers, int fetch_batch, int n_cu,
                               CallExtras ex, uint32_t *d_states, float *d_out, uint32_t *d_ray_counts,
-                              unsigned long long *d_work, hipStream_t stream) {
+                              unsigned long long *d_work, hipStream_t stream, bool id_stack = true) {
   // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
   // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
   int threads = 0, per_cu = 0;
   for (int t = 256; t >= 64; t /= 2) {
     size_t lds_t = 0;
-    (void)make_cfg(F, sc, fr, t, &lds_t, true, true, tex_layers);
+    (void)make_cfg(F, sc, fr, t, &lds_t, true, id_stack, tex_layers);
     int nb = 0;
     (void)kernel_occupancy<Kernel>(t, lds_t, &nb);
     if (t * nb > threads * per_cu) threads = t, per_cu = nb;
@@ -968,7 +976,7 @@ static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_l
   if (per_cu < 1) return hipErrorInvalidConfiguration;  // (the staged tables and the stack do not fit a CU's LDS)
   size_t lds = 0;
   CallParams cp;
-  cp.rp.sc = sc, cp.rp.fr = fr, cp.rp.lc = make_cfg(F, sc, fr, threads, &lds, true, true, tex_layers);
+  cp.rp.sc = sc, cp.rp.fr = fr, cp.rp.lc = make_cfg(F, sc, fr, threads, &lds, true, id_stack, tex_layers);
   cp.rp.lc.lane_stride = 1, cp.rp.lc.fetch_batch = fetch_batch, cp.rp.lc.rate_scale = 1.f;
   cp.rp.states = d_states, cp.rp.out = d_out, cp.rp.ray_counts = d_ray_counts, cp.rp.counters = d_work;
   cp.ex = ex, cp.ex.tex_layers = tex_layers ? 1 : 0;
@@ -991,6 +999,52 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
     // (64: the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
     return launch_call<F, trace_kernel<F>>(sc, fr, tex_layers, 64, n_cu, ex, d_states, d_radiance, d_ray_counts, d_work, stream);
   });
+}
+
+// One iteration of the trace loop per ray (rtmi_bounce; render_body.h: STEP): the item is a path, its depth is the
+// caller's business (fr.max_depth = 1 only opens the loop's depth test), and no layer is stacked -- no id stack in LDS.
+hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, float *d_o, float *d_d,
+                         uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
+                         unsigned long long *d_work, hipStream_t stream) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    FrameDev fr{};
+    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = 1, fr.post = 0;
+    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
+    fr.items = n;
+    CallExtras ex{};
+    ex.step = {d_o, d_d, d_emitted, d_attenuation, d_hits, d_steps, qd};
+    return launch_call<F, bounce_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false);
+  });
+}
+
+// Trace's return expression over the layers the steps wrote (rtmi_path_fold; include/rtmi.h states the rule): one lane
+// per path, so a layer's reads are coalesced over n; product and sum each rounded on their own.
+__global__ __launch_bounds__(256) void path_fold_kernel(int64_t n, uint32_t layers, const float *__restrict__ dirs,
+                                                         const uint32_t *__restrict__ steps, const float *__restrict__ emitted,
+                                                         const float *__restrict__ attenuation, float *__restrict__ radiance) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t s = steps[q];
+  int k = (int)(s < layers ? s : layers) - 1;
+  V3 r = splat(0.f);
+  if (k >= 0 && dirs[q * 3 + 0] == 0.f && dirs[q * 3 + 1] == 0.f && dirs[q * 3 + 2] == 0.f) {  // the path ended in layer k
+    const float *e = emitted + ((int64_t)k * n + q) * 3;
+    r = mk(e[0], e[1], e[2]);
+    k--;
+  }
+  for (; k >= 0; k--) {
+    const float *e = emitted + ((int64_t)k * n + q) * 3, *a = attenuation + ((int64_t)k * n + q) * 3;
+    r = mk(__fadd_rn(e[0], __fmul_rn(a[0], r.x)), __fadd_rn(e[1], __fmul_rn(a[1], r.y)), __fadd_rn(e[2], __fmul_rn(a[2], r.z)));
+  }
+  radiance[q * 3 + 0] = r.x, radiance[q * 3 + 1] = r.y, radiance[q * 3 + 2] = r.z;
+}
+hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                            const float *d_attenuation, float *d_radiance, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(path_fold_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, n, (uint32_t)layers, d_dirs, d_steps,
+                     d_emitted, d_attenuation, d_radiance);
+  return hipGetLastError();
 }
 
 // The budget mode runs on the query variants + F_DEFOCUS, its items in image order.  A pixel is a serial chain, so a call

@@ -7,8 +7,16 @@
 // rtmi_render_budget (budget_kernel): a work item is a pixel as in the render, but how many samples it gets is its own
 // word of a budget map, and the sums, second moments, sample and ray counts it finds in the buffers are carried on;
 // with FEATURES (rtmi_render_features, feature_kernel) it also sums what each sample's primary hit looks like.
+// STEP (with RAYS) is rtmi_bounce (bounce_kernel): ONE iteration of the loop per item -- the query, the winner's
+// resolution, Emit and Scatter, this same copy of them -- whose results are written out instead of stacked and folded:
+// no depth, no layer stack, no fold.
 // What each mode is told: RenderParams and CallExtras below.
 #pragma once
+
+// query_body.h (included after this file): the winner as an rtmi_hit record, which STEP writes as rtmi_intersect does.
+struct QueryHit;
+template <uint32_t F>
+__device__ __forceinline__ QueryHit resolve_hit(const SceneDev &sc, const QueryDev &qd, const Hit &h, V3 o, V3 d);
 
 // ================================================================== trace kernel
 // Dynamic LDS: [ material records: lds_mats * 32 B ][ id stack: max_depth * blockDim entries ]
@@ -159,6 +167,13 @@ struct BudgetBufs {
   float *sq;               // the second moments (nullable); accumulates
   uint32_t *samples;       // samples per item; accumulates
 };
+struct StepBufs {
+  float *origins, *dirs;         // float[items][3]: the rays, replaced by the scattered rays
+  float *emitted, *attenuation;  // float[items][3]
+  int32_t *hits;                 // nullable: items x 12 words (rtmi_hit)
+  uint32_t *steps;               // nullable: += 1 per stepped path
+  QueryDev qd;                   // the recording order's names of the winner (query_body.h: resolve_hit)
+};
 struct CallExtras {
   union {  // one work-item source at a time; either way right behind RenderParams' pointers, which they are loaded with
     RayBufs rays;   // RAYS
@@ -173,6 +188,8 @@ struct CallExtras {
   // in registers: the lane owns the item, so these are plain vector loads and stores, and nothing more is live across
   // closest_hit and the fold than in the budget mode.  No RNG draw is made or skipped.
   FeatureBufs feat;
+  // STEP (with RAYS, whose `rays` stays unset: the step reads its rays where it writes them)
+  StepBufs step;
 };
 struct CallParams {
   RenderParams rp;
@@ -194,7 +211,7 @@ __device__ __forceinline__ const P &in_constant(const P *p) {
 // (NOTES.md 11).
 // M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
 // the front end folds: with M == 0 every line below is the run-time test it was.
-template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0>
+template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0, bool STEP = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -203,8 +220,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const float *__restrict__ ray_d = nullptr, bool tex_layers = true,
                                             const uint32_t *__restrict__ budget = nullptr,
                                             float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr,
-                                            const FeatureBufs *feat = nullptr) {
+                                            const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
+  static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
   static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
   static_assert(M == 0 || (F == F_TRIS && !RAYS && !BUDGET), "the pins are the list-triangle render's");
   static_assert(!((M & PIN_CHAINS) && (M & PIN_QUEUE)), "a wave gets its work one way");
@@ -354,15 +372,23 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     q32 = (int32_t)item;
     const int64_t q = item;
     if constexpr (RAYS) {  // the caller's ray q, left out as rtmi_intersect leaves it out (query_body.h)
-      const V3 ro = mk(ray_o[q * 3 + 0], ray_o[q * 3 + 1], ray_o[q * 3 + 2]);
-      const V3 rd = mk(ray_d[q * 3 + 0], ray_d[q * 3 + 1], ray_d[q * 3 + 2]);
+      V3 ro, rd;
+      if constexpr (STEP) {
+        ro = mk(step->origins[q * 3 + 0], step->origins[q * 3 + 1], step->origins[q * 3 + 2]);
+        rd = mk(step->dirs[q * 3 + 0], step->dirs[q * 3 + 1], step->dirs[q * 3 + 2]);
+      } else {
+        ro = mk(ray_o[q * 3 + 0], ray_o[q * 3 + 1], ray_o[q * 3 + 2]);
+        rd = mk(ray_d[q * 3 + 0], ray_d[q * 3 + 1], ray_d[q * 3 + 2]);
+      }
       bool live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
       V3 nd = splat(0.f);
       if (live) nd = unit3_rn(rd);  // Ray's constructor (ray.cu:8-10)
       live = live && finite3(nd) && (nd.x != 0.f || nd.y != 0.f || nd.z != 0.f);
-      if (!live) {  // radiance 0, count 0, state untouched
-        out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
-        if (ray_counts) ray_counts[q] = 0;
+      if (!live) {  // radiance 0, count 0, state untouched (STEP: nothing of the item is written)
+        if constexpr (!STEP) {
+          out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
+          if (ray_counts) ray_counts[q] = 0;
+        }
         return false;
       }
       o = ro, d = nd;  // (the lane holds no path while it takes an item: o, d carry the ray to the path's start)
@@ -448,7 +474,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       wave_priority_update(lc.prio_tab, (uint32_t)fminf(left, 4.0e9f));
     }
     // -------------------------------------------------------- sample / pixel bookkeeping
-    if (!active && !done && has_px && k >= k_end()) {
+    if (!STEP && !active && !done && has_px && k >= k_end()) {  // (STEP: an item is written where it is shaded)
       const int64_t q = (int64_t)q32;
       V3 c = color;
       if (!BUDGET && fr.post && fr.k_end >= fr.spp) {  // ray_tracing.cu:78-83 (a first pass leaves the raw sum)
@@ -752,6 +778,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
 
       V3 result = splat(0.f);
       bool ended = true;
+      V3 step_att = splat(0.f), step_o = o, step_d = splat(0.f);  // (STEP) Scatter's attenuation and the vector it hands to Ray
       if (h.ok && depth < fr.max_depth) {  // ray_tracing.cu:23
         const uint32_t kind = h.win >> 29;
         const uint32_t index = h.win & ID_INDEX_MASK;
@@ -867,7 +894,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 V3 s = ball_sample(rng, sum);
                 s = sampler_on_sphere(s, sum);  // l = (float)pow((double)sum, 0.5); vec /= l (lambertian.cu:25-29)
                 // normalize(S + n), then Ray's constructor (lambertian.cu:41-42) (DEFER: at the top of the loop)
-                nd = DEFER ? s + nrm : unit3_rn_twice(s + nrm);
+                // (STEP: normalize(S + n) alone -- the next step's Ray normalises again)
+                nd = STEP ? unit3_rn(s + nrm) : DEFER ? s + nrm : unit3_rn_twice(s + nrm);
                 scattered = true;
               }
             } else if (m.kind == MAT_METAL) {  // metal.cu:12-25
@@ -880,7 +908,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 } else {
                   nd = refl;
                 }
-                nd = unit3_rn(nd);  // Ray's constructor
+                if (!STEP) nd = unit3_rn(nd);  // Ray's constructor (STEP: the next step's)
                 scattered = true;
               }
             } else {  // MAT_DIELECTRIC, dielectric.cu:16-44
@@ -891,9 +919,16 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               bool zero = (nd.x == 0.f && nd.y == 0.f && nd.z == 0.f);
               bool nan = (nd.x != nd.x) || (nd.y != nd.y) || (nd.z != nd.z);
               scattered = !(zero || nan);
-              if (scattered) nd = unit3_rn(nd);  // Ray's constructor
+              if (!STEP && scattered) nd = unit3_rn(nd);  // Ray's constructor (STEP: the next step's)
             }
-            if (scattered) {
+            if constexpr (STEP) {  // the layer itself instead of its place on the stack: what the fold would read of it
+              if (scattered) {
+                step_att = ((F & F_TEX) && (layer >> 31)) ? texel_rgb(layer) : rgb;
+                step_o = p, step_d = nd;
+                ended = false;
+              }
+            }
+            if (!STEP && scattered) {
               if (tex32) {
                 *reinterpret_cast<uint32_t *>(smem + tex_layer_offset(depth)) = layer;
               } else if (nibble_ids) {
@@ -916,6 +951,36 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       }
       RTMI_STAT2(if (!(F & F_BVH)) { const unsigned long long tsb = stat_now();
         if ((int)(threadIdx.x & 63u) == __builtin_ctzll(__ballot(1))) g_wave_stats[((blockIdx.x * blockDim.x + threadIdx.x) >> 6) & 16383u][10] += tsb - tq2; })
+      if constexpr (STEP) {
+        // One iteration of Trace is done: everything of it goes to the caller (include/rtmi.h: rtmi_bounce), the record
+        // as rtmi_intersect reports it for the ray that came in (o, d still hold it).
+        const int64_t q = (int64_t)q32;
+        float *em = step->emitted + q * 3, *at = step->attenuation + q * 3, *dr = step->dirs + q * 3;
+        em[0] = result.x, em[1] = result.y, em[2] = result.z;
+        at[0] = step_att.x, at[1] = step_att.y, at[2] = step_att.z;
+        dr[0] = step_d.x, dr[1] = step_d.y, dr[2] = step_d.z;  // (three +0.0f where the path ended)
+        if (!ended) {  // only a path that scatters has a new origin -- and only Scatter draws
+          float *on = step->origins + q * 3;
+          on[0] = step_o.x, on[1] = step_o.y, on[2] = step_o.z;
+          states[0 * n_items + q] = rng.d;
+          states[1 * n_items + q] = rng.v0;
+          states[2 * n_items + q] = rng.v1;
+          states[3 * n_items + q] = rng.v2;
+          states[4 * n_items + q] = rng.v3;
+          states[5 * n_items + q] = rng.v4;
+        }
+        if (step->hits) {
+          const auto r = resolve_hit<F>(sc, step->qd, h, o, d);
+          int4 *rec = reinterpret_cast<int4 *>(step->hits + q * 12);
+          rec[0] = make_int4(__float_as_int(r.t), __float_as_int(r.u), __float_as_int(r.v), __float_as_int(r.n.x));
+          rec[1] = make_int4(__float_as_int(r.n.y), __float_as_int(r.n.z), r.mat, r.kind);
+          rec[2] = make_int4(r.entry, r.element, 0, 0);
+        }
+        if (step->steps) step->steps[q] += 1u;
+        ray_acc += 1u;  // (a lane steps fewer than 2^31 paths: n is below that)
+        active = false, has_px = false;
+        ended = false;  // (nothing to fold)
+      }
       if (ended) {
         // ray_tracing.cu:50-52 with emitted == 0 on every stored layer: result = emitted +
         // attenuation * result, deepest layer first.  The addition only matters for a product of -0,

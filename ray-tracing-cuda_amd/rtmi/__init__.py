@@ -234,6 +234,9 @@ SYMBOLS = [
                                    C.c_void_p, C.c_void_p]),
     ("rtmi_sample_add", C.c_int, [_frp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    ("rtmi_bounce", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_path_fold", C.c_int, [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -367,6 +370,75 @@ class Trace:
 
     def total_rays(self):
         return int(self.work[1].item())
+
+
+class Bounce:
+    """What ``SceneBuilder.bounce`` returns: ``emitted`` and ``attenuation`` (N, 3) float32; ``hits`` the step's ``Hits``
+    (views into an (N, 12) int32 buffer, ``hits.raw``) or None when they were not asked for; ``steps`` (N,) int32, each
+    path's step count so far, or None; ``work`` the call's (RTMI_TRACE_WORK_WORDS,) int64 device words; ``origins``,
+    ``directions`` and ``states``: the caller's tensors, which now hold the scattered rays.  ``check()`` waits for the call
+    and raises when it abandoned a mesh search (the answers are then not to be used); ``stepped()`` is how many paths
+    the call stepped."""
+
+    def __init__(self, origins, directions, states, emitted, attenuation, hits, steps, work):
+        self.origins, self.directions, self.states = origins, directions, states
+        self.emitted, self.attenuation, self.hits, self.steps, self.work = emitted, attenuation, hits, steps, work
+
+    def check(self):
+        n = int(self.work[0].item())  # (a device-to-host copy: waits for the call)
+        if n:
+            raise RtmiError("rtmi_bounce abandoned %d mesh search(es): the answers are incomplete" % n)
+        return self
+
+    def stepped(self):
+        return int(self.work[1].item())
+
+
+class Steps(collections.namedtuple("Steps", "rgb steps alive origins directions emitted attenuation works")):
+    """What ``SceneBuilder.trace_steps`` returns: ``rgb`` (N, 3) float32, the folded radiance; ``steps`` (N,) int32, the
+    steps each path made; ``alive`` (N,) bool, the paths whose direction is still non-zero (``steps + alive`` is
+    rtmi_trace's ray count); ``origins`` / ``directions``: the loop's own copies of the rays as the last step left them;
+    ``emitted`` / ``attenuation``: the (max(max_depth, 1), N, 3) float32 layer stacks; ``works``: every step's work words.
+    ``check()`` waits for the loop and raises when a step abandoned a mesh search."""
+
+    def check(self):
+        for k, w in enumerate(self.works):
+            n = int(w[0].item())
+            if n:
+                raise RtmiError("rtmi_bounce abandoned %d mesh search(es) in step %d: the answers are incomplete" % (n, k))
+        return self
+
+
+def path_fold(directions, steps, emitted_stack, attenuation_stack, out=None):
+    """Trace's return expression over the layers the steps wrote (rtmi_path_fold), enqueued on torch's current stream.
+
+    ``directions`` (N, 3) float32: the paths' directions after the last step (a zero vector: the path ended); ``steps``
+    (N,) int32; ``emitted_stack`` / ``attenuation_stack``: contiguous (layers, N, 3) float32, layer k what step k wrote,
+    1 <= layers <= 64.  All CUDA tensors on one device.  ``out``: an optional (N, 3) float32 tensor to write into.  Returns
+    the radiance."""
+    try:
+        import torch
+    except ImportError:
+        raise RtmiError("directions: torch is needed for rtmi_path_fold")
+    if not (isinstance(directions, torch.Tensor) and directions.is_cuda and directions.dtype == torch.float32 and
+            directions.dim() == 2 and directions.shape[1] == 3 and directions.is_contiguous()):
+        raise RtmiError("directions must be a contiguous CUDA float32 tensor of shape (N, 3): rtmi_path_fold has no CPU path")
+    n, dev = int(directions.shape[0]), directions.device
+    if not _is_buffer(steps, (n,), dev, torch.int32):
+        raise RtmiError("steps must be a contiguous CUDA int32 tensor of shape (N,) on the directions' device")
+    if not (isinstance(emitted_stack, torch.Tensor) and emitted_stack.dim() == 3 and 1 <= emitted_stack.shape[0] <= MAX_DEPTH):
+        raise RtmiError("emitted_stack must have shape (layers, N, 3) with 1 <= layers <= %d" % MAX_DEPTH)
+    layers = int(emitted_stack.shape[0])
+    for name, t in (("emitted_stack", emitted_stack), ("attenuation_stack", attenuation_stack)):
+        if not _is_buffer(t, (layers, n, 3), dev, torch.float32):
+            raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape (layers, N, 3) on the directions' device" % name)
+    out = _out_buffer(out, "float32 tensor of shape (N, 3)", (n, 3), dev, torch.float32)
+    with torch.cuda.device(dev):
+        _check(lib().rtmi_path_fold(n, layers, C.c_void_p(directions.data_ptr()), C.c_void_p(steps.data_ptr()),
+                                    C.c_void_p(emitted_stack.data_ptr()), C.c_void_p(attenuation_stack.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+               "rtmi_path_fold")
+    return out
 
 
 class Adaptive(collections.namedtuple("Adaptive", "tiles samples passes total_samples features", defaults=(None,))):
@@ -806,6 +878,82 @@ class SceneBuilder:
                                      C.c_void_p(rays.data_ptr()) if rays is not None else None,
                                      C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
         return Trace(out, rays, work, (origins, directions, states))
+
+    def bounce(self, origins, directions, states, emitted=None, attenuation=None, hits=False, steps=None):
+        """One iteration of Trace's loop for each path (rtmi_bounce), enqueued on torch's current stream.
+
+        ``origins`` / ``directions``: contiguous CUDA float32 (N, 3) tensors on the scene's device, REPLACED in place by
+        the scattered rays (a zero direction: the path has ended, and further steps leave it alone); ``states``: a
+        contiguous (6, N) int32 CUDA tensor of RNG states, advanced in place by Scatter's draws.  ``emitted`` /
+        ``attenuation``: optional (N, 3) float32 tensors to write into (a layer of the stacks ``path_fold`` reads);
+        ``hits``: True for the step's hit records, or an (N, 12) int32 tensor to write them into; ``steps``: an optional
+        (N,) int32 tensor whose entry is incremented for every path this call steps.  Returns ``Bounce``; call
+        ``.check()`` on it before trusting the answers of a mesh scene."""
+        import torch
+        n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
+        if not (origins.is_contiguous() and directions.is_contiguous()):
+            raise RtmiError("origins and directions must be contiguous: rtmi_bounce writes the scattered rays into them")
+        if not _is_buffer(states, (STATE_WORDS, n), dev, torch.int32):
+            raise RtmiError("states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
+        for name, t in (("emitted", emitted), ("attenuation", attenuation)):
+            if t is not None and not _is_buffer(t, (n, 3), dev, torch.float32):
+                raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape (N, 3) on the rays' device" % name)
+        if steps is not None and not _is_buffer(steps, (n,), dev, torch.int32):
+            raise RtmiError("steps must be a contiguous CUDA int32 tensor of shape (N,) on the rays' device")
+        raw = None
+        if isinstance(hits, torch.Tensor):
+            raw = _out_buffer(hits, "int32 tensor of shape (N, 12)", (n, HIT_WORDS), dev, torch.int32)
+        elif hits:
+            raw = torch.empty((n, HIT_WORDS), dtype=torch.int32, device=dev)
+        stream = self._stream(dev)
+        if emitted is None:
+            emitted = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if attenuation is None:
+            attenuation = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        work = torch.zeros((TRACE_WORK_WORDS,), dtype=torch.int64, device=dev)  # (n == 0 leaves it untouched)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_bounce(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                      C.c_void_p(states.data_ptr()), C.c_void_p(emitted.data_ptr()),
+                                      C.c_void_p(attenuation.data_ptr()),
+                                      C.c_void_p(raw.data_ptr()) if raw is not None else None,
+                                      C.c_void_p(steps.data_ptr()) if steps is not None else None,
+                                      C.c_void_p(work.data_ptr()), stream), "rtmi_bounce")
+        rec = None
+        if raw is not None:
+            f = raw.view(torch.float32)
+            rec = Hits(f[:, 0], f[:, 1:3], f[:, 3:6], raw[:, 6], raw[:, 7], raw[:, 8], raw[:, 9])
+            rec.raw = raw
+        return Bounce(origins, directions, states, emitted, attenuation, rec, steps, work)
+
+    def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None):
+        """rtmi_trace as a loop of ``max_depth`` steps and one fold, on copies of the rays: bit for bit ``trace``'s
+        radiance while ``each`` changes nothing.  ``states`` advance in place, as in ``trace``.  ``each(step, result)``
+        is called after every step is enqueued, with the step's ``Bounce`` (``result.origins`` / ``.directions`` are the
+        loop's own ray tensors): the place for shadow rays from ``result.hits``, or a termination rule -- zeroing a path's
+        direction ends it, and the fold then takes its last layer's emitted as the path's end.  ``hits``: whether the
+        steps record hits (default: when ``each`` is given).  Returns ``Steps``."""
+        import torch
+        n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
+        max_depth = int(max_depth)
+        if not 0 <= max_depth <= MAX_DEPTH:
+            raise RtmiError("max_depth %d outside [0, %d]" % (max_depth, MAX_DEPTH))
+        if not _is_buffer(states, (STATE_WORDS, n), dev, torch.int32):
+            raise RtmiError("states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
+        self._stream(dev)
+        o, d = origins.clone().contiguous(), directions.clone().contiguous()
+        layers = max(max_depth, 1)
+        E = torch.empty((layers, n, 3), dtype=torch.float32, device=dev)
+        A = torch.empty((layers, n, 3), dtype=torch.float32, device=dev)
+        steps = torch.zeros((n,), dtype=torch.int32, device=dev)
+        want_hits = (each is not None) if hits is None else bool(hits)
+        works = []
+        for k in range(max_depth):
+            r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
+            works.append(r.work)
+            if each is not None:
+                each(k, r)
+        rgb = path_fold(d, steps, E, A)
+        return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works)
 
     def _stream(self, dev):
         """torch's current stream on dev, the rays' device; raises unless the scene was committed there."""
