@@ -218,7 +218,9 @@ int rtmi_last_ray_total(const rtmi_scene *s, uint64_t *out_rays, void *stream);
 /* Diagnostic: the raw device counter words of a render ([0] work-queue head, [1] closest-hit queries,
  * [2] abandoned mesh searches, [3] head-queue cursor; a -DRTMI_STATS build of the kernels adds wave-level
  * step counts of the mesh search from word 4 on; a -DRTMI_CHECK_MARGINS build counts, in [33] / [34], the
- * sampled queries it re-did without the cull and the disagreements it found).  [2], [33] and [34] count over
+ * sampled queries it re-did without the cull and the disagreements it found; [16], in every build, counts the
+ * pair tasks of the fast list kernels' culled scan both of whose triangles passed with the second one nearer: the
+ * flushes that held one were folded in list order, every other by one minimum per ray).  [2], [33] and [34] count over
  * both launches of a resumed frame (a first pass the frame keeps, then the rest); the other words are the last
  * launch's, whose [1] is still the whole frame's total because a resumed pixel carries its count on. */
 #define RTMI_COUNTER_WORDS 40

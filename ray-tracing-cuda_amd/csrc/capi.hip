@@ -1100,6 +1100,9 @@ static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uin
   //   [2]       abandoned mesh searches (rtmi_render_status)        kept after a first pass the frame keeps
   //   [3]       head-queue cursor                                   zeroed (per launch)
   //   [4..32]   -DRTMI_STATS wave step counts and cycles            zeroed (per launch)
+  //   [16]      of them, in every build: tasks of the culled scan    zeroed (per launch)
+  //             that sent their flush through the ordered fold
+  //             ([12..15]: a list kernel's stats build counts the ordered fold's trips per flush there)
   //   [33] [34] -DRTMI_CHECK_MARGINS queries re-done, disagreements kept after a first pass the frame keeps
   //   [35] [36] planned chains: SIMD arrival, take-over cursor      zeroed (per launch)
   //   [37..39]  -DRTMI_STATS flushes of the culled scan by n_now    zeroed (per launch)

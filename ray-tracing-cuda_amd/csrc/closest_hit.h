@@ -135,6 +135,8 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   // the culled list scan is on when the wave has its task region (ll) and the scene has pair records; the triangles'
   // records come from LDS when the list was short enough to be staged (s_tris), else from sc.tris in global memory
   constexpr bool SLAB = culls_by_slab(M);  // (kernels.h) the pair test in centre / half-extent form
+  constexpr bool MINF = folds_by_min(M);   // (kernels.h) a flush of shared tests folds by one LDS minimum per ray
+  static_assert(!MINF || (!OCC && !DT && !(F & F_TEX)), "a key holds a binary32 t and the triangle's place, nothing else");
   const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
   if ((F & F_TRIS) && cull_list) {
@@ -316,11 +318,68 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             const bool now = todo && base + cnt - lo_t <= kListTasks(F);
             const int n_now = __builtin_amdgcn_readlane(base + cnt, 63 - __builtin_clzll(__builtin_amdgcn_ballot_w64(now))) - lo_t;
             RTMI_STAT(st.nnow_hist[(n_now - 1) >> 5 < 5 ? (n_now - 1) >> 5 : 5]++;)
+            RTMI_STAT({  // trips of (c)'s loop: the most candidates any lane of this flush folds
+              int pc = now ? cnt : 0;
+              for (int off = 32; off > 0; off >>= 1) pc = max(pc, __shfl_xor(pc, off));
+              st.trip_hist[pc < 8 ? pc - 1 : 7]++;
+            })
+            // (MINF) the lane id of steps (b) and (c), opaque to the compiler: what derives from it (the key's address, the
+            // lane's triangle of a task) is formed here, per flush, and holds no register across the trace loop
+            int ln = lane;
+            if (MINF) asm volatile("" : "+v"(ln));
             if (now) {  // (a)
               int k = base - lo_t;
               for (uint32_t m = mask; m != 0u; m &= m - 1u) tasks[k++] = (lane << 5) | __builtin_ctz(m);
+              if (MINF) results[2 * ln + 1] = -1;  // my key's t: nothing posted yet (any posted key is below it, whatever its low word)
             }
             wave_lds_fence();
+            // (MINF) the flush without its order: (b) posts one key per accepted pair, (c) reads the ray's smallest.  A
+            // task both of whose triangles pass, the second nearer, is the one case whose answer depends on the running
+            // bound at its turn: it posts nothing and sends the whole flush through the ordered steps
+            // below, which read the same tasks and ray records and overwrite the keys with their result words.
+            if (MINF) {
+              bool flagged = false;
+              for (int t0 = 0; t0 < 2 * n_now; t0 += 64) {  // (b)
+                const int ti = t0 + ln;
+                if (ti < 2 * n_now) {  // (2 n_now is even: the two lanes of a task are both here or both not)
+                  const int w = tasks[ti >> 1], which = ti & 1;
+                  const int *orr = ll + (w >> 5) * 8;
+                  const float4 r0 = *reinterpret_cast<const float4 *>(orr), r1 = *reinterpret_cast<const float4 *>(orr + 4);
+                  const V3 ro = mk(r0.x, r0.y, r0.z), rd = mk(r1.x, r1.y, r1.z);
+                  V3 p0, e1, e2;
+                  const bool present = load_tri_pts<M>(sc, s_tris, 2 * (pair0 + c0 + (w & 31)) + which, which, p0, e1, e2);
+                  float tt = 0.f, uu, vv;
+                  bool hit = false;
+                  if (present) hit = tri_test_flat<T>(p0, e1, e2, cross3(rd, e2), ro, rd, (T)r0.w, tt, uu, vv, det_safe);
+                  const int mine = hit ? __float_as_int(tt) : -1;  // (no accepted t has this pattern: it is a NaN's)
+                  const int other = __builtin_amdgcn_update_dpp(mine, mine, 0xb1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
+                  // the other triangle of my pair passed too, and it is the first (it goes before me) or the nearer second
+                  const bool yield = other != -1 && (which != 0 || __int_as_float(other) < tt);
+                  flagged = flagged || (hit && yield && which == 0);
+                  if (hit && !yield) {
+                    const unsigned long long key = ((unsigned long long)(uint32_t)mine << 32) | (uint32_t)(2 * (w & 31) + which);
+                    (void)__hip_atomic_fetch_min(reinterpret_cast<unsigned long long *>(results + 2 * (w >> 5)), key,
+                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                  }
+                }
+              }
+              wave_lds_fence();
+              const unsigned long long fl = __builtin_amdgcn_ballot_w64(flagged);
+              if (fl == 0ull) {
+                if (now) {  // (c)
+                  const int2 key = *reinterpret_cast<const int2 *>(results + 2 * ln);  // .x: place in the chunk, .y: t
+                  const float t = __int_as_float(key.y);
+                  const bool acc = key.y != -1 && (!ok || (T)t < t_to);  // (t <= t_to by its test: t_to is the record's still)
+                  ok = ok || acc;
+                  t_to = acc ? (T)t : t_to;
+                  win = acc ? make_id(RUN_TRIS, run.first + 2 * c0 + key.x) : win;
+                  todo = false;
+                }
+                wave_lds_fence();
+                continue;
+              }
+              if (lane == 0) atomicAdd(overflow + (kOrderedTasksWord - 2), (unsigned long long)__popcll(fl));  // (rtmi_debug_counters)
+            }
             for (int t0 = 0; t0 < 2 * n_now; t0 += 64) {  // (b)
               const int ti = t0 + lane;  // triangle `which` of pair task ti >> 1
               if (ti < 2 * n_now) {

@@ -81,6 +81,16 @@ constexpr bool defers_unit(uint32_t m) { return (m & kFastCommon) == kFastCommon
 // launch's camera (fast_path_facts: pairs_in_lds).  Every other kernel keeps PairBox and the per-ray slack, and
 // compiles to what it was.
 constexpr bool culls_by_slab(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+// The same kernels fold a flush of the culled scan's shared tests without its order: the lanes that test post one
+// 64-bit key per accepted pair, (bits of t) << 32 | place in the chunk, with an LDS minimum on the ray's slot, and the
+// ray's lane reads one key where it looped over result words (closest_hit.h, steps (b) and (c); DESIGN.md 2.1 says why
+// the smallest key is the sequential answer, and which task is not: that flush is redone in list order).  They are
+// binary32, untextured and never the occlusion engine, which is what a key of t and place alone takes for granted.
+// Every other kernel keeps the result words and the fold, and compiles to what it was.
+constexpr bool folds_by_min(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+// The tasks that sent their flush through the ordered steps are counted in counters[kOrderedTasksWord], a word only
+// -DRTMI_STATS builds of mesh kernels used (rtmi_debug_counters).  closest_hit sees the words from [2] on.
+constexpr int kOrderedTasksWord = 16;
 // Everything the fast kernels take for granted, as the call's plan knows it (capi.hip: plan_render).  One predicate for
 // the plan, which the launch and rtmi_render_mode both read, and for the tests (rtmi_fast_path_kernel).
 struct FastPathFacts {

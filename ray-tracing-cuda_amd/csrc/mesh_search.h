@@ -144,6 +144,7 @@ struct MeshStats {
   // [8] face steps incl. inserts
   unsigned long long cull_bits, cull_rays, cull_iters;  // culled list scan: candidate pairs, rays, wave iterations
   unsigned nnow_hist[6];  // ... and its flushes by pair tasks in flight (n_now): 1-32, 33-64, ..., 161-192
+  unsigned trip_hist[8];  // ... and by the most candidates one lane folds in (c): 1, 2, ..., 7, 8 or more
   unsigned long long calib;  // two stamps back to back, once per search: what a stamp costs
   unsigned long long cyc[11];  // [9] search setup before the first step, [10] between steps (loop control)
 };

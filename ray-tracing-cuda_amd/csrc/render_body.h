@@ -1097,6 +1097,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     // (two buckets per word, low half first: a diagnostic frame stays far below 2^32 flushes)
     for (int i = 0; i < 3; i++)
       atomicAdd(&counters[37 + i], (unsigned long long)st.nnow_hist[2 * i] | ((unsigned long long)st.nnow_hist[2 * i + 1] << 32));
+    // (the same packing, in the words of the mesh search's step histogram from its second bucket on: a list kernel has none)
+    for (int i = 0; i < 4 && !(F & F_BVH); i++)
+      atomicAdd(&counters[12 + i], (unsigned long long)st.trip_hist[2 * i] | ((unsigned long long)st.trip_hist[2 * i + 1] << 32));
     const unsigned wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (!(F & F_BVH) && wid < 16384u) {
       atomicAdd(&counters[25], g_wave_stats[wid][9]);

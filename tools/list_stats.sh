@@ -1,5 +1,6 @@
 #!/bin/bash
-# Diagnostic (GPU box, stats build): how many pairs survive the cull of the world-list scan on C2-like frames.
+# Diagnostic (GPU box, stats build): how many pairs survive the cull of the world-list scan on C2-like frames, how full
+# the flushes of its shared tests run, how many trips a fold in list order takes per flush and how many tasks asked for one.
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 # RTMI_TOOL_BPC / RTMI_TOOL_THREADS: workgroups per CU / lanes per workgroup (1 / 64 = every wave alone on its CU);
 # RTMI_TOOL_SIZE: frame side; RTMI_TOOL_LEVEL: stats build (1 sections, 2 + the culled scan's parts)
@@ -30,5 +31,11 @@ nf = max(sum(hist), 1)
 print("flushes by pair tasks in flight (n_now), buckets of 32: %s = %s" % (hist, ["%.3f" % (h / nf) for h in hist]))
 print("  per flush: pair rounds (ceil(n/64)) %.3f, triangle rounds (ceil(2n/64)) %.3f; flushes per wave_query %.3f" % (
     sum((i // 2 + 1) * h for i, h in enumerate(hist)) / nf, sum((i + 1) * h for i, h in enumerate(hist)) / nf, sum(hist) / max(wq, 1)))
+# step (c)'s trips per flush where it folds in list order: the most candidates any one lane of the flush hands over
+trips = [(out[12 + i // 2] >> (32 * (i % 2))) & 0xffffffff for i in range(8)]
+nt = max(sum(trips), 1)
+print("flushes by the most tasks of one lane (1, 2, ..., 7, 8 or more): %s = %s" % (trips, ["%.3f" % (t / nt) for t in trips]))
+print("  mean %.2f trips per flush (8 or more counted as 8); tasks that sent their flush through the ordered fold: %d" % (
+    sum((i + 1) * t for i, t in enumerate(trips)) / nt, out[16]))
 print("rays %d wave_queries %d: candidate pairs per ray %.2f (of %d lane-chunks), wave iterations per query %.2f" % (rays, wq, bits / max(crays, 1), crays, iters / max(wq, 1)))
 PY
