@@ -33,6 +33,7 @@ from abi_host import CHECK_LIB, ROOT
 from budgetlib import ADAPTIVE, H, W, OracleReplay, Shards, assert_same_results, plan_rule, random_budget, resolve_rule
 from parity import same
 from querylib import glm_normalize
+from texlib import image_value
 
 pytestmark = pytest.mark.gpu
 
@@ -170,17 +171,6 @@ class Recorder:
         m = self._b.diffuse_light(tex)
         self.mats[m] = ("light", tex)
         return m
-
-
-def image_value(rgba, u, v):
-    """ImageTexture::Value (image_texture.cu:9-38 as oracle.cc restates it): u, v binary64 from the record."""
-    h, w = rgba.shape[0], rgba.shape[1]
-    v = 1.0 - float(v)
-    fu, fv = F32(u), F32(v)
-    fu, fv = F32(fu - np.floor(fu)), F32(fv - np.floor(fv))
-    ix, iy = int(np.floor(F32(fu * F32(w)))), int(np.floor(F32(fv * F32(h))))
-    ix, iy = max(0, min(ix, w - 1)), max(0, min(iy, h - 1))
-    return rgba[iy, ix, :3].astype(F32) / F32(255.0)
 
 
 _SCALES = (F32(1) + np.arange(8192, dtype=F32) / F32(8192)).astype(F32)
