@@ -556,6 +556,52 @@ int rtmi_bounce(const rtmi_scene *s, int64_t n, float *d_origins, float *d_dirs,
 int rtmi_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                    const float *d_attenuation, float *d_radiance, void *stream);
 
+/* ------------------------------------------------------------ live paths --
+ * Steps over the live paths only.  rtmi_bounce looks at all n paths in every step, although most of a wavefront has ended
+ * after a few; rtmi_path_compact makes the list of the paths the next step would step, and rtmi_bounce_list steps the
+ * paths of a list, handed to the waves by index.  The list's length stays on the device: nothing here synchronises with
+ * the host.  Added without a version change: a caller detects them by the symbol rtmi_bounce_list.
+ *
+ * A LIST is uint32 path indices d_list with room for n_list of them (the host's bound, n_list <= 2^31 - 1) and a device
+ * word d_count; its CANDIDATES are the entries j in [0, min(n_list, d_count ? *d_count : n_list)).  A null d_list is the
+ * identity -- candidate j is path j -- and then n_list <= n.  A candidate >= n is no path and is dropped (skipped).
+ *
+ * rtmi_path_compact.  A path is LIVE exactly when the next step would step it: its ray is not one of rtmi_bounce's bad
+ * rays -- finite origin and direction, and a direction that normalises to a finite non-zero vector.  So a path that has
+ * ended (a zero direction, -0.0f included), a bad scattered ray (rtmi_bounce's documented difference) and an inactive
+ * item of rtmi_camera_rays are not live.
+ *   - d_list_out[0 .. c) = the live candidates' path indices IN THE ORDER OF THE CANDIDATES (ascending for a null or an
+ *     ascending input; the same list run to run), *d_count_out = c; entries from c on are not written.  d_list_out has
+ *     room for n_list entries.  The rays (float[n][3]) are only read.
+ *   - d_scratch: rtmi_path_compact_scratch_bytes(n_list) bytes (device, 4-byte aligned): one word per
+ *     RTMI_PATH_COMPACT_ITEMS entries.  Three small launches on `stream` -- counts per workgroup, their scan, the
+ *     scatter -- in which no workgroup waits for another.
+ *   - d_list_out must not be d_list_in and d_count_out must not be d_count_in: the caller ping-pongs two lists.
+ *   - n_list == 0 writes *d_count_out = 0 and nothing else.  The call needs no scene.
+ * RTMI_ERR_INVALID before any HIP call for n or n_list negative or above 2^31 - 1, a null d_list_in with n_list > n, a
+ * null d_origins, d_dirs, d_list_out, d_count_out or d_scratch with n_list > 0, and either aliasing above.
+ *
+ * rtmi_bounce_list.  rtmi_bounce for the candidates of (d_list, n_list, d_count) only.  EVERY array is indexed by path
+ * and has rtmi_bounce's shape with n paths -- the RNG planes keep stride n, a layer of rtmi_path_fold's stacks stays
+ * float[n][3] -- so rtmi_path_fold is used unchanged and nothing is gathered or scattered.
+ *   - A listed path gets exactly what rtmi_bounce gives it (rays, state, emitted, attenuation, hit record,
+ *     d_steps[i] += 1); bad rays are skipped as there.  A path that is not listed keeps every word.
+ *   - The entries must be distinct: a path listed twice gets an unspecified result (every access stays in bounds).
+ *   - d_work is rtmi_trace's block (RTMI_TRACE_WORK_WORDS words, reset on `stream`); afterwards [0] holds the abandoned
+ *     mesh searches and [1] the paths stepped.  n == 0 launches nothing and leaves d_work as it is; n_list == 0 resets
+ *     d_work and launches nothing.
+ *   - The waves take the list 64 entries at a time by their own number: no work cursor, no atomic in the distribution.
+ * Refused as rtmi_bounce refuses, and for n_list negative or above 2^31 - 1 or a null d_list with n_list > n. */
+#define RTMI_PATH_COMPACT_ITEMS 1024
+size_t rtmi_path_compact_scratch_bytes(int64_t n_list);
+int rtmi_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in /* nullable */,
+                      int64_t n_list, const uint32_t *d_count_in /* nullable */, uint32_t *d_list_out,
+                      uint32_t *d_count_out, void *d_scratch, void *stream);
+int rtmi_bounce_list(const rtmi_scene *s, int64_t n, const uint32_t *d_list /* nullable */, int64_t n_list,
+                     const uint32_t *d_count /* nullable */, float *d_origins, float *d_dirs, void *d_states,
+                     float *d_emitted, float *d_attenuation, rtmi_hit *d_hits /* nullable */,
+                     uint32_t *d_steps /* nullable */, unsigned long long *d_work, void *stream);
+
 /* ------------------------------------------------------------ camera rays --
  * The render's primary rays as a call of their own, and the fold of a traced sample into the budget buffers.  For every
  * sample index `sample` = 0, 1, ... the three calls

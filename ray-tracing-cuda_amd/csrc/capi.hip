@@ -1263,6 +1263,53 @@ int rtmi_bounce(const rtmi_scene *sp, int64_t n, float *d_origins, float *d_dirs
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ steps over live paths only
+// What rtmi_path_compact and rtmi_bounce_list check of their list, without a HIP call.
+static int check_list(int64_t n, const uint32_t *d_list, int64_t n_list) {
+  if (n_list < 0) return fail(RTMI_ERR_INVALID, "negative list length");
+  if (n_list > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 list entries");
+  if (!d_list && n_list > n) return fail(RTMI_ERR_INVALID, "a null list is the paths 0 .. n_list - 1: n_list must not exceed n");
+  return RTMI_OK;
+}
+
+size_t rtmi_path_compact_scratch_bytes(int64_t n_list) { return path_compact_scratch_bytes(n_list); }
+
+int rtmi_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
+                      const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, void *d_scratch, void *stream) {
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
+  if (const int rc = check_list(n, d_list_in, n_list)) return rc;
+  if (n_list > 0 && !(d_origins && d_dirs && d_list_out && d_count_out && d_scratch))
+    return fail(RTMI_ERR_INVALID, "null ray, output list, output count or scratch array");
+  if (d_list_out && d_list_out == d_list_in) return fail(RTMI_ERR_INVALID, "d_list_out must not be d_list_in: ping-pong two lists");
+  if (d_count_out && d_count_out == d_count_in) return fail(RTMI_ERR_INVALID, "d_count_out must not be d_count_in: ping-pong two counts");
+  if (!d_count_out) return RTMI_OK;  // (n_list == 0 and nowhere to write the 0)
+  HIP_TRY(launch_path_compact(n, d_origins, d_dirs, d_list_in, n_list, d_count_in, d_list_out, d_count_out,
+                              reinterpret_cast<uint32_t *>(d_scratch), (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_bounce_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+                     float *d_origins, float *d_dirs, void *d_states, float *d_emitted, float *d_attenuation, rtmi_hit *d_hits,
+                     uint32_t *d_steps, unsigned long long *d_work, void *stream) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n >= 0 && n <= (int64_t)INT32_MAX)  // (else batch_prologue refuses n itself)
+    if (const int rc = check_list(n, d_list, n_list)) return rc;
+  const Scene *s;
+  int n_cu;
+  const int no_depth = 0;  // (as rtmi_bounce)
+  const int rc = batch_prologue(sp, n, d_origins && d_dirs && d_states && d_emitted && d_attenuation && d_work,
+                                "null ray, state, emitted, attenuation or work array", &no_depth, &s, &n_cu);
+  if (rc || n == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
+  if (n_list == 0) return RTMI_OK;                            // (an empty list: no path stepped, and d_work says so)
+  HIP_TRY(launch_bounce_list(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_list, n_list, d_count, d_origins, d_dirs,
+                             reinterpret_cast<uint32_t *>(d_states), d_emitted, d_attenuation,
+                             reinterpret_cast<int32_t *>(d_hits), d_steps, d_work, st));
+  return RTMI_OK;
+}
+
 int rtmi_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                    const float *d_attenuation, float *d_radiance, void *stream) {
   if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");

@@ -203,6 +203,19 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
 hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, float *d_o, float *d_d,
                          uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
                          unsigned long long *d_work, hipStream_t stream);
+// The same step for the listed paths only (rtmi_bounce_list; kernels.hip: bounce_list_kernel): d_list (nullable: the
+// identity) holds n_list entries at most, d_count (nullable, a device word) cuts it short; every array keeps n paths.
+// n_list >= 1.
+hipError_t launch_bounce_list(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const uint32_t *d_list,
+                              int64_t n_list, const uint32_t *d_count, float *d_o, float *d_d, uint32_t *d_states,
+                              float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
+                              unsigned long long *d_work, hipStream_t stream);
+// The live candidates' path indices, in the candidates' order, and their number (rtmi_path_compact): three launches, no
+// workgroup waits for another.  d_scratch: path_compact_scratch_bytes(n_list) bytes.
+size_t path_compact_scratch_bytes(int64_t n_list);
+hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
+                               const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, uint32_t *d_scratch,
+                               hipStream_t stream);
 // Trace's return expression over the first min(d_steps[i], layers) layers of the stacks float[layers][n][3] (rtmi_path_fold).
 hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                             const float *d_attenuation, float *d_radiance, hipStream_t stream);

@@ -207,6 +207,15 @@ __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void bounce
   render_body<F, true, false, false, 0, true>(rp.sc, rp.fr, rp.lc, rp.states, nullptr, nullptr, rp.counters, nullptr, nullptr, false,
                                               nullptr, nullptr, nullptr, nullptr, &ex.step);
 }
+// rtmi_bounce_list: bounce_kernel's twin with the LIST flag of the body set.  A kernel of its own, so that bounce_kernel
+// stays instruction for instruction what it is.
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void bounce_list_kernel(const CallParams *p) {
+  const RenderParams &rp = in_constant(p).rp;
+  const CallExtras &ex = in_constant(p).ex;
+  render_body<F, true, false, false, 0, true, true>(rp.sc, rp.fr, rp.lc, rp.states, nullptr, nullptr, rp.counters, nullptr, nullptr,
+                                                    false, nullptr, nullptr, nullptr, nullptr, &ex.step, &ex.list);
+}
 
 // ------------------------------------------------------------------ untile / post
 template <typename E, int C>
@@ -962,7 +971,8 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
 template <uint32_t F, auto Kernel>
 static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_layers, int fetch_batch, int n_cu,
                               CallExtras ex, uint32_t *d_states, float *d_out, uint32_t *d_ray_counts,
-                              unsigned long long *d_work, hipStream_t stream, bool id_stack = true) {
+                              unsigned long long *d_work, hipStream_t stream, bool id_stack = true,
+                              int64_t grid_items = -1) {  // (>= 0: the items the grid is capped by, when not fr.items)
   // workgroup size: the one that keeps the most lanes resident (a deep 32-bit layer stack can leave room for one
   // 256-lane workgroup per CU only, as for the render's mesh variants: capi.hip launch_shape)
   int threads = 0, per_cu = 0;
@@ -980,7 +990,7 @@ static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_l
   cp.rp.lc.lane_stride = 1, cp.rp.lc.fetch_batch = fetch_batch, cp.rp.lc.rate_scale = 1.f;
   cp.rp.states = d_states, cp.rp.out = d_out, cp.rp.ray_counts = d_ray_counts, cp.rp.counters = d_work;
   cp.ex = ex, cp.ex.tex_layers = tex_layers ? 1 : 0;
-  const int64_t want = (fr.items + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
+  const int64_t want = ((grid_items >= 0 ? grid_items : fr.items) + threads - 1) / threads, cap = (int64_t)n_cu * per_cu;
   return launch_block<Kernel>(LaunchAt{(int)(want < cap ? want : cap), threads, lds, stream}, cp,
                               reinterpret_cast<CallParams *>(reinterpret_cast<char *>(d_work) + kCallParamsOffset));
 }
@@ -1016,6 +1026,166 @@ hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &q
     ex.step = {d_o, d_d, d_emitted, d_attenuation, d_hits, d_steps, qd};
     return launch_call<F, bounce_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false);
   });
+}
+
+// The same step for the listed paths (rtmi_bounce_list; render_body.h: LIST).  Every array keeps n paths -- fr.items is n,
+// the stride of the RNG planes -- and only the grid is sized by the list: launch_call's occupancy-sized grid, capped by
+// n_list, the host's bound on a length that stays on the device.
+hipError_t launch_bounce_list(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const uint32_t *d_list,
+                              int64_t n_list, const uint32_t *d_count, float *d_o, float *d_d, uint32_t *d_states,
+                              float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
+                              unsigned long long *d_work, hipStream_t stream) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    FrameDev fr{};
+    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = 1, fr.post = 0;
+    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
+    fr.items = n;
+    CallExtras ex{};
+    ex.step = {d_o, d_d, d_emitted, d_attenuation, d_hits, d_steps, qd};
+    ex.list = {d_list, d_count, (uint32_t)n_list};
+    return launch_call<F, bounce_list_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false, n_list);
+  });
+}
+
+// ------------------------------------------------------------------ the live paths as a list (rtmi_path_compact)
+// Three launches, none of whose workgroups waits for another: each workgroup counts the live candidates among its
+// kCompactItems entries; one workgroup turns the counts into offsets (and the total into *d_count_out); each workgroup
+// finds its live candidates again and writes them from its offset on, in the candidates' order.  A wave owns
+// kCompactChunks consecutive chunks of 64 entries, lane l entry l of each, so a live candidate's place is its
+// workgroup's offset + the live ones of the waves and chunks before its own + those of the lower lanes (mbcnt).
+// The rays are read twice (24 B a path); the list's length, where it is on the device, is read by every workgroup and
+// the grids are sized by the host's bound.
+constexpr int kCompactThreads = 256, kCompactChunks = 4;
+constexpr int kCompactItems = kCompactThreads * kCompactChunks;  // entries per workgroup: a scratch word each
+constexpr int kCompactScanThreads = 256;  // the scan's one workgroup; each lane sums ceil(workgroups / 256) counts in a row
+static_assert(kCompactItems == RTMI_PATH_COMPACT_ITEMS, "rtmi.h states the entries per scratch word");
+
+struct CompactArgs {
+  const float *origins, *dirs;  // float[n][3]
+  const uint32_t *list_in;      // nullable: the candidates (null: 0, 1, 2, ...)
+  const uint32_t *count_in;     // nullable: a device word that cuts the candidates short
+  uint32_t n, n_list;
+};
+// Whether a step would step the ray (ro, rd): finite, and a direction that Ray's constructor (ray.cu:8-10) normalises to a
+// finite non-zero vector.  A RESTATEMENT of the predicate in render_body.h's take_item, line for line: with one
+// __device__ function called from both sites, all eight trace_kernel<F> and all eight bounce_kernel<F> compiled to other
+// instructions (and bounce_kernel<23> spilled four more SGPRs), and the existing kernels are not this feature's to
+// change.  tests/test_gpu_bounce_list.py holds the two to each other: a compaction's count is the next step's d_work[1].
+__device__ __forceinline__ bool live_ray(V3 ro, V3 rd) {
+  bool live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
+  V3 nd = splat(0.f);
+  if (live) nd = unit3_rn(rd);
+  live = live && finite3(nd) && (nd.x != 0.f || nd.y != 0.f || nd.z != 0.f);
+  return live;
+}
+// Entry e of the candidates: its path, and whether the next step would step it.
+__device__ __forceinline__ bool compact_live(const CompactArgs &a, uint32_t e, uint32_t end, uint32_t &path) {
+  path = 0u;
+  if (e >= end) return false;
+  path = a.list_in ? a.list_in[e] : e;
+  if (path >= a.n) return false;  // (not a path: dropped)
+  const float *o = a.origins + (int64_t)path * 3, *d = a.dirs + (int64_t)path * 3;
+  return live_ray(mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]));
+}
+__device__ __forceinline__ uint32_t compact_end(const CompactArgs &a) {
+  uint32_t end = a.n_list;
+  if (a.count_in) {
+    const uint32_t c = *a.count_in;
+    end = c < end ? c : end;
+  }
+  return end;
+}
+// The live candidates of this lane's kCompactChunks entries: their paths, the chunks' wave masks, and the wave's total.
+__device__ __forceinline__ uint32_t compact_wave(const CompactArgs &a, uint32_t (&path)[kCompactChunks],
+                                                 unsigned long long (&mask)[kCompactChunks]) {
+  const uint32_t end = compact_end(a);
+  // (entries below 2^31 + kCompactItems: the grid covers n_list <= 2^31 - 1)
+  const uint32_t first = blockIdx.x * (uint32_t)kCompactItems + (threadIdx.x >> 6) * (uint32_t)(64 * kCompactChunks) + (threadIdx.x & 63u);
+  uint32_t total = 0u;
+#pragma unroll
+  for (int c = 0; c < kCompactChunks; c++) {
+    mask[c] = __builtin_amdgcn_ballot_w64(compact_live(a, first + (uint32_t)c * 64u, end, path[c]));
+    total += (uint32_t)__popcll(mask[c]);
+  }
+  return total;
+}
+
+__global__ __launch_bounds__(kCompactThreads) void compact_count_kernel(CompactArgs a, uint32_t *__restrict__ counts) {
+  __shared__ uint32_t s_wave[kCompactThreads / 64];
+  uint32_t path[kCompactChunks];
+  unsigned long long mask[kCompactChunks];
+  const uint32_t total = compact_wave(a, path, mask);
+  if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = total;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    uint32_t sum = 0u;
+    for (int w = 0; w < kCompactThreads / 64; w++) sum += s_wave[w];
+    counts[blockIdx.x] = sum;
+  }
+}
+
+// counts[0 .. n_blocks) -> their exclusive prefix sums, in place; *count_out = their total.  One workgroup.
+__global__ __launch_bounds__(kCompactScanThreads) void compact_scan_kernel(uint32_t n_blocks, uint32_t *__restrict__ counts,
+                                                                            uint32_t *__restrict__ count_out) {
+  __shared__ uint32_t s_wave[kCompactScanThreads / 64];
+  const uint32_t per = (n_blocks + (uint32_t)kCompactScanThreads - 1u) / (uint32_t)kCompactScanThreads;
+  const uint32_t lo = threadIdx.x * per < n_blocks ? threadIdx.x * per : n_blocks;  // (per <= 2^13: no wrap)
+  const uint32_t hi = lo + per < n_blocks ? lo + per : n_blocks;
+  uint32_t sum = 0u;
+  for (uint32_t i = lo; i < hi; i++) sum += counts[i];
+  uint32_t incl = sum;  // inclusive scan over the wave's lanes
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t below = (uint32_t)__shfl_up((int)incl, off);
+    if ((threadIdx.x & 63u) >= (uint32_t)off) incl += below;
+  }
+  if ((threadIdx.x & 63u) == 63u) s_wave[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t run = incl - sum;
+  for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) run += s_wave[w];
+  for (uint32_t i = lo; i < hi; i++) {
+    const uint32_t c = counts[i];
+    counts[i] = run;
+    run += c;
+  }
+  if (threadIdx.x == (uint32_t)kCompactScanThreads - 1u) *count_out = run;  // (the last lane's end is the total)
+}
+
+__global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(CompactArgs a, const uint32_t *__restrict__ offsets,
+                                                                           uint32_t *__restrict__ list_out) {
+  __shared__ uint32_t s_wave[kCompactThreads / 64];
+  uint32_t path[kCompactChunks];
+  unsigned long long mask[kCompactChunks];
+  const uint32_t total = compact_wave(a, path, mask);
+  if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = total;
+  __syncthreads();
+  uint32_t at = offsets[blockIdx.x];
+  for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) at += s_wave[w];
+  const unsigned long long me = 1ull << (threadIdx.x & 63u);
+#pragma unroll
+  for (int c = 0; c < kCompactChunks; c++) {
+    // (at + rank < the total of all workgroups <= the candidates <= n_list: inside list_out)
+    if (mask[c] & me) list_out[at + (uint32_t)lane_rank(mask[c])] = path[c];
+    at += (uint32_t)__popcll(mask[c]);
+  }
+}
+
+size_t path_compact_scratch_bytes(int64_t n_list) {
+  if (n_list < 0) n_list = 0;
+  const int64_t blocks = cdiv(n_list, (int64_t)kCompactItems);
+  return (size_t)(blocks > 0 ? blocks : 1) * sizeof(uint32_t);
+}
+
+hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
+                               const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, uint32_t *d_scratch,
+                               hipStream_t stream) {
+  if (n_list == 0) return hipMemsetAsync(d_count_out, 0, sizeof(uint32_t), stream);
+  const CompactArgs a = {d_origins, d_dirs, d_list_in, d_count_in, (uint32_t)n, (uint32_t)n_list};
+  const unsigned blocks = (unsigned)cdiv(n_list, (int64_t)kCompactItems);
+  hipLaunchKernelGGL(compact_count_kernel, dim3(blocks), dim3(kCompactThreads), 0, stream, a, d_scratch);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kCompactScanThreads), 0, stream, (uint32_t)blocks, d_scratch, d_count_out);
+  hipLaunchKernelGGL(compact_scatter_kernel, dim3(blocks), dim3(kCompactThreads), 0, stream, a, (const uint32_t *)d_scratch, d_list_out);
+  return hipGetLastError();
 }
 
 // Trace's return expression over the layers the steps wrote (rtmi_path_fold; include/rtmi.h states the rule): one lane

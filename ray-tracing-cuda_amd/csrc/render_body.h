@@ -9,7 +9,8 @@
 // with FEATURES (rtmi_render_features, feature_kernel) it also sums what each sample's primary hit looks like.
 // STEP (with RAYS) is rtmi_bounce (bounce_kernel): ONE iteration of the loop per item -- the query, the winner's
 // resolution, Emit and Scatter, this same copy of them -- whose results are written out instead of stacked and folded:
-// no depth, no layer stack, no fold.
+// no depth, no layer stack, no fold.  LIST (with STEP) is rtmi_bounce_list (bounce_list_kernel): the same step, its items
+// the entries of a list of path indices, handed to the waves by index instead of drawn from the queue.
 // What each mode is told: RenderParams and CallExtras below.
 #pragma once
 
@@ -174,6 +175,11 @@ struct StepBufs {
   uint32_t *steps;               // nullable: += 1 per stepped path
   QueryDev qd;                   // the recording order's names of the winner (query_body.h: resolve_hit)
 };
+struct ListBufs {
+  const uint32_t *list;   // nullable: entry e of the list is path list[e] (null: path e)
+  const uint32_t *count;  // nullable: a device word that cuts the list short
+  uint32_t n_list;        // the host's bound on the list's length
+};
 struct CallExtras {
   union {  // one work-item source at a time; either way right behind RenderParams' pointers, which they are loaded with
     RayBufs rays;   // RAYS
@@ -190,6 +196,8 @@ struct CallExtras {
   FeatureBufs feat;
   // STEP (with RAYS, whose `rays` stays unset: the step reads its rays where it writes them)
   StepBufs step;
+  // LIST (with STEP): where the step's items come from (rtmi_bounce_list) -- behind everything the other modes read
+  ListBufs list;
 };
 struct CallParams {
   RenderParams rp;
@@ -211,7 +219,8 @@ __device__ __forceinline__ const P &in_constant(const P *p) {
 // (NOTES.md 11).
 // M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
 // the front end folds: with M == 0 every line below is the run-time test it was.
-template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0, bool STEP = false>
+template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0, bool STEP = false,
+          bool LIST = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -220,9 +229,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const float *__restrict__ ray_d = nullptr, bool tex_layers = true,
                                             const uint32_t *__restrict__ budget = nullptr,
                                             float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr,
-                                            const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr) {
+                                            const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr,
+                                            const ListBufs *list = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
   static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
+  static_assert(!LIST || STEP, "the list is where a step's items come from");
   static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
   static_assert(M == 0 || (F == F_TRIS && !RAYS && !BUDGET), "the pins are the list-triangle render's");
   static_assert(!((M & PIN_CHAINS) && (M & PIN_QUEUE)), "a wave gets its work one way");
@@ -380,6 +391,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         ro = mk(ray_o[q * 3 + 0], ray_o[q * 3 + 1], ray_o[q * 3 + 2]);
         rd = mk(ray_d[q * 3 + 0], ray_d[q * 3 + 1], ray_d[q * 3 + 2]);
       }
+      // (kernels.hip restates this predicate as live_ray, for the compaction: keep the two in step)
       bool live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
       V3 nd = splat(0.f);
       if (live) nd = unit3_rn(rd);  // Ray's constructor (ray.cu:8-10)
@@ -438,6 +450,16 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   uint32_t prio_tick = 0u;  // (wave-uniform)
   uint32_t pool_at = 0u, pool_end = 0u;  // (wave-uniform) list variants: the wave's share of the queue, [pool_at, pool_end)
   bool queue_dry = false;                // (wave-uniform) ... and the queue has nothing more to give
+  uint32_t list_at = 0u, list_count = 0u, list_stride = 0u;  // (wave-uniform, LIST) the wave's next chunk, the list's end, the grid's lanes
+  if constexpr (LIST) {
+    list_count = list->n_list;
+    if (list->count) {  // the device's count cuts the host's bound short, never the other way
+      const uint32_t c = *list->count;
+      list_count = c < list_count ? c : list_count;
+    }
+    list_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((blockIdx.x * n_threads + threadIdx.x) >> 6) << 6));
+    list_stride = gridDim.x * n_threads;
+  }
   // A frame with fewer pixels than the grid has lanes (C1: 65,536 on 262,144) is spread THIN: one pixel per
   // lane_stride lanes, so that every SIMD gets a wave and a wave's shared candidate tests serve 16 rays with 64 lanes
   // instead of 64 rays on a quarter of the SIMDs.  The idle lanes never fetch; they work in closest_hit.
@@ -508,7 +530,29 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     }
     const bool wave_heavy = !QUEUE && (F & F_BVH) && lc.exclusive &&
                             __builtin_amdgcn_ballot_w64(has_px && heavy && (active || k < k_end())) != 0ull;
-    if (!QUEUE && (F & F_BVH) && classes) {
+    if constexpr (LIST) {
+      // rtmi_bounce_list: items by index, no cursor and no atomic.  Chunk c of the list -- entries 64c .. 64c + 63 -- is
+      // one wave's, lane l taking entry 64c + l, and the wave with global number w walks chunks w, w + W, w + 2W, ... of
+      // the grid's W waves up to the count on the device.  A step leaves every lane idle, so a chunk is taken whole; a
+      // chunk none of whose entries is steppable (past the count, not a path, a bad ray) is followed by the wave's next
+      // at once.  (The loop's control is wave-uniform -- list_at, which so stays a scalar, and a ballot; `done` is set for
+      // all lanes together, and a wave that comes back with its chunks used up leaves through the same test.  The test
+      // for a taken item stands at the loop's end, not in a `while` at its head -- no lane holds an item on the way in:
+      // with it at the head bounce_list_kernel<16> takes 58 VGPRs where bounce_kernel<16> takes 57.)
+      for (;;) {
+        if (list_at >= list_count) {
+          done = true;
+          break;
+        }
+        const uint32_t e = list_at + (threadIdx.x & 63u);
+        if (e < list_count) {
+          const uint32_t item = list->list ? list->list[e] : e;
+          if (item < (uint32_t)n_items) (void)take_item((int64_t)item);  // (an entry that is no path is skipped; n < 2^31)
+        }
+        list_at += list_stride;  // (below 2^31 + the grid's lanes: no wrap)
+        if (__builtin_amdgcn_ballot_w64(has_px) != 0ull) break;
+      }
+    } else if (!QUEUE && (F & F_BVH) && classes) {
       const bool wants = !active && !done && !has_px;
       if (__builtin_amdgcn_ballot_w64(wants) != 0ull) {
         if (head_open)

@@ -21,6 +21,7 @@ STATE_WORDS = 6
 MAX_DEPTH = 64
 TRACE_WORK_WORDS = 256  # RTMI_TRACE_WORK_WORDS: the device words of one rtmi_trace call
 BUDGET_WORK_WORDS = TRACE_WORK_WORDS  # RTMI_BUDGET_WORK_WORDS: the device words of one rtmi_render_budget call
+PATH_COMPACT_ITEMS = 1024  # RTMI_PATH_COMPACT_ITEMS: list entries per workgroup (and per scratch word) of rtmi_path_compact
 MODE_FIELDS = 9  # RTMI_MODE_FIELDS: the words of rtmi_render_mode_ex
 FAST_PATH_FACTS = 14  # RTMI_FAST_PATH_FACTS: the words rtmi_fast_path_kernel reads
 MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
@@ -237,6 +238,11 @@ SYMBOLS = [
     ("rtmi_bounce", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtmi_path_fold", C.c_int, [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_path_compact_scratch_bytes", C.c_size_t, [C.c_int64]),
+    ("rtmi_path_compact", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_bounce_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -378,11 +384,12 @@ class Bounce:
     path's step count so far, or None; ``work`` the call's (RTMI_TRACE_WORK_WORDS,) int64 device words; ``origins``,
     ``directions`` and ``states``: the caller's tensors, which now hold the scattered rays.  ``check()`` waits for the call
     and raises when it abandoned a mesh search (the answers are then not to be used); ``stepped()`` is how many paths
-    the call stepped."""
+    the call stepped.  ``paths``: the ``Paths`` a ``bounce_list`` stepped (None: every path was a candidate)."""
 
-    def __init__(self, origins, directions, states, emitted, attenuation, hits, steps, work):
+    def __init__(self, origins, directions, states, emitted, attenuation, hits, steps, work, paths=None):
         self.origins, self.directions, self.states = origins, directions, states
         self.emitted, self.attenuation, self.hits, self.steps, self.work = emitted, attenuation, hits, steps, work
+        self.paths = paths
 
     def check(self):
         n = int(self.work[0].item())  # (a device-to-host copy: waits for the call)
@@ -439,6 +446,80 @@ def path_fold(directions, steps, emitted_stack, attenuation_stack, out=None):
                                     C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                "rtmi_path_fold")
     return out
+
+
+class Paths:
+    """A list of path indices on the device, as ``path_compact`` makes it and ``SceneBuilder.bounce_list`` steps it:
+    ``index``, a contiguous int32 CUDA tensor whose length is the list's CAPACITY; ``count``, a 1-element int32 CUDA tensor
+    holding how many of its leading entries are the list (None: all of them).  The count stays on the device; ``n()``
+    reads it back, which waits for the call that writes it."""
+
+    def __init__(self, index, count=None):
+        self.index, self.count = index, count
+        self._keep = None  # (what the call that fills the list may still read)
+
+    def n(self):
+        cap = int(self.index.shape[0])
+        return cap if self.count is None else min(cap, int(self.count.item()))
+
+
+def _list_args(paths, n, dev, what="paths"):
+    """(index tensor or None, n_list, count tensor or None) of a ``Paths`` (None: the identity over all n paths)."""
+    import torch
+    if paths is None:
+        return None, n, None
+    if not isinstance(paths, Paths):
+        raise RtmiError("%s must be an rtmi.Paths or None" % what)
+    idx, cnt = paths.index, paths.count
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 1 and
+            idx.is_contiguous() and idx.device == dev):
+        raise RtmiError("%s.index must be a contiguous CUDA int32 tensor of shape (capacity,) on the rays' device" % what)
+    if cnt is not None and not _is_buffer(cnt, (1,), dev, torch.int32):
+        raise RtmiError("%s.count must be a CUDA int32 tensor of shape (1,) on the rays' device, or None" % what)
+    if int(idx.shape[0]) > 0x7fffffff:
+        raise RtmiError("%s.index holds more than 2^31 - 1 entries" % what)
+    return idx, int(idx.shape[0]), cnt
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _path_compact(n, origins, directions, idx, n_list, cnt, out, dev):
+    """rtmi_path_compact on checked arguments, with a scratch of its own, on torch's current stream."""
+    import torch
+    words = lib().rtmi_path_compact_scratch_bytes(n_list) // 4
+    scratch = torch.empty((max(words, 1),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().rtmi_path_compact(n, _ptr(origins), _ptr(directions), _ptr(idx), n_list, _ptr(cnt), _ptr(out.index),
+                                       _ptr(out.count), _ptr(scratch),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rtmi_path_compact")
+    out._keep = (origins, directions, idx, cnt, scratch)
+    return out
+
+
+def path_compact(origins, directions, paths=None, out=None):
+    """The live paths among ``paths`` as a list, in the list's own order (rtmi_path_compact), enqueued on torch's
+    current stream; nothing is read back.
+
+    ``origins`` / ``directions``: CUDA float32 (N, 3) tensors, only read.  A path is live exactly when the next step
+    would step it (``SceneBuilder.bounce``'s bad rays, ended paths among them, are not).  ``paths``: the candidates, a
+    ``Paths`` (entries >= N are dropped), or None for all N paths.  ``out``: an optional ``Paths`` to write into, with a
+    count tensor and room for every candidate, and not ``paths`` itself (two lists are ping-ponged).  Returns the
+    ``Paths``: ascending indices for ascending (or no) ``paths``."""
+    import torch
+    n, dev, _ = _check_batch("rtmi_path_compact", origins, directions)
+    idx, n_list, cnt = _list_args(paths, n, dev)
+    if out is None:
+        out = Paths(torch.empty((n_list,), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+    else:
+        o_idx, o_cap, o_cnt = _list_args(out, n, dev, "out")
+        if o_idx is None or o_cnt is None or o_cap < n_list:
+            raise RtmiError("out must be an rtmi.Paths with a count tensor and room for every candidate (%d)" % n_list)
+        if (idx is not None and o_idx.data_ptr() == idx.data_ptr() and n_list > 0) or \
+                (cnt is not None and o_cnt.data_ptr() == cnt.data_ptr()):
+            raise RtmiError("out must not be paths: rtmi_path_compact reads one list while it writes the other")
+    return _path_compact(n, origins.contiguous(), directions.contiguous(), idx, n_list, cnt, out, dev)
 
 
 class Adaptive(collections.namedtuple("Adaptive", "tiles samples passes total_samples features", defaults=(None,))):
@@ -889,8 +970,22 @@ class SceneBuilder:
         ``hits``: True for the step's hit records, or an (N, 12) int32 tensor to write them into; ``steps``: an optional
         (N,) int32 tensor whose entry is incremented for every path this call steps.  Returns ``Bounce``; call
         ``.check()`` on it before trusting the answers of a mesh scene."""
+        return self._step(False, None, origins, directions, states, emitted, attenuation, hits, steps)
+
+    def bounce_list(self, paths, origins, directions, states, emitted=None, attenuation=None, hits=False, steps=None):
+        """``bounce`` for the paths of a list only (rtmi_bounce_list), enqueued on torch's current stream.
+
+        ``paths``: a ``Paths`` (``path_compact`` makes them), or None for the identity list over all N.  Every tensor is
+        indexed by path and has ``bounce``'s shape with N paths; a listed path gets exactly what ``bounce`` gives it, a
+        path that is not listed keeps every word, an entry >= N is skipped.  The entries must be distinct: a path listed
+        twice gets an unspecified result.  The list's count is read on the device.  Returns ``Bounce``, its ``paths`` the
+        list."""
+        return self._step(True, paths, origins, directions, states, emitted, attenuation, hits, steps)
+
+    def _step(self, listed, paths, origins, directions, states, emitted, attenuation, hits, steps):
         import torch
-        n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
+        n, dev, _ = _check_batch("rtmi_bounce_list" if listed else "rtmi_bounce", origins, directions)
+        idx, n_list, cnt = _list_args(paths, n, dev)
         if not (origins.is_contiguous() and directions.is_contiguous()):
             raise RtmiError("origins and directions must be contiguous: rtmi_bounce writes the scattered rays into them")
         if not _is_buffer(states, (STATE_WORDS, n), dev, torch.int32):
@@ -912,27 +1007,43 @@ class SceneBuilder:
             attenuation = torch.empty((n, 3), dtype=torch.float32, device=dev)
         work = torch.zeros((TRACE_WORK_WORDS,), dtype=torch.int64, device=dev)  # (n == 0 leaves it untouched)
         with torch.cuda.device(dev):
-            _check(self.L.rtmi_bounce(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
-                                      C.c_void_p(states.data_ptr()), C.c_void_p(emitted.data_ptr()),
-                                      C.c_void_p(attenuation.data_ptr()),
-                                      C.c_void_p(raw.data_ptr()) if raw is not None else None,
-                                      C.c_void_p(steps.data_ptr()) if steps is not None else None,
-                                      C.c_void_p(work.data_ptr()), stream), "rtmi_bounce")
+            if listed:
+                _check(self.L.rtmi_bounce_list(self.h, n, _ptr(idx), n_list, _ptr(cnt), C.c_void_p(origins.data_ptr()),
+                                               C.c_void_p(directions.data_ptr()), C.c_void_p(states.data_ptr()),
+                                               C.c_void_p(emitted.data_ptr()), C.c_void_p(attenuation.data_ptr()),
+                                               _ptr(raw), _ptr(steps), C.c_void_p(work.data_ptr()), stream),
+                       "rtmi_bounce_list")
+            else:
+                _check(self.L.rtmi_bounce(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                          C.c_void_p(states.data_ptr()), C.c_void_p(emitted.data_ptr()),
+                                          C.c_void_p(attenuation.data_ptr()),
+                                          C.c_void_p(raw.data_ptr()) if raw is not None else None,
+                                          C.c_void_p(steps.data_ptr()) if steps is not None else None,
+                                          C.c_void_p(work.data_ptr()), stream), "rtmi_bounce")
         rec = None
         if raw is not None:
             f = raw.view(torch.float32)
             rec = Hits(f[:, 0], f[:, 1:3], f[:, 3:6], raw[:, 6], raw[:, 7], raw[:, 8], raw[:, 9])
             rec.raw = raw
-        return Bounce(origins, directions, states, emitted, attenuation, rec, steps, work)
+        return Bounce(origins, directions, states, emitted, attenuation, rec, steps, work, paths if listed else None)
 
-    def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None):
+    def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None, compact=False):
         """rtmi_trace as a loop of ``max_depth`` steps and one fold, on copies of the rays: bit for bit ``trace``'s
         radiance while ``each`` changes nothing.  ``states`` advance in place, as in ``trace``.  ``each(step, result)``
         is called after every step is enqueued, with the step's ``Bounce`` (``result.origins`` / ``.directions`` are the
         loop's own ray tensors): the place for shadow rays from ``result.hits``, or a termination rule -- zeroing a path's
         direction ends it, and the fold then takes its last layer's emitted as the path's end.  ``hits``: whether the
-        steps record hits (default: when ``each`` is given).  Returns ``Steps``."""
+        steps record hits (default: when ``each`` is given).  Returns ``Steps``.
+
+        ``compact``: False (the default) steps all N paths every time (``bounce``).  True steps the live paths only: every
+        step is a ``bounce_list`` on a list that ``path_compact`` made from the list of the step before (the first from
+        all N), two lists ping-ponged, their counts never read back; ``result.paths`` is the list the step used.  The
+        radiance is the same bit for bit.  A path that ``each`` revives or redirects while it is NOT in the current list
+        is not seen by the next compaction, which starts from that list: for such hooks ``compact="full"`` compacts from
+        all N paths before every step."""
         import torch
+        if not (compact is False or compact is True or compact == "full"):
+            raise RtmiError("compact must be False, True or \"full\"")
         n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
         max_depth = int(max_depth)
         if not 0 <= max_depth <= MAX_DEPTH:
@@ -947,11 +1058,25 @@ class SceneBuilder:
         steps = torch.zeros((n,), dtype=torch.int32, device=dev)
         want_hits = (each is not None) if hits is None else bool(hits)
         works = []
+        lists, cur = None, None
+        if compact and max_depth > 0:
+            lists = [Paths(torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+                     for _ in range(2)]
+            cur = _path_compact(n, o, d, None, n, None, lists[0], dev)
         for k in range(max_depth):
-            r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
+            if compact:
+                r = self.bounce_list(cur, o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
+            else:
+                r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
             works.append(r.work)
             if each is not None:
                 each(k, r)
+            if compact and k + 1 < max_depth:  # the next step's list: the live ones of this step's (or of all N)
+                nxt = lists[(k + 1) & 1]
+                if compact == "full":
+                    cur = _path_compact(n, o, d, None, n, None, nxt, dev)
+                else:
+                    cur = _path_compact(n, o, d, cur.index, n, cur.count, nxt, dev)
         rgb = path_fold(d, steps, E, A)
         return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works)
 
