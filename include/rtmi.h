@@ -602,6 +602,96 @@ int rtmi_bounce_list(const rtmi_scene *s, int64_t n, const uint32_t *d_list /* n
                      float *d_emitted, float *d_attenuation, rtmi_hit *d_hits /* nullable */,
                      uint32_t *d_steps /* nullable */, unsigned long long *d_work, void *stream);
 
+/* ----------------------------------------------------------------- direct --
+ * Next-event estimation for wavefront paths: a light table made at rtmi_scene_commit, one step that samples it, and a fold
+ * that knows the extra term.  A loop of rtmi_bounce_list, rtmi_direct_sample, rtmi_occluded and one rtmi_path_fold_direct
+ * is a path tracer with direct-light sampling whose expectation is rtmi_trace's: Lambertian::Scatter draws an exactly
+ * cosine-distributed direction, so its attenuation = albedo is the BRDF albedo / pi times cosine over pdf, and the light a
+ * scattered ray would find on a table light is estimated at the vertex instead and not counted again.  Added without a
+ * version change: a caller detects them by the symbol rtmi_direct_sample.  Every other entry is what it was.
+ *
+ * The light table.  A TABLE LIGHT is a Triangle, a Parallelogram or a face of a Parallelepiped of the world list (nested
+ * lists inlined) whose material is a DiffuseLight on a constant texture with three finite, not all zero components, and
+ * whose e1 x e2 (in binary64) is finite and non-zero.  Emissive spheres, mesh faces, image-textured lights and Sky are not
+ * table lights: their light keeps arriving through hits.  DiffuseLight::Emit ignores the side: lights are two-sided.
+ * One record per Parallelogram or box face (sampled as p0 + u e1 + v e2) and one per lone Triangle, in the order of the
+ * flattened world list:
+ *   - p0, e1, e2, n: bit for bit those of the hitable's first triangle as the kernels hold it (p0, p1 - p0, p2 - p0 and
+ *     normalize(cross(e1, e2)) in binary32);  emission: the texture's rgb;  material: the handle;
+ *   - kind: 0 parallelogram, 1 triangle;  entry, element: as rtmi_hit names a hit on the light (element: the face 0..5 of a
+ *     Parallelepiped, else 0);
+ *   - area: in binary64 c = e1 x e2 = (e1y e2z - e2y e1z, e1z e2x - e2z e1x, e1x e2y - e2x e1y),
+ *     |c| = sqrt((cx cx + cy cy) + cz cz), half of it for a triangle; rounded to binary32;
+ *   - cdf: with w_i = area_i * ((|r| + |g|) + |b|) and W = the sum of the w_i in table order, all in binary64 from the
+ *     unrounded areas, cdf_j = (float)((w_0 + ... + w_j) / W); the last entry is 1.0f;
+ *   - scale: (float)(area_j * W / (w_j * pi)), the area over the selection probability and pi.
+ * rtmi_scene_light_count: the table's length (0: none; RTMI_ERR_INVALID for a null or uncommitted scene).
+ * rtmi_scene_lights copies the first min(n, count) records into out (RTMI_ERR_INVALID for a null or uncommitted scene,
+ * n < 0, or a null out with n > 0).  rtmi_camera_update does not touch the table.
+ *
+ * rtmi_direct_sample runs after step number `step` (0-based) of rtmi_bounce or rtmi_bounce_list, on that step's outputs.
+ * Its candidates are rtmi_bounce_list's: (d_list, n_list, d_count), a null list the identity, entries >= n dropped, the
+ * entries distinct.  Every array is indexed by path and has n paths: d_origins, d_dirs (the scattered rays, only read),
+ * d_emitted and d_attenuation (layer `step` of the fold's stacks), d_shadow_origins, d_shadow_dirs and d_direct
+ * float[n][3]; d_hits rtmi_hit[n], 16-byte aligned; d_steps, d_flags uint32[n]; d_shadow_t_max float[n].
+ * d_light_states is RNG state in rtmi_trace's layout (RTMI_STATE_WORDS planes, stride n), seeded by the caller as a stream
+ * of its own -- rtmi_rng_init_n with another seed, or first = n.  The paths' own states are never touched: the paths of a
+ * loop with this call in it are bit for bit the paths of the loop without it.  (d_light_states may be the path states
+ * themselves; the paths then differ from the plain loop's.)  d_flags is zeroed once by the caller; bit 0 of a word means
+ * "this path's last vertex sampled the lights", the other bits are kept.
+ * Per candidate i, in binary32 with every operation rounded on its own (no fused multiply-add), sums of three as
+ * (x + y) + z, IEEE division and sqrt:
+ *   - NOT STEPPED by this step (d_steps[i] != step + 1): d_shadow_dirs[i] and d_direct[i] become three +0.0f,
+ *     d_shadow_t_max[i] = 0, the flag is cleared; nothing else changes.
+ *   - DROP: if the flag is set and the hit is on a table light -- d_hits[i].kind is TRIANGLE, PARALLELOGRAM or
+ *     PARALLELEPIPED and d_hits[i].material is the material of some table light -- d_emitted[i] becomes three +0.0f and
+ *     d_counts[1] += 1: the vertex before already accounted for that light.
+ *   - SAMPLE: if sample != 0, the table is not empty, the path scattered (d_dirs[i] is not the zero vector) and the hit's
+ *     material is Lambertian: r0, r1, r2 = CudaRandomFloat(0, 1) from d_light_states in that order (the state advances by
+ *     exactly three);  j = the smallest index with r0 <= cdf[j];  for a triangle light with r1 + r2 > 1: r1 = 1 - r1,
+ *     r2 = 1 - r2;  q = (p0 + r1 e1) + r2 e2;  x = d_origins[i];  w = q - x;  d2 = (wx wx + wy wy) + wz wz;
+ *     dist = sqrt(d2);  wi = w / dist per component;  cs = (Nx wix + Ny wiy) + Nz wiz with N = d_hits[i].normal;
+ *     cl = fabs(the same with the light's n).  The sample is valid iff d2 > 0 && cs > 0 && cl > 0 && dist < +inf (a NaN makes
+ *     it invalid).  Valid: g = ((cs * cl) / d2) * scale_j;  d_direct[i][c] = (d_attenuation[i][c] * emission_j[c]) * g;  the
+ *     shadow ray is (x, wi, dist * 0.999f).  Invalid: d_shadow_dirs[i] and d_direct[i] are three +0.0f, d_shadow_t_max[i] = 0.
+ *     Either way the flag is set and d_counts[0] += 1.
+ *   - OTHERWISE: d_shadow_dirs[i] and d_direct[i] are three +0.0f, d_shadow_t_max[i] = 0, the flag is cleared, no draw.
+ * d_shadow_origins[i] is written with a valid sample only: a zero direction is a bad ray for rtmi_occluded whatever its
+ * origin, answered "clear" at no cost, so the caller never masks anything and d_direct of such a path is +0.0f.  A
+ * candidate always gets its shadow direction, t_max, d_direct and flag written; a path that is not a candidate keeps every
+ * word.  The last step of a loop passes sample = 0: it only drops, as Trace would not have counted the emission one vertex
+ * further.  d_counts (nullable, device, two unsigned long long): [0] += paths sampled, [1] += emissions dropped.
+ * One lane per candidate, the list taken 64 entries at a time by wave number (no cursor, no atomic in the distribution).
+ *
+ * rtmi_path_fold_direct is rtmi_path_fold with one change: wherever that fold reads E[k], this one reads
+ * T[k] = d_occluded[k][i] ? E[k] : E[k] + D[k], one binary32 addition per channel.  d_direct is a stack float[layers][n][3]
+ * (layer k: what rtmi_direct_sample wrote after step k), d_occluded a stack uint8[layers][n] (what rtmi_occluded answered
+ * for layer k's shadow rays).  With every D word +0.0f and no E word -0.0f it is rtmi_path_fold bit for bit.
+ *
+ * Both are asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: rtmi_direct_sample for a null or uncommitted
+ * scene, n negative or above 2^31 - 1, n_list negative or above 2^31 - 1, a null d_list with n_list > n, a null array
+ * (d_list, d_count and d_counts are the optional ones) with n_list > 0, step >= RTMI_MAX_DEPTH; then also when
+ * the current device is not the one the scene was committed on.  rtmi_path_fold_direct as rtmi_path_fold, and for a null
+ * d_direct or d_occluded with n > 0.  n == 0 or n_list == 0 launches nothing. */
+typedef struct rtmi_light {
+  float p0[3], e1[3], e2[3], n[3];
+  float emission[3];
+  float area, cdf, scale;
+  int32_t kind;     /* 0 parallelogram, 1 triangle */
+  int32_t entry, element, material;
+} rtmi_light;
+int64_t rtmi_scene_light_count(const rtmi_scene *s);
+int rtmi_scene_lights(const rtmi_scene *s, rtmi_light *out, int64_t n);
+int rtmi_direct_sample(const rtmi_scene *s, int64_t n, const uint32_t *d_list /* nullable */, int64_t n_list,
+                       const uint32_t *d_count /* nullable */, uint32_t step, int sample, const float *d_origins,
+                       const float *d_dirs, const rtmi_hit *d_hits, const uint32_t *d_steps, float *d_emitted,
+                       const float *d_attenuation, void *d_light_states, uint32_t *d_flags, float *d_shadow_origins,
+                       float *d_shadow_dirs, float *d_shadow_t_max, float *d_direct,
+                       unsigned long long *d_counts /* nullable */, void *stream);
+int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                          const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded, float *d_radiance,
+                          void *stream);
+
 /* ------------------------------------------------------------ camera rays --
  * The render's primary rays as a call of their own, and the fold of a traced sample into the budget buffers.  For every
  * sample index `sample` = 0, 1, ... the three calls

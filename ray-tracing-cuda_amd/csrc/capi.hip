@@ -520,6 +520,20 @@ int rtmi_scene_commit(rtmi_scene *sp) {
   if ((rc = upload(s, s->q_face_input, &q.face_input))) return rc;
   q.sky_entry = s->q_sky_entry;
   s->qdev = q;
+  {
+    // the light table (rtmi_direct_sample only; direct.hip): beside QueryDev, SceneDev keeps its layout
+    std::vector<uint32_t> light_mats;
+    std::vector<LightRec> recs;
+    std::vector<float> cdf;
+    build_light_table(*s, &s->lights, &light_mats);
+    light_records(s->lights, &recs, &cdf);
+    LightDev l{};
+    if ((rc = upload(s, recs, &l.recs))) return rc;
+    if ((rc = upload(s, cdf, &l.cdf))) return rc;
+    if ((rc = upload(s, light_mats, &l.light_mats))) return rc;
+    l.n_lights = (int32_t)s->lights.size(), l.n_mats = (int32_t)s->mat_recs.size();
+    s->ldev = l;
+  }
   void *c = nullptr;
   // (behind the counters: the two kernel-argument blocks of a render without caller-owned scratch -- probe pass, real pass)
   HIP_TRY(hipMalloc(&c, RTMI_COUNTER_WORDS * sizeof(unsigned long long) + 2 * render_params_bytes()));
@@ -1318,6 +1332,69 @@ int rtmi_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d
   if (n > 0 && !(d_dirs && d_steps && d_emitted && d_attenuation && d_radiance))
     return fail(RTMI_ERR_INVALID, "null direction, step, emitted, attenuation or radiance array");
   HIP_TRY(launch_path_fold(n, layers, d_dirs, d_steps, d_emitted, d_attenuation, d_radiance, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ next-event estimation
+int64_t rtmi_scene_light_count(const rtmi_scene *sp) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!S(sp)->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  return (int64_t)S(sp)->lights.size();
+}
+
+int rtmi_scene_lights(const rtmi_scene *sp, rtmi_light *out, int64_t n) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!S(sp)->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative light count");
+  if (n > 0 && !out) return fail(RTMI_ERR_INVALID, "null light array");
+  const std::vector<rtmi_light> &l = S(sp)->lights;
+  const size_t c = std::min((size_t)n, l.size());
+  if (c) memcpy(out, l.data(), c * sizeof(rtmi_light));
+  return RTMI_OK;
+}
+
+int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+                       uint32_t step, int sample, const float *d_origins, const float *d_dirs, const rtmi_hit *d_hits,
+                       const uint32_t *d_steps, float *d_emitted, const float *d_attenuation, void *d_light_states,
+                       uint32_t *d_flags, float *d_shadow_origins, float *d_shadow_dirs, float *d_shadow_t_max, float *d_direct,
+                       unsigned long long *d_counts, void *stream) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
+  if (const int rc = check_list(n, d_list, n_list)) return rc;
+  if (step >= (uint32_t)RTMI_MAX_DEPTH) return fail(RTMI_ERR_INVALID, "step outside 0..RTMI_MAX_DEPTH - 1");
+  if (n_list > 0 && !(d_origins && d_dirs && d_hits && d_steps && d_emitted && d_attenuation && d_light_states && d_flags &&
+                      d_shadow_origins && d_shadow_dirs && d_shadow_t_max && d_direct))
+    return fail(RTMI_ERR_INVALID, "null ray, hit, step, emitted, attenuation, light state, flag, shadow ray or direct array");
+  const Scene *s = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  const bool work = n > 0 && n_list > 0;
+  int n_cu = 0;
+  if (const int rc = scene_device(s, work ? &n_cu : nullptr)) return rc;
+  if (!work) return RTMI_OK;
+  DirectArgs a{};
+  a.lt = s->ldev, a.mats = s->dev.mats;
+  a.list = d_list, a.count = d_count;
+  a.n = (uint32_t)n, a.n_list = (uint32_t)n_list, a.step = step, a.sample = sample != 0 ? 1u : 0u;
+  a.origins = d_origins, a.dirs = d_dirs, a.hits = reinterpret_cast<const int32_t *>(d_hits), a.steps = d_steps;
+  a.emitted = d_emitted, a.attenuation = d_attenuation;
+  a.light_states = reinterpret_cast<uint32_t *>(d_light_states), a.flags = d_flags;
+  a.shadow_o = d_shadow_origins, a.shadow_d = d_shadow_dirs, a.shadow_t = d_shadow_t_max, a.direct = d_direct;
+  a.counts = d_counts;
+  HIP_TRY(launch_direct_sample(a, n_cu, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                          const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded, float *d_radiance,
+                          void *stream) {
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
+  if (layers < 1 || layers > RTMI_MAX_DEPTH) return fail(RTMI_ERR_INVALID, "layers outside 1..RTMI_MAX_DEPTH");
+  if (n > 0 && !(d_dirs && d_steps && d_emitted && d_attenuation && d_direct && d_occluded && d_radiance))
+    return fail(RTMI_ERR_INVALID, "null direction, step, emitted, attenuation, direct, occlusion or radiance array");
+  HIP_TRY(launch_path_fold_direct(n, layers, d_dirs, d_steps, d_emitted, d_attenuation, d_direct, d_occluded, d_radiance,
+                                  (hipStream_t)stream));
   return RTMI_OK;
 }
 

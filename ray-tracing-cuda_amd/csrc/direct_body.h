@@ -1,0 +1,180 @@
+// Next-event estimation for wavefront paths (rtmi_direct_sample, rtmi_path_fold_direct; include/rtmi.h "direct" states
+// the rule operation by operation).  The scene's light table -- the world-list triangles and parallelograms whose material
+// is a DiffuseLight on a constant texture -- is made on the host at commit (direct.hip: build_light_table); the step
+// kernel below picks one light per path by its share of area x emission, a point on it, and leaves the shadow ray and the
+// unoccluded contribution; rtmi_occluded answers the shadow rays and the fold adds what is visible.
+//
+// Every operation is one binary32 rounding in the order written (the translation unit is compiled with
+// -ffp-contract=off; division and sqrt are IEEE): tests/directlib.py restates the step in numpy and the two agree bit for
+// bit.
+#pragma once
+#include <stdint.h>
+
+#include "scene_dev.h"
+#include "vec.h"
+#include "xorwow.h"
+
+namespace rtmi {
+
+// One light, 128 aligned bytes.  The step gathers the first 80 per lane as five 16-byte loads: words 0..15 the geometry,
+// emission and scale, words 16..19 the kind.  The rest is the host's (rtmi_scene_lights) and travels along so that one
+// record says everything about a light.
+struct alignas(128) LightRec {
+  float p0[3], e1[3], e2[3], n[3];  // the pair's first HotTri, bit for bit
+  float emission[3];
+  float scale;     // area / (selection probability * pi)
+  int32_t kind;    // 0 parallelogram (p0 + u e1 + v e2), 1 triangle
+  int32_t material, entry, element;
+  float area, cdf;
+  int32_t pad[10];
+};
+static_assert(sizeof(LightRec) == 128, "LightRec is 128 bytes");
+
+// The table on the device, beside QueryDev: SceneDev keeps its layout.
+struct LightDev {
+  const LightRec *recs;
+  const float *cdf;            // per light, ascending, the last 1.0f: the search reads 4 bytes a probe, not a record
+  const uint32_t *light_mats;  // one bit per material: some table light has it
+  int32_t n_lights, n_mats;
+};
+
+constexpr int kLdsLights = 1024;  // at most this many cdf entries are staged in LDS (4 KiB); longer tables search global memory
+constexpr int kDirectThreads = 256;
+constexpr int kDirectBlocksPerCu = 8;  // the grid's cap: longer lists are walked in strides of the grid's lanes
+
+struct DirectArgs {
+  LightDev lt;
+  const MatRec *mats;
+  const uint32_t *list, *count;  // rtmi_bounce_list's candidates (both nullable)
+  uint32_t n, n_list, step, sample;
+  const float *origins, *dirs;
+  const int32_t *hits;  // rtmi_hit[n]
+  const uint32_t *steps;
+  float *emitted;
+  const float *attenuation;
+  uint32_t *light_states, *flags;
+  float *shadow_o, *shadow_d, *shadow_t, *direct;
+  unsigned long long *counts;  // nullable
+};
+
+// The smallest j with r0 <= cdf[j]; the last entry is 1 and r0 <= 1, so one exists.  j stays in [0, n - 1] whatever the
+// table holds.
+__device__ __forceinline__ int light_pick(const float *cdf, int n, float r0) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (r0 <= cdf[mid]) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void direct_body(const DirectArgs &a, float *s_cdf) {
+  const LightDev &lt = a.lt;
+  const bool staged = lt.n_lights > 0 && lt.n_lights <= kLdsLights;  // (wave-uniform)
+  if (staged) {
+    for (int i = (int)threadIdx.x; i < lt.n_lights; i += (int)blockDim.x) s_cdf[i] = lt.cdf[i];
+    __syncthreads();
+  }
+  uint32_t end = a.n_list;
+  if (a.count) {
+    const uint32_t c = *a.count;
+    end = c < end ? c : end;
+  }
+  // chunks of 64 entries by wave number, as bounce_list_kernel takes them: no cursor, no atomic
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const uint32_t stride = gridDim.x * blockDim.x;  // the grid's lanes (a multiple of 64)
+  uint32_t n_sampled = 0u, n_dropped = 0u;         // (wave-uniform)
+  for (uint64_t at = (uint64_t)wave * 64u; at < end; at += stride) {
+    const uint32_t e = (uint32_t)at + lane;
+    bool sampled = false, dropped = false;
+    uint32_t i = 0u;
+    bool cand = e < end;
+    if (cand) {
+      i = a.list ? a.list[e] : e;
+      cand = i < a.n;  // (an entry that is no path is dropped)
+    }
+    if (cand) {
+      const int64_t i3 = (int64_t)i * 3;
+      V3 wi = splat(0.f), dir = splat(0.f), x = splat(0.f);
+      float t_max = 0.f;
+      uint32_t flag = a.flags[i];
+      const uint32_t was = flag & 1u;
+      flag &= ~1u;
+      bool valid = false;
+      if (a.steps[i] == a.step + 1u) {
+        const int4 *hp = reinterpret_cast<const int4 *>(a.hits) + (int64_t)i * 3;
+        const int4 h0 = hp[0], h1 = hp[1];  // t u v nx | ny nz material kind  (the third 16 bytes name the hitable)
+        const int32_t mat = h1.z, kind = h1.w;
+        const bool mat_ok = mat >= 0 && mat < lt.n_mats;
+        if (was && mat_ok && (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM || kind == QHIT_PARALLELEPIPED) &&
+            lt.light_mats != nullptr && ((lt.light_mats[mat >> 5] >> (mat & 31)) & 1u)) {
+          a.emitted[i3 + 0] = 0.f, a.emitted[i3 + 1] = 0.f, a.emitted[i3 + 2] = 0.f;
+          dropped = true;
+        }
+        const V3 d = mk(a.dirs[i3 + 0], a.dirs[i3 + 1], a.dirs[i3 + 2]);
+        const bool scattered = d.x != 0.f || d.y != 0.f || d.z != 0.f;
+        if (a.sample != 0u && lt.n_lights > 0 && scattered && mat_ok && a.mats[mat].kind == MAT_LAMBERTIAN) {
+          sampled = true;
+          flag |= 1u;
+          Rng rng;
+          rng.d = a.light_states[0 * (int64_t)a.n + i], rng.v0 = a.light_states[1 * (int64_t)a.n + i];
+          rng.v1 = a.light_states[2 * (int64_t)a.n + i], rng.v2 = a.light_states[3 * (int64_t)a.n + i];
+          rng.v3 = a.light_states[4 * (int64_t)a.n + i], rng.v4 = a.light_states[5 * (int64_t)a.n + i];
+          const float r0 = rng_range(0.f, 1.f, rng);
+          float r1 = rng_range(0.f, 1.f, rng);
+          float r2 = rng_range(0.f, 1.f, rng);
+          a.light_states[0 * (int64_t)a.n + i] = rng.d, a.light_states[1 * (int64_t)a.n + i] = rng.v0;
+          a.light_states[2 * (int64_t)a.n + i] = rng.v1, a.light_states[3 * (int64_t)a.n + i] = rng.v2;
+          a.light_states[4 * (int64_t)a.n + i] = rng.v3, a.light_states[5 * (int64_t)a.n + i] = rng.v4;
+          const int j = staged ? light_pick(s_cdf, lt.n_lights, r0) : light_pick(lt.cdf, lt.n_lights, r0);
+          const float4 *lp = reinterpret_cast<const float4 *>(lt.recs + j);
+          const float4 l0 = lp[0], l1 = lp[1], l2 = lp[2], l3 = lp[3];  // p0 e1.x | e1.yz e2.xy | e2.z n | emission scale
+          const int4 l4 = reinterpret_cast<const int4 *>(lt.recs + j)[4];
+          if (l4.x == 1 && r1 + r2 > 1.f) r1 = 1.f - r1, r2 = 1.f - r2;
+          const V3 p0 = mk(l0.x, l0.y, l0.z), e1 = mk(l0.w, l1.x, l1.y), e2 = mk(l1.z, l1.w, l2.x), ln = mk(l2.y, l2.z, l2.w);
+          const V3 q = (p0 + r1 * e1) + r2 * e2;
+          x = mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2]);
+          const V3 w = q - x;
+          const float d2 = dot3(w, w);
+          const float dist = sqrtf(d2);
+          wi = w / dist;
+          const V3 N = mk(__int_as_float(h0.w), __int_as_float(h1.x), __int_as_float(h1.y));
+          const float cs = dot3(N, wi);
+          const float cl = fabsf(dot3(ln, wi));
+          valid = d2 > 0.f && cs > 0.f && cl > 0.f && dist < INFINITY;
+          if (valid) {
+            const float g = ((cs * cl) / d2) * l3.w;
+            const V3 att = mk(a.attenuation[i3 + 0], a.attenuation[i3 + 1], a.attenuation[i3 + 2]);
+            dir = (att * mk(l3.x, l3.y, l3.z)) * g;
+            t_max = dist * 0.999f;
+          } else {
+            wi = splat(0.f);
+          }
+        }
+      }
+      if (valid) a.shadow_o[i3 + 0] = x.x, a.shadow_o[i3 + 1] = x.y, a.shadow_o[i3 + 2] = x.z;
+      a.shadow_d[i3 + 0] = wi.x, a.shadow_d[i3 + 1] = wi.y, a.shadow_d[i3 + 2] = wi.z;
+      a.shadow_t[i] = t_max;
+      a.direct[i3 + 0] = dir.x, a.direct[i3 + 1] = dir.y, a.direct[i3 + 2] = dir.z;
+      a.flags[i] = flag;
+    }
+    n_sampled += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(sampled));
+    n_dropped += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(dropped));
+  }
+  // the two counters, once per wave: one vector atomic each from lane 0
+  if (a.counts && lane == 0u) {
+    if (n_sampled) atomicAdd(&a.counts[0], (unsigned long long)n_sampled);
+    if (n_dropped) atomicAdd(&a.counts[1], (unsigned long long)n_dropped);
+  }
+}
+
+// rtmi_path_fold with T[k] = occluded[k] ? E[k] : E[k] + D[k] wherever that fold reads E[k].
+__device__ __forceinline__ V3 fold_term(const float *e, const float *d, uint8_t occ) {
+  V3 t = mk(e[0], e[1], e[2]);
+  if (!occ) t = t + mk(d[0], d[1], d[2]);
+  return t;
+}
+
+}  // namespace rtmi

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/rtmi.h"  // RTMI_COUNTER_WORDS
 #include "scene_dev.h"
 
@@ -219,6 +221,19 @@ hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d
 // Trace's return expression over the first min(d_steps[i], layers) layers of the stacks float[layers][n][3] (rtmi_path_fold).
 hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                             const float *d_attenuation, float *d_radiance, hipStream_t stream);
+// Next-event estimation (direct.hip; the argument block and the table's device form are direct_body.h's).  The light table
+// of a flattened scene as rtmi_scene_lights hands it out, and one bit per material that some table light has.
+struct Scene;
+struct LightRec;
+struct DirectArgs;
+void build_light_table(const Scene &s, std::vector<rtmi_light> *lights, std::vector<uint32_t> *light_mats);
+void light_records(const std::vector<rtmi_light> &lights, std::vector<LightRec> *recs, std::vector<float> *cdf);
+// The step for the candidates of a.list (rtmi_direct_sample): a.n_list >= 1.
+hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t stream);
+// rtmi_path_fold with T[k] = d_occluded[k] ? E[k] : E[k] + D[k] for E[k] (rtmi_path_fold_direct).
+hipError_t launch_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
+                                   const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded,
+                                   float *d_radiance, hipStream_t stream);
 // Per-pixel sample budgets (rtmi_render_budget; kernels.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).

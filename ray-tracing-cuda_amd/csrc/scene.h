@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rtmi.h"
+#include "direct_body.h"
 #include "scene_dev.h"
 #include "vec.h"
 
@@ -91,6 +93,9 @@ struct Scene {
   // rtmi_intersect only (QueryDev): flattened records -> recording order
   std::vector<int32_t> q_sphere_entry, q_pair_entry, q_bvh_entry, q_face_input;
   int32_t q_sky_entry = -1;
+  // rtmi_direct_sample only (LightDev): the table lights, made at commit (direct.hip: build_light_table)
+  std::vector<rtmi_light> lights;
+  LightDev ldev{};
   std::vector<void *> dev_allocs;
   SceneDev dev{};
   QueryDev qdev{};

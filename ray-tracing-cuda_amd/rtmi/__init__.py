@@ -243,7 +243,17 @@ SYMBOLS = [
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtmi_bounce_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtmi_scene_light_count", C.c_int64, [C.c_void_p]),
+    ("rtmi_scene_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("rtmi_direct_sample", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int] +
+                                    [C.c_void_p] * 14),
+    ("rtmi_path_fold_direct", C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8),
 ]
+
+# rtmi_light of include/rtmi.h, as a numpy record (88 bytes)
+LIGHT_DTYPE = np.dtype([("p0", np.float32, 3), ("e1", np.float32, 3), ("e2", np.float32, 3), ("n", np.float32, 3),
+                        ("emission", np.float32, 3), ("area", np.float32), ("cdf", np.float32), ("scale", np.float32),
+                        ("kind", np.int32), ("entry", np.int32), ("element", np.int32), ("material", np.int32)])
 
 
 def lib():
@@ -401,12 +411,14 @@ class Bounce:
         return int(self.work[1].item())
 
 
-class Steps(collections.namedtuple("Steps", "rgb steps alive origins directions emitted attenuation works")):
+class Steps(collections.namedtuple("Steps", "rgb steps alive origins directions emitted attenuation works direct occluded flags",
+                                   defaults=(None, None, None))):
     """What ``SceneBuilder.trace_steps`` returns: ``rgb`` (N, 3) float32, the folded radiance; ``steps`` (N,) int32, the
     steps each path made; ``alive`` (N,) bool, the paths whose direction is still non-zero (``steps + alive`` is
     rtmi_trace's ray count); ``origins`` / ``directions``: the loop's own copies of the rays as the last step left them;
     ``emitted`` / ``attenuation``: the (max(max_depth, 1), N, 3) float32 layer stacks; ``works``: every step's work words.
-    ``check()`` waits for the loop and raises when a step abandoned a mesh search."""
+    With ``direct=True`` also ``direct`` (layers, N, 3) float32, ``occluded`` (layers, N) uint8 -- the stacks
+    ``path_fold_direct`` read -- and ``flags`` (N,) int32; else None.  ``check()`` waits for the loop and raises when a step abandoned a mesh search."""
 
     def check(self):
         for k, w in enumerate(self.works):
@@ -446,6 +458,43 @@ def path_fold(directions, steps, emitted_stack, attenuation_stack, out=None):
                                     C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                "rtmi_path_fold")
     return out
+
+
+def path_fold_direct(directions, steps, emitted_stack, attenuation_stack, direct_stack, occluded_stack, out=None):
+    """``path_fold`` with the direct light of every layer added where its shadow ray was clear (rtmi_path_fold_direct):
+    wherever that fold reads E[k] this one reads ``occluded[k] ? E[k] : E[k] + D[k]``.  ``direct_stack``: contiguous
+    (layers, N, 3) float32, layer k what ``SceneBuilder.direct_sample`` wrote after step k; ``occluded_stack``: contiguous
+    (layers, N) uint8 or bool, what ``SceneBuilder.occluded`` answered for layer k's shadow rays.  The rest as ``path_fold``."""
+    try:
+        import torch
+    except ImportError:
+        raise RtmiError("directions: torch is needed for rtmi_path_fold_direct")
+    if not (isinstance(directions, torch.Tensor) and directions.is_cuda and directions.dtype == torch.float32 and
+            directions.dim() == 2 and directions.shape[1] == 3 and directions.is_contiguous()):
+        raise RtmiError("directions must be a contiguous CUDA float32 tensor of shape (N, 3): rtmi_path_fold_direct has no CPU path")
+    n, dev = int(directions.shape[0]), directions.device
+    if not _is_buffer(steps, (n,), dev, torch.int32):
+        raise RtmiError("steps must be a contiguous CUDA int32 tensor of shape (N,) on the directions' device")
+    if not (isinstance(emitted_stack, torch.Tensor) and emitted_stack.dim() == 3 and 1 <= emitted_stack.shape[0] <= MAX_DEPTH):
+        raise RtmiError("emitted_stack must have shape (layers, N, 3) with 1 <= layers <= %d" % MAX_DEPTH)
+    layers = int(emitted_stack.shape[0])
+    for name, t in (("emitted_stack", emitted_stack), ("attenuation_stack", attenuation_stack), ("direct_stack", direct_stack)):
+        if not _is_buffer(t, (layers, n, 3), dev, torch.float32):
+            raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape (layers, N, 3) on the directions' device" % name)
+    if not _is_buffer(occluded_stack, (layers, n), dev, torch.uint8, torch.bool):
+        raise RtmiError("occluded_stack must be a contiguous CUDA uint8 or bool tensor of shape (layers, N) on the directions' device")
+    out = _out_buffer(out, "float32 tensor of shape (N, 3)", (n, 3), dev, torch.float32)
+    with torch.cuda.device(dev):
+        _check(lib().rtmi_path_fold_direct(n, layers, _ptr(directions), _ptr(steps), _ptr(emitted_stack), _ptr(attenuation_stack),
+                                           _ptr(direct_stack), _ptr(occluded_stack), _ptr(out),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rtmi_path_fold_direct")
+    return out
+
+
+DirectSample = collections.namedtuple("DirectSample", "origins directions t_max direct flags counts")
+"""What ``SceneBuilder.direct_sample`` returns: the shadow rays ``origins`` / ``directions`` (N, 3) float32 and ``t_max``
+(N,) float32 -- a zero direction where a path has none, which ``occluded`` answers "clear" --, ``direct`` (N, 3) float32,
+the unoccluded contribution, ``flags`` (N,) int32 and ``counts`` (2,) int64: paths sampled, emissions dropped."""
 
 
 class Paths:
@@ -887,6 +936,58 @@ class SceneBuilder:
             pass
         return self
 
+    def lights(self):
+        """The committed scene's light table (rtmi_scene_lights): a numpy record array of dtype ``LIGHT_DTYPE`` with the
+        fields p0, e1, e2, n, emission (each (L, 3) float32), area, cdf, scale (float32), kind, entry, element, material
+        (int32) -- ``lights()["cdf"]`` and so on; length 0 when no world-list triangle or parallelogram emits."""
+        n = _check(self.L.rtmi_scene_light_count(self.h), "rtmi_scene_light_count")
+        out = np.zeros((n,), dtype=LIGHT_DTYPE)
+        _check(self.L.rtmi_scene_lights(self.h, out.ctypes.data_as(C.c_void_p), n), "rtmi_scene_lights")
+        return out
+
+    def direct_sample(self, step, result, light_states, flags, sample=True, out=None, counts=None):
+        """Next-event estimation after step number ``step`` of a loop (rtmi_direct_sample), on torch's current stream.
+
+        ``result``: the ``Bounce`` of that step, made with ``hits=True``, ``steps`` and the layer tensors ``emitted`` /
+        ``attenuation`` of the fold's stacks; its candidates are the step's (``result.paths``, or all N).  ``light_states``:
+        a contiguous (6, N) int32 tensor of RNG states of their own (``rng_states`` with another seed, or ``first=N``),
+        advanced by three draws per sampled path; ``flags``: an (N,) int32 tensor, zeroed once before the loop.
+        ``sample=False`` (a loop's last step) only drops.  A path that hits a table light after its previous vertex
+        sampled the lights has ``result.emitted`` zeroed.  ``out``: an optional ``(origins, directions, t_max, direct)`` of
+        (N, 3), (N, 3), (N,), (N, 3) float32 tensors to write into (tensors made here start as zeros); ``counts``: an
+        optional (2,) int64 tensor to add into.  Returns ``DirectSample``."""
+        import torch
+        if not isinstance(result, Bounce) or result.hits is None or result.steps is None:
+            raise RtmiError("result must be the Bounce of a step made with hits=True and steps")
+        o, d = result.origins, result.directions
+        n, dev, _ = _check_batch("rtmi_direct_sample", o, d)
+        step = int(step)
+        if not 0 <= step < MAX_DEPTH:
+            raise RtmiError("step %d outside [0, %d)" % (step, MAX_DEPTH))
+        idx, n_list, cnt = _list_args(result.paths, n, dev)
+        if not _is_buffer(light_states, (STATE_WORDS, n), dev, torch.int32):
+            raise RtmiError("light_states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
+        if not _is_buffer(flags, (n,), dev, torch.int32):
+            raise RtmiError("flags must be a contiguous CUDA int32 tensor of shape (N,) on the rays' device")
+        if counts is None:
+            counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+        elif not _is_buffer(counts, (2,), dev, torch.int64):
+            raise RtmiError("counts must be a CUDA int64 tensor of shape (2,) on the rays' device")
+        if out is None:
+            out = (torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
+                   torch.zeros((n,), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev))
+        so, sd, st, dd = out
+        for name, t, shape in (("origins", so, (n, 3)), ("directions", sd, (n, 3)), ("t_max", st, (n,)), ("direct", dd, (n, 3))):
+            if not _is_buffer(t, shape, dev, torch.float32):
+                raise RtmiError("out's %s must be a contiguous CUDA float32 tensor of shape %s on the rays' device" % (name, shape))
+        stream = self._stream(dev)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_direct_sample(self.h, n, _ptr(idx), n_list, _ptr(cnt), step, 1 if sample else 0, _ptr(o), _ptr(d),
+                                             _ptr(result.hits.raw), _ptr(result.steps), _ptr(result.emitted),
+                                             _ptr(result.attenuation), _ptr(light_states), _ptr(flags), _ptr(so), _ptr(sd),
+                                             _ptr(st), _ptr(dd), _ptr(counts), stream), "rtmi_direct_sample")
+        return DirectSample(so, sd, st, dd, flags, counts)
+
     def intersect(self, origins, directions, t_max=None, out=None):
         """Closest hit of each ray on the committed scene (rtmi_intersect), enqueued on torch's current stream.
 
@@ -1027,7 +1128,8 @@ class SceneBuilder:
             rec.raw = raw
         return Bounce(origins, directions, states, emitted, attenuation, rec, steps, work, paths if listed else None)
 
-    def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None, compact=False):
+    def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None, compact=False, direct=False,
+                    light_states=None):
         """rtmi_trace as a loop of ``max_depth`` steps and one fold, on copies of the rays: bit for bit ``trace``'s
         radiance while ``each`` changes nothing.  ``states`` advance in place, as in ``trace``.  ``each(step, result)``
         is called after every step is enqueued, with the step's ``Bounce`` (``result.origins`` / ``.directions`` are the
@@ -1040,8 +1142,17 @@ class SceneBuilder:
         all N), two lists ping-ponged, their counts never read back; ``result.paths`` is the list the step used.  The
         radiance is the same bit for bit.  A path that ``each`` revives or redirects while it is NOT in the current list
         is not seen by the next compaction, which starts from that list: for such hooks ``compact="full"`` compacts from
-        all N paths before every step."""
+        all N paths before every step.
+
+        ``direct=True`` (needs ``light_states``, a (6, N) int32 tensor of RNG states of their own; implies hits) is the
+        same loop with next-event estimation: after step k ``direct_sample(step=k, sample=k + 1 < max_depth)`` on that
+        step's list (or on all paths), ``occluded`` on its shadow rays into layer k of an occlusion stack, and
+        ``path_fold_direct`` at the end.  The paths themselves -- states, attenuation, hits, steps, final rays -- are the
+        plain loop's bit for bit, and the radiance has ``trace``'s expectation.  ``each`` runs after the step's direct
+        sampling."""
         import torch
+        if direct and light_states is None:
+            raise RtmiError("direct=True needs light_states: RNG states of their own, e.g. rng_states(seed, N, first=N)")
         if not (compact is False or compact is True or compact == "full"):
             raise RtmiError("compact must be False, True or \"full\"")
         n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
@@ -1057,6 +1168,17 @@ class SceneBuilder:
         A = torch.empty((layers, n, 3), dtype=torch.float32, device=dev)
         steps = torch.zeros((n,), dtype=torch.int32, device=dev)
         want_hits = (each is not None) if hits is None else bool(hits)
+        Dk = occ = flags = shadow = None
+        if direct:
+            want_hits = True
+            if not _is_buffer(light_states, (STATE_WORDS, n), dev, torch.int32):
+                raise RtmiError("light_states must be a contiguous CUDA int32 tensor of shape (6, N) on the rays' device")
+            Dk = torch.zeros((layers, n, 3), dtype=torch.float32, device=dev)
+            occ = torch.zeros((layers, n), dtype=torch.uint8, device=dev)
+            flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+            shadow = (torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
+                      torch.zeros((n,), dtype=torch.float32, device=dev))
+            counts = torch.zeros((2,), dtype=torch.int64, device=dev)
         works = []
         lists, cur = None, None
         if compact and max_depth > 0:
@@ -1069,6 +1191,9 @@ class SceneBuilder:
             else:
                 r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
             works.append(r.work)
+            if direct:
+                self.direct_sample(k, r, light_states, flags, sample=k + 1 < max_depth, out=shadow + (Dk[k],), counts=counts)
+                r.work[0] += self.occluded(shadow[0], shadow[1], shadow[2], out=occ[k]).counts[0]  # (abandoned searches: check())
             if each is not None:
                 each(k, r)
             if compact and k + 1 < max_depth:  # the next step's list: the live ones of this step's (or of all N)
@@ -1077,6 +1202,9 @@ class SceneBuilder:
                     cur = _path_compact(n, o, d, None, n, None, nxt, dev)
                 else:
                     cur = _path_compact(n, o, d, cur.index, n, cur.count, nxt, dev)
+        if direct:
+            rgb = path_fold_direct(d, steps, E, A, Dk, occ)
+            return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works, Dk, occ, flags)
         rgb = path_fold(d, steps, E, A)
         return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works)
 
@@ -1297,7 +1425,7 @@ class Renderer:
                                           self._stream()), "rtmi_sample_add")
         return self
 
-    def render_rays(self, budget=None, projection=None, count_rays=True, each=None):
+    def render_rays(self, budget=None, projection=None, count_rays=True, each=None, direct=False):
         """``render_budget(budget)`` as the composed loop -- for every sample index: ``camera_rays``, ``SceneBuilder.trace``,
         ``sample_add`` -- on torch's current stream, bit for bit the same sums, moments, counts and states with the scene's
         camera.  ``budget``: None for the frame's spp everywhere; the largest active budget is read back once (a
@@ -1305,7 +1433,12 @@ class Renderer:
         between the generation of a sample's rays and their tracing -- the place to run ``intersect`` or ``occluded`` on
         the very rays of the frame (or to change them in place).  Adds each trace's closest-hit queries to ``rays_total``
         and its abandoned mesh searches to ``budget_abandoned`` (``check()`` raises on them).  The frame must have been
-        made with ``post=False``."""
+        made with ``post=False``.
+
+        ``direct=True`` traces every sample with ``SceneBuilder.trace_steps(compact=True, direct=True)`` instead: the same
+        paths with next-event estimation, the same expectation and less variance where small lights light the scene; the
+        sums are then not ``render_budget``'s.  Its light states are seeded from the renderer's seed with first = items on
+        the first such call and carried on."""
         torch = self.torch
         if self.frame.post_process:
             raise RtmiError("render_rays needs a frame made with post=False: per-pixel sample counts have no uniform division (resolve)")
@@ -1328,6 +1461,17 @@ class Renderer:
                 self.camera_rays(sample, budget, projection, out=(origins, dirs))
                 if each is not None:
                     each(sample, origins, dirs)
+                if direct:
+                    if getattr(self, "light_states", None) is None:
+                        self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
+                    st = self.scene.trace_steps(origins, dirs, self.states, int(self.frame.max_depth), compact=True, direct=True,
+                                                light_states=self.light_states)
+                    for w in st.works:
+                        self.budget_abandoned += w[0]
+                    queries = st.steps + st.alive.to(torch.int32)
+                    self.rays_total += queries.sum()
+                    self.sample_add(sample, st.rgb, queries if count_rays else None, budget)
+                    continue
                 _check(self.L.rtmi_trace(self.scene.h, self.items, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
                                          int(self.frame.max_depth), C.c_void_p(self.states.data_ptr()),
                                          C.c_void_p(radiance.data_ptr()), C.c_void_p(counts.data_ptr()) if count_rays else None,

@@ -1,15 +1,25 @@
 #!/bin/bash
-# Register / spill / scratch metadata of every kernel in a built librtmi.so (read from the embedded code object).
+# Register / spill / scratch metadata of every kernel in a built librtmi.so (read from the embedded code objects: one
+# per translation unit that has kernels).
 # Usage: tools/kernel_regs.sh [path/to/librtmi.so]
 SO=$(realpath "${1:-$(dirname "$0")/../ray-tracing-cuda_amd/lib/librtmi.so}")
 TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
 cd "$TMP"
-/opt/rocm/lib/llvm/bin/clang-offload-bundler --list --type=o --input="$SO" >/dev/null 2>&1
-# the fat binary sits in .hip_fatbin; extract the gfx950 code object
+# the fat binaries sit one behind the other in .hip_fatbin; extract the gfx950 code object of each
 /opt/rocm/lib/llvm/bin/llvm-objcopy -O binary --only-section=.hip_fatbin "$SO" fatbin
-/opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=fatbin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=co.o 2>/dev/null || { echo "unbundle failed"; exit 1; }
-/opt/rocm/lib/llvm/bin/llvm-readelf --notes co.o | python3 -c '
+python3 - <<'PY' || { echo "no offload bundle found"; exit 1; }
+import re, sys
+d = open("fatbin", "rb").read()
+at = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", d)]
+for k, a in enumerate(at):
+    open("part%d" % k, "wb").write(d[a:at[k + 1] if k + 1 < len(at) else len(d)])
+sys.exit(0 if at else 1)
+PY
+for part in part*; do
+  /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input="$part" --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output="$part.o" 2>/dev/null || { echo "unbundle failed"; exit 1; }
+  /opt/rocm/lib/llvm/bin/llvm-readelf --notes "$part.o"
+done | python3 -c '
 import sys, re
 txt = sys.stdin.read()
 for blk in txt.split("- .agpr_count")[1:]:
