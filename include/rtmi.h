@@ -692,6 +692,38 @@ int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint
                           const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded, float *d_radiance,
                           void *stream);
 
+/* rtmi_occluded_list.  rtmi_occluded for the candidates of (d_list, n_list, d_count) only: the visibility query of a loop
+ * whose other steps take a live-path list, and of any caller who shoots shadow or ambient-occlusion rays from the vertices
+ * rtmi_bounce_list leaves behind.  Added without a version change: a caller detects it by the symbol rtmi_occluded_list.
+ *   - The candidates are exactly rtmi_bounce_list's: the entries j in [0, min(n_list, d_count ? *d_count : n_list)), a null
+ *     d_list the identity (then n_list <= n), an entry >= n dropped before anything is addressed with it.  The count word is
+ *     read on the device, nothing synchronises with the host, and the grid is sized by n_list, not by n.
+ *   - EVERY array is indexed by path and has rtmi_occluded's shape with n paths, n <= 2^31 - 1: d_origins, d_dirs
+ *     float[n][3], d_t_max (nullable) float[n], d_occluded uint8[n].
+ *   - For a listed path i, d_occluded[i] is exactly the byte rtmi_occluded writes for the ray (o_i, d_i, t_max_i): bad rays
+ *     answer 0, a NaN t_max and t_max < 1e-3 are clear, Sky answers at 1e9, and the same two passes decide it (the bounded
+ *     pass, the near-box rule, the exact fallback of quirk g8).  A path that is not listed KEEPS ITS BYTE: a caller who wants
+ *     "clear" there zeroes the array once.
+ *   - Unlike rtmi_bounce_list, the entries need NOT be distinct: the query changes no state, so a path listed twice gets
+ *     the same byte twice.
+ *   - d_counts (nullable, device, two unsigned long long) is rtmi_occluded's: [0] += abandoned mesh searches, [1] += rays
+ *     answered by the fallback; a path listed twice is counted once per occurrence.
+ *   - The waves take the list 64 entries at a time by their own number: no work cursor, no atomic in the distribution; a
+ *     chunk behind the count or without a path in it costs its wave one test.
+ * Asynchronous on `stream`; the call shares no device state with any other call.  RTMI_ERR_INVALID before any HIP call for
+ * a null or uncommitted scene, n or n_list negative or above 2^31 - 1, a null d_list with n_list > n, a null d_origins,
+ * d_dirs or d_occluded with n > 0 and n_list > 0; then also when the current device is not the one the scene was committed
+ * on.  n == 0 or n_list == 0 launches nothing and writes nothing. */
+int rtmi_occluded_list(const rtmi_scene *s, int64_t n, const uint32_t *d_list /* nullable */, int64_t n_list,
+                       const uint32_t *d_count /* nullable */, const float *d_origins, const float *d_dirs,
+                       const float *d_t_max /* nullable */, uint8_t *d_occluded,
+                       unsigned long long *d_counts /* nullable */, void *stream);
+/* The diagnostic build (librtmi_check1.so) also exports, declared here only in words:
+ * rtmi_occluded_list_check_counts(s, n, d_list, n_list, d_count, d_origins, d_dirs, d_t_max, d_occluded, d_counts,
+ * unsigned long long *d_check, stream) -- the list form of rtmi_occluded_check_counts: every candidate that is a path is
+ * answered a second time by the unculled closest-hit engine from +inf, then the filter; d_check (nullable, device, two
+ * words) += {candidates re-done, disagreements}. */
+
 /* ------------------------------------------------------------ camera rays --
  * The render's primary rays as a call of their own, and the fold of a traced sample into the budget buffers.  For every
  * sample index `sample` = 0, 1, ... the three calls

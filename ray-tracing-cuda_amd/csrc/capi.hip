@@ -1398,6 +1398,43 @@ int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ any-hit queries for the paths of a list
+// rtmi_occluded for rtmi_bounce_list's candidates.  The arguments first, without a HIP call, then the scene's device.
+static int occluded_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+                         const float *d_o, const float *d_d, const float *d_t_max, uint8_t *d_occluded,
+                         unsigned long long *d_counts, unsigned long long *d_check, void *stream) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count n");
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths n");
+  if (const int rc = check_list(n, d_list, n_list)) return rc;
+  const bool work = n > 0 && n_list > 0;
+  if (work && !(d_o && d_d && d_occluded)) return fail(RTMI_ERR_INVALID, "null d_origins, d_dirs or d_occluded");
+  const Scene *s = S(sp);
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  int n_cu = 0;
+  if (const int rc = scene_device(s, work ? &n_cu : nullptr)) return rc;
+  if (!work) return RTMI_OK;
+  float near_lo[3], near_hi[3], near_short;
+  near_box(s, near_lo, near_hi, &near_short);
+  HIP_TRY(launch_occlusion_list(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, d_list, n_list,
+                                d_count, d_o, d_d, d_t_max, d_occluded, d_counts, d_check, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_occluded_list(const rtmi_scene *s, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+                       const float *d_origins, const float *d_dirs, const float *d_t_max, uint8_t *d_occluded,
+                       unsigned long long *d_counts, void *stream) {
+  return occluded_list(s, n, d_list, n_list, d_count, d_origins, d_dirs, d_t_max, d_occluded, d_counts, nullptr, stream);
+}
+#ifdef RTMI_CHECK_MARGINS
+int rtmi_occluded_list_check_counts(const rtmi_scene *s, int64_t n, const uint32_t *d_list, int64_t n_list,
+                                    const uint32_t *d_count, const float *d_origins, const float *d_dirs, const float *d_t_max,
+                                    uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check,
+                                    void *stream) {
+  return occluded_list(s, n, d_list, n_list, d_count, d_origins, d_dirs, d_t_max, d_occluded, d_counts, d_check, stream);
+}
+#endif
+
 // ------------------------------------------------------------------ per-pixel sample budgets
 // What the three entries below check of their frame, in the other entries' order: the arguments first, without a HIP call.
 static int budget_frame(const rtmi_frame *f, bool arrays, const char *null_arrays, FrameDev *d) {

@@ -190,6 +190,14 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
                             float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream);
+// The same query for the listed paths only (rtmi_occluded_list; kernels.hip: occlusion_list_kernel): launch_bounce_list's
+// (d_list, n_list, d_count), entries need not be distinct; every array keeps n paths, an unlisted path keeps its byte.
+// The grid is sized by n_list.  n_list >= 1.
+hipError_t launch_occlusion_list(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
+                                 float near_short, int n_cu, int64_t n, const uint32_t *d_list, int64_t n_list,
+                                 const uint32_t *d_count, const float *d_o, const float *d_d, const float *d_t_max,
+                                 uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check,
+                                 hipStream_t stream);
 // Radiance of caller rays (rtmi_trace; kernels.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
 // words, zeroed in stream order before the call -- [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's
 // cursor, and from byte kCallParamsOffset the kernel's argument block (written in stream order just before the launch).

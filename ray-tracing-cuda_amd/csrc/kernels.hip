@@ -962,6 +962,42 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
   });
 }
 
+// rtmi_occluded_list: occlusion_kernel's twin with the LIST flag of the body set, as bounce_list_kernel is bounce_kernel's.
+// A kernel of its own, so that occlusion_kernel stays what it was; the list's words travel behind the argument block the
+// two share.  (Its name must not contain "occlusion_kernel": tests/test_occluded_host.py counts those.)
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlusion_list_kernel(OcclusionParams p, OcclusionList l) {
+  occlusion_body<F, true>(p, l);
+}
+
+// Staging, LDS layout, stand-in words and sizing are launch_occlusion's; the grid is capped by the list's capacity
+// (n_list > 0), not by n: a short list over many paths launches few workgroups.
+hipError_t launch_occlusion_list(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
+                                 float near_short, int n_cu, int64_t n, const uint32_t *d_list, int64_t n_list,
+                                 const uint32_t *d_count, const float *d_o, const float *d_d, const float *d_t_max,
+                                 uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check,
+                                 hipStream_t stream) {
+  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
+    constexpr uint32_t F = decltype(v)::value;
+    size_t lds = 0;
+    OcclusionParams p;
+    p.sc = sc;
+    p.lc = query_cfg(F, sc, &lds);
+    int blocks = 0;
+    const hipError_t e = query_blocks<occlusion_list_kernel<F>>(lds, n_cu, n_list, &blocks);
+    if (e != hipSuccess) return e;
+    p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
+    p.counts = d_counts, p.check = d_check;
+    p.dummy_off = (int32_t)(lds - kQueryLdsExtra);
+    for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
+    p.near_short = near_short;
+    OcclusionList l;
+    l.list = d_list, l.count = d_count, l.n_list = (uint32_t)n_list;
+    hipLaunchKernelGGL(occlusion_list_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p, l);
+    return hipGetLastError();
+  });
+}
+
 // ------------------------------------------------------------------ the entries that own their device state
 // rtmi_trace, rtmi_render_budget, rtmi_render_features: render_body.h in a mode of Kernel's on the query variants (F_TEX
 // always: the layer stack is one 32-bit word per level, the material id or the sampled texel -- or, without tex_layers,

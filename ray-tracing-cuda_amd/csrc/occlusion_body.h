@@ -1,5 +1,5 @@
-// Batched any-hit visibility queries on caller-made rays (rtmi_occluded).  Included by kernels.hip inside namespace
-// rtmi, after query_body.h (not a stand-alone header).
+// Batched any-hit visibility queries on caller-made rays (rtmi_occluded, and rtmi_occluded_list for the paths of a
+// list).  Included by kernels.hip inside namespace rtmi, after query_body.h (not a stand-alone header).
 //
 // The answer is defined by rtmi_intersect: occluded[i] = 1 iff HitableList::Hit(Ray(o, d), 1e-3, inf) has a hit and
 // (float)t <= t_max[i].  The engine is closest_hit<F, true> (closest_hit.h, OCC) with query_body.h's staging, run in up
@@ -16,6 +16,9 @@
 //         fallback below, and the bound prunes little of a search that starts in the middle of the mesh.
 //   pass 1, exact fallback, only for uncertain lanes that accepted nothing: the unbounded engine from +inf, stopping
 //     once the running bound is at or below the seed; then the filter.  Counted in counts[1].
+//
+// LIST is rtmi_occluded_list (occlusion_list_kernel): the same query, its rays named by the candidates of a list.  Only
+// the place a lane's ray comes from differs; the passes, the near-box rule and the fallback are the lines below for both.
 #pragma once
 
 struct OcclusionParams {
@@ -30,6 +33,13 @@ struct OcclusionParams {
   int32_t dummy_off;          // byte offset in dynamic LDS of two words that stand in for a null `counts`
   float near_lo[3], near_hi[3];  // padded union of the meshes' root bounds (empty without meshes) ...
   float near_short;              // ... and the t_max below which a ray from inside them still walks bounded
+};
+
+// LIST: rtmi_bounce_list's candidates (list, count: both nullable).  Handed over beside OcclusionParams, not inside it: the
+// argument block of occlusion_kernel stays what it was.
+struct OcclusionList {
+  const uint32_t *list, *count;
+  uint32_t n_list;
 };
 
 // query_body.h's staging (render_body.h's prologue without the materials), as a function: the scene's pair corners,
@@ -94,8 +104,8 @@ __device__ __forceinline__ double occlusion_seed(float tm) {
   return m;
 }
 
-template <uint32_t F>
-__device__ __forceinline__ void occlusion_body(const OcclusionParams &p) {
+template <uint32_t F, bool LIST = false>
+__device__ __forceinline__ void occlusion_body(const OcclusionParams &p, const OcclusionList &l = OcclusionList{}) {
   constexpr bool DT = (F & F_SPHERE) != 0;
   typedef typename TSel<DT>::type T;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -112,18 +122,42 @@ __device__ __forceinline__ void occlusion_body(const OcclusionParams &p) {
   MeshStats st{};
 #endif
 
-  // ---- 64 consecutive rays per wave, the waves striding over the batch (as query_body.h)
+  // ---- 64 consecutive rays per wave, the waves striding over the batch (as query_body.h).  LIST: 64 consecutive
+  // entries -- chunk c of the list is one wave's, lane l taking entry 64c + l, and wave w of the grid's W walks chunks
+  // w, w + W, ... up to the count on the device, as bounce_list_kernel does: no cursor, no atomic.
   const int lane = (int)(threadIdx.x & 63u);
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  // (LIST: the wave's number through readfirstlane, so that the chunk's base, the loop's control and the count stay scalar.
+  // The list kernels then take no more VGPRs than their twins in the product build, and occlusion_list_kernel<26> of the
+  // diagnostic build 127 where it took 129 against its twin's 128, one occupancy step down.  The plain kernel keeps its
+  // expression: it stays instruction for instruction what it was.)
+  const int64_t wave = LIST ? (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+                            : (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6) * 64;
   const bool all_lanes_in = (F & F_BVH) || ((F & F_TRIS) && q.ll != nullptr && sc.n_pairs >= kCullMinPairs) ||
                             ((F & F_SGROUP) && q.cands != nullptr);  // wave-uniform
-  for (int64_t base = wave * 64; base < p.n; base += stride) {
-    const int64_t i = base + lane;
+  int64_t end = p.n;
+  if constexpr (LIST) {
+    end = (int64_t)l.n_list;
+    if (l.count != nullptr) {  // (wave-uniform: one word, read once per wave)
+      const int64_t c = (int64_t)*l.count;
+      end = c < end ? c : end;
+    }
+  }
+  for (int64_t base = wave * 64; base < end; base += stride) {
+    int64_t i = base + lane;
+    bool cand = i < end;
+    if constexpr (LIST) {
+      if (cand) {
+        const uint32_t item = l.list != nullptr ? l.list[i] : (uint32_t)i;
+        cand = (int64_t)item < p.n;  // (an entry that is no path is dropped before anything is addressed with it)
+        i = (int64_t)item;
+      }
+      if (__builtin_amdgcn_ballot_w64(cand) == 0ull) continue;  // no path in this chunk: on to the wave's next at once
+    }
     V3 o = splat(0.f), d = mk(0.f, 0.f, 1.f);  // (a lane without a usable ray carries a harmless one)
     bool live = false;
     float tm = INFINITY;
-    if (i < p.n) {
+    if (cand) {
       const V3 ro = mk(p.origins[i * 3], p.origins[i * 3 + 1], p.origins[i * 3 + 2]);
       const V3 rd = mk(p.dirs[i * 3], p.dirs[i * 3 + 1], p.dirs[i * 3 + 2]);
       live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
@@ -167,6 +201,9 @@ __device__ __forceinline__ void occlusion_body(const OcclusionParams &p) {
                                  , start, seed, &unc);
       occ = occ || (go && h.ok && h.t <= tm);  // rtmi_intersect's filter
     }
+    if constexpr (LIST) {
+      if (cand) p.occluded[i] = occ ? 1 : 0;  // (ahead of the diagnostic build's second answer: i is not held across it)
+    }
 #ifdef RTMI_CHECK_MARGINS
     // Diagnostic build: every ray answered a second time by the unculled engine from +inf, then the filter;
     // p.check[0] += rays re-done, [1] += disagreements.
@@ -185,13 +222,15 @@ __device__ __forceinline__ void occlusion_body(const OcclusionParams &p) {
 #endif
         );
       const bool occ2 = live && h2.ok && h2.t <= tm;
-      const unsigned long long na = __builtin_amdgcn_ballot_w64(i < p.n), nd = __builtin_amdgcn_ballot_w64(occ2 != occ);
+      const unsigned long long na = __builtin_amdgcn_ballot_w64(cand), nd = __builtin_amdgcn_ballot_w64(occ2 != occ);
       if (lane == 0 && p.check != nullptr) {
         if (na) atomicAdd(&p.check[0], (unsigned long long)__popcll(na));
         if (nd) atomicAdd(&p.check[1], (unsigned long long)__popcll(nd));
       }
     }
 #endif
-    if (i < p.n) p.occluded[i] = occ ? 1 : 0;
+    if constexpr (!LIST) {
+      if (cand) p.occluded[i] = occ ? 1 : 0;
+    }
   }
 }

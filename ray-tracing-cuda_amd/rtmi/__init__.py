@@ -25,6 +25,10 @@ PATH_COMPACT_ITEMS = 1024  # RTMI_PATH_COMPACT_ITEMS: list entries per workgroup
 MODE_FIELDS = 9  # RTMI_MODE_FIELDS: the words of rtmi_render_mode_ex
 FAST_PATH_FACTS = 14  # RTMI_FAST_PATH_FACTS: the words rtmi_fast_path_kernel reads
 MAX_MATERIALS = 1 << 24  # RTMI_MAX_MATERIALS: a larger scene is refused by commit (RTMI_ERR_CAPACITY)
+# what trace_steps(compact, direct=True, shadow=None) means: "all" (rtmi_occluded over all N shadow rays) or "list"
+# (rtmi_occluded_list on the step's list).  The outputs are the same; DESIGN.md 2.14 has the cost that decides it: on an
+# MI355X the "list" loop is not slower than the "all" loop on any of the four measured scenes.
+SHADOW_DEFAULT = "list"
 
 # rtmi_hit.kind (include/rtmi.h)
 RTMI_HIT_NONE = 0
@@ -248,6 +252,7 @@ SYMBOLS = [
     ("rtmi_direct_sample", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int] +
                                     [C.c_void_p] * 14),
     ("rtmi_path_fold_direct", C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8),
+    ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
 ]
 
 # rtmi_light of include/rtmi.h, as a numpy record (88 bytes)
@@ -1033,6 +1038,32 @@ class SceneBuilder:
                    "rtmi_occluded")
         return Occlusion(raw, counts, (origins, directions, t_max))
 
+    def occluded_list(self, paths, origins, directions, t_max=None, out=None):
+        """``occluded`` for the paths of a list only (rtmi_occluded_list), enqueued on torch's current stream.
+
+        ``paths``: a ``Paths`` (``path_compact`` makes them; a step's ``Bounce.paths``), or None for the identity list over
+        all N.  Every tensor is indexed by path and has ``occluded``'s shape with N paths.  A listed path gets exactly the
+        byte ``occluded`` gives its ray; an entry >= N is skipped; the entries need not be distinct (the query changes no
+        state).  The list's count is read on the device and the launch is sized by the list's capacity, not by N.
+        ``out``: an optional (N,) uint8 or bool CUDA tensor that is UPDATED -- a path that is not listed keeps its byte;
+        when it is None the answers start as zeros, so unlisted paths read "clear".  Returns ``Occlusion`` and refuses what
+        ``occluded`` refuses."""
+        import torch
+        n, dev, t_max = _check_batch("rtmi_occluded_list", origins, directions, t_max)
+        idx, n_list, cnt = _list_args(paths, n, dev)
+        if out is None:
+            out = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        elif not _is_buffer(out, (n,), dev, torch.uint8, torch.bool):
+            raise RtmiError("out must be a contiguous CUDA uint8 or bool tensor of shape (N,) on the rays' device")
+        stream = self._stream(dev)
+        origins, directions = origins.contiguous(), directions.contiguous()
+        raw = out.view(torch.uint8)
+        counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_occluded_list(self.h, n, _ptr(idx), n_list, _ptr(cnt), _ptr(origins), _ptr(directions),
+                                             _ptr(t_max), _ptr(raw), _ptr(counts), stream), "rtmi_occluded_list")
+        return Occlusion(raw, counts, (origins, directions, t_max, idx, cnt))
+
     def trace(self, origins, directions, states, max_depth, count_rays=False, out=None):
         """Path-traced radiance of each ray (rtmi_trace): Trace(world, Ray(o, d), &state, max_depth) as a render runs
         it for one sample, enqueued on torch's current stream.
@@ -1129,7 +1160,7 @@ class SceneBuilder:
         return Bounce(origins, directions, states, emitted, attenuation, rec, steps, work, paths if listed else None)
 
     def trace_steps(self, origins, directions, states, max_depth, each=None, hits=None, compact=False, direct=False,
-                    light_states=None):
+                    light_states=None, shadow=None):
         """rtmi_trace as a loop of ``max_depth`` steps and one fold, on copies of the rays: bit for bit ``trace``'s
         radiance while ``each`` changes nothing.  ``states`` advance in place, as in ``trace``.  ``each(step, result)``
         is called after every step is enqueued, with the step's ``Bounce`` (``result.origins`` / ``.directions`` are the
@@ -1149,12 +1180,29 @@ class SceneBuilder:
         step's list (or on all paths), ``occluded`` on its shadow rays into layer k of an occlusion stack, and
         ``path_fold_direct`` at the end.  The paths themselves -- states, attenuation, hits, steps, final rays -- are the
         plain loop's bit for bit, and the radiance has ``trace``'s expectation.  ``each`` runs after the step's direct
-        sampling."""
+        sampling.
+
+        ``shadow`` chooses the visibility query of ``direct=True``: ``"all"`` is ``occluded`` over all N shadow rays,
+        ``"list"`` is ``occluded_list`` on the list the step used (``result.paths``), valid only with ``compact`` and
+        ``direct=True``; None (the default) is ``SHADOW_DEFAULT`` where ``"list"`` is valid, else ``"all"``.  Every output
+        is the same bit for bit either way.  The occlusion stack starts as zeros, so a byte the list form does not write
+        reads "clear"; ``"all"`` writes 0 there too, because the path's shadow direction is the zero vector (a bad ray):
+        ``direct_sample`` gives every candidate that does not sample a zero shadow direction, the shadow tensors start as
+        zeros, and a path that leaves the list was a candidate in its last step, where -- ended, its direction zero -- it
+        did not sample.  (The one path outside this argument is ``bounce``'s documented bad scattered ray, a non-zero
+        direction that does not normalise: it may sample, leaves the list alive, and ``"all"`` answers its stale shadow
+        ray again in the layers after its last, which no fold reads.)"""
         import torch
         if direct and light_states is None:
             raise RtmiError("direct=True needs light_states: RNG states of their own, e.g. rng_states(seed, N, first=N)")
         if not (compact is False or compact is True or compact == "full"):
             raise RtmiError("compact must be False, True or \"full\"")
+        if shadow not in (None, "all", "list"):
+            raise RtmiError("shadow must be None, \"all\" or \"list\"")
+        if shadow == "list" and not (compact and direct):
+            raise RtmiError("shadow=\"list\" needs compact and direct=True: it queries the list a compacted step used")
+        if shadow is None:
+            shadow = SHADOW_DEFAULT if (compact and direct) else "all"
         n, dev, _ = _check_batch("rtmi_bounce", origins, directions)
         max_depth = int(max_depth)
         if not 0 <= max_depth <= MAX_DEPTH:
@@ -1168,7 +1216,7 @@ class SceneBuilder:
         A = torch.empty((layers, n, 3), dtype=torch.float32, device=dev)
         steps = torch.zeros((n,), dtype=torch.int32, device=dev)
         want_hits = (each is not None) if hits is None else bool(hits)
-        Dk = occ = flags = shadow = None
+        Dk = occ = flags = rays = None
         if direct:
             want_hits = True
             if not _is_buffer(light_states, (STATE_WORDS, n), dev, torch.int32):
@@ -1176,8 +1224,8 @@ class SceneBuilder:
             Dk = torch.zeros((layers, n, 3), dtype=torch.float32, device=dev)
             occ = torch.zeros((layers, n), dtype=torch.uint8, device=dev)
             flags = torch.zeros((n,), dtype=torch.int32, device=dev)
-            shadow = (torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
-                      torch.zeros((n,), dtype=torch.float32, device=dev))
+            rays = (torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
+                    torch.zeros((n,), dtype=torch.float32, device=dev))  # (the shadow rays: one set, rewritten every step)
             counts = torch.zeros((2,), dtype=torch.int64, device=dev)
         works = []
         lists, cur = None, None
@@ -1192,8 +1240,12 @@ class SceneBuilder:
                 r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
             works.append(r.work)
             if direct:
-                self.direct_sample(k, r, light_states, flags, sample=k + 1 < max_depth, out=shadow + (Dk[k],), counts=counts)
-                r.work[0] += self.occluded(shadow[0], shadow[1], shadow[2], out=occ[k]).counts[0]  # (abandoned searches: check())
+                self.direct_sample(k, r, light_states, flags, sample=k + 1 < max_depth, out=rays + (Dk[k],), counts=counts)
+                if shadow == "list":
+                    q = self.occluded_list(r.paths, rays[0], rays[1], rays[2], out=occ[k])
+                else:
+                    q = self.occluded(rays[0], rays[1], rays[2], out=occ[k])
+                r.work[0] += q.counts[0]  # (abandoned searches: check())
             if each is not None:
                 each(k, r)
             if compact and k + 1 < max_depth:  # the next step's list: the live ones of this step's (or of all N)
@@ -1435,7 +1487,8 @@ class Renderer:
         and its abandoned mesh searches to ``budget_abandoned`` (``check()`` raises on them).  The frame must have been
         made with ``post=False``.
 
-        ``direct=True`` traces every sample with ``SceneBuilder.trace_steps(compact=True, direct=True)`` instead: the same
+        ``direct=True`` traces every sample with ``SceneBuilder.trace_steps(compact=True, direct=True)`` instead (its
+        shadow query is that loop's default, ``SHADOW_DEFAULT``; the sums are the same with either): the same
         paths with next-event estimation, the same expectation and less variance where small lights light the scene; the
         sums are then not ``render_budget``'s.  Its light states are seeded from the renderer's seed with first = items on
         the first such call and carried on."""
