@@ -63,12 +63,22 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 // One triangle of the culled list scan by its record index (2 * pair + which): base point and the two edges.  Staged
 // lists read the 48-byte TriPts record from LDS; longer ones gather the same words from the HotTri of that index, which
 // begins with them (scene_dev.h).  Returns whether the triangle is there: a lone Triangle has no second one.
-template <uint32_t M>
+// PAIR: the caller reads both records of a pair, `which` a constant: with trims_mul24 the address is formed from the
+// pair's first record, so the two calls share one product and the second record is 48 bytes on.
+template <uint32_t M, bool PAIR = false>
 __device__ __forceinline__ bool load_tri_pts(const SceneDev &sc, const float4 *s_tris, int rec, int which, V3 &p0, V3 &e1, V3 &e2) {
   float4 qa, qb, qc;
   bool present;
   if ((M & PIN_LDS_TABLES) || s_tris != nullptr) {  // (wave-uniform) staged in LDS
+    // (trims_mul24: a record index is below 2 * kLdsPairs + 2 and a record is 48 bytes -- a 24-bit product, full rate)
     const float4 *pp = s_tris + (size_t)rec * 3;
+    if (trims_mul24(M)) {
+      // the record's LDS address (the low word of the generic pointer) in one multiply-add, then opaque: an address the
+      // compiler can re-form for the price of an instruction or two it re-forms at every use instead of keeping it
+      uint32_t at = (uint32_t)(uintptr_t)s_tris + __umul24((uint32_t)(PAIR ? rec - which : rec), 48u);
+      asm volatile("" : "+v"(at));
+      pp = (const float4 *)(const RT_LDS float4 *)(uintptr_t)at + (PAIR ? 3 * which : 0);
+    }
     qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2);
     present = !(__float_as_int(qc.y) & TRIPTS_ABSENT);
   } else {  // a list too long for the staging: per-lane gather of 64 bytes (L1 / L2 resident)
@@ -136,6 +146,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   // records come from LDS when the list was short enough to be staged (s_tris), else from sc.tris in global memory
   constexpr bool SLAB = culls_by_slab(M);  // (kernels.h) the pair test in centre / half-extent form
   constexpr bool MINF = folds_by_min(M);   // (kernels.h) a flush of shared tests folds by one LDS minimum per ray
+  constexpr bool VOTE = trims_votes(M);    // (kernels.h) wave votes on a compare take the compare's own lane mask
   static_assert(!MINF || (!OCC && !DT && !(F & F_TEX)), "a key holds a binary32 t and the triangle's place, nothing else");
   const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
@@ -258,18 +269,18 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
         // starts on, or the one it hits), so this round of tests is as full as a round of shared tasks, and the ray
         // is in the lane's own registers -- no task word, no ray record, no result words for it.  Its test sees the
         // lane's running t_to directly, as the reference's does (utils.cu:74).
-        if (__builtin_amdgcn_ballot_w64(mask != 0u) != 0ull) {
+        if (wave_ballot_nz<VOTE>(mask) != 0ull) {
           if (mask != 0u) {
             const int bit = __builtin_ctz(mask);
             mask &= mask - 1u;
             const int rec = 2 * (pair0 + c0 + bit);  // the pair's two records: edges formed on the host (scene.hip: push_pair)
             V3 p0, e1, e2, p1, e1b, e2b;
-            (void)load_tri_pts<M>(sc, s_tris, rec, 0, p0, e1, e2);
-            const bool second = load_tri_pts<M>(sc, s_tris, rec + 1, 1, p1, e1b, e2b);
+            (void)load_tri_pts<M, true>(sc, s_tris, rec, 0, p0, e1, e2);
+            const bool second = load_tri_pts<M, true>(sc, s_tris, rec + 1, 1, p1, e1b, e2b);
             float ta = 0.f, ua = 0.f, va = 0.f, tb = 0.f, ub = 0.f, vb = 0.f;
-            const bool hit_a = tri_test_flat<T>(p0, e1, e2, cross3(d, e2), o, d, t_to, ta, ua, va, det_safe);
+            const bool hit_a = tri_test_flat<T, VOTE>(p0, e1, e2, cross3(d, e2), o, d, t_to, ta, ua, va, det_safe);
             bool hit_b = false;
-            if (second) hit_b = tri_test_flat<T>(p1, e1b, e2b, cross3(d, e2b), o, d, t_to, tb, ub, vb, det_safe) && !hit_a;  // parallelogram.cu:33
+            if (second) hit_b = tri_test_flat<T, VOTE>(p1, e1b, e2b, cross3(d, e2b), o, d, t_to, tb, ub, vb, det_safe) && !hit_a;  // parallelogram.cu:33
             const float t = hit_a ? ta : tb;
             const bool acc = (hit_a || hit_b) && (!ok || (T)t < t_to);
             ok = ok || acc;
@@ -312,11 +323,17 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             *reinterpret_cast<int4 *>(rr + 4) = make_int4(__float_as_int(d.x), __float_as_int(d.y), __float_as_int(d.z), w7);
           }
           bool todo = cnt != 0;
-          while (__builtin_amdgcn_ballot_w64(todo) != 0ull) {
+          // (VOTE) `todo` as a number, the candidates the lane has not folded yet: the wave's votes on it are then votes on a
+          // compare (wave_ballot_nz), and the vote on `now` is that mask and the compare `now` adds
+          uint32_t left = (uint32_t)cnt;
+#define RTMI_TODO_LANES (VOTE ? wave_ballot_nz<true>(left) : __builtin_amdgcn_ballot_w64(todo))
+          while (RTMI_TODO_LANES != 0ull) {
             RTMI_STAT(st.cull_iters++;)
-            const int lo_t = __builtin_amdgcn_readlane(base, __builtin_ctzll(__builtin_amdgcn_ballot_w64(todo)));
-            const bool now = todo && base + cnt - lo_t <= kListTasks(F);
-            const int n_now = __builtin_amdgcn_readlane(base + cnt, 63 - __builtin_clzll(__builtin_amdgcn_ballot_w64(now))) - lo_t;
+            const int lo_t = __builtin_amdgcn_readlane(base, __builtin_ctzll(RTMI_TODO_LANES));
+            const bool now = (VOTE ? left != 0u : todo) && base + cnt - lo_t <= kListTasks(F);
+            const unsigned long long now_lanes = VOTE ? RTMI_TODO_LANES & __builtin_amdgcn_sicmp(base + cnt - lo_t, kListTasks(F), 41)
+                                                      : __builtin_amdgcn_ballot_w64(now);
+            const int n_now = __builtin_amdgcn_readlane(base + cnt, 63 - __builtin_clzll(now_lanes)) - lo_t;
             RTMI_STAT(st.nnow_hist[(n_now - 1) >> 5 < 5 ? (n_now - 1) >> 5 : 5]++;)
             RTMI_STAT({  // trips of (c)'s loop: the most candidates any lane of this flush folds
               int pc = now ? cnt : 0;
@@ -350,7 +367,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                   const bool present = load_tri_pts<M>(sc, s_tris, 2 * (pair0 + c0 + (w & 31)) + which, which, p0, e1, e2);
                   float tt = 0.f, uu, vv;
                   bool hit = false;
-                  if (present) hit = tri_test_flat<T>(p0, e1, e2, cross3(rd, e2), ro, rd, (T)r0.w, tt, uu, vv, det_safe);
+                  if (present) hit = tri_test_flat<T, VOTE>(p0, e1, e2, cross3(rd, e2), ro, rd, (T)r0.w, tt, uu, vv, det_safe);
                   const int mine = hit ? __float_as_int(tt) : -1;  // (no accepted t has this pattern: it is a NaN's)
                   const int other = __builtin_amdgcn_update_dpp(mine, mine, 0xb1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
                   // the other triangle of my pair passed too, and it is the first (it goes before me) or the nearer second
@@ -373,7 +390,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                   ok = ok || acc;
                   t_to = acc ? (T)t : t_to;
                   win = acc ? make_id(RUN_TRIS, run.first + 2 * c0 + key.x) : win;
-                  todo = false;
+                  todo = false, left = 0u;
                 }
                 wave_lds_fence();
                 continue;
@@ -397,7 +414,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                 const bool present = load_tri_pts<M>(sc, s_tris, 2 * (pair0 + c0 + (w & 31)) + which, which, p0, e1, e2);
                 float tt = 0.f, uu = 0.f, vv = 0.f;
                 bool hit = false;  // (a lone Triangle's second record: the miss pattern, untested)
-                if (present) hit = tri_test_flat<T>(p0, e1, e2, cross3(rd, e2), ro, rd, t0_to, tt, uu, vv, det_safe);
+                if (present) hit = tri_test_flat<T, VOTE>(p0, e1, e2, cross3(rd, e2), ro, rd, t0_to, tt, uu, vv, det_safe);
                 int *res = results + (ti >> 1) * RW;
                 res[which] = hit ? __float_as_int(tt) : (int)0xffffffff;  // (a NaN pattern no t can have)
                 if (F & F_TEX) res[2 + 2 * which] = __float_as_int(uu), res[3 + 2 * which] = __float_as_int(vv);
@@ -425,11 +442,12 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
                   bv = acc ? __int_as_float(hit_a ? res[3] : res[5]) : bv;
                 }
               }
-              todo = false;
+              todo = false, left = 0u;
             }
             wave_lds_fence();
             RTMI_STAT2(st.cyc[7] += stat_now() - tc2;)
           }
+#undef RTMI_TODO_LANES
         }
         RTMI_STAT2(st.cyc[6] += stat_now() - tc1;)  // (a) + (b) + (c); [7] is (c) alone
       }

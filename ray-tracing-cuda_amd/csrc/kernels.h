@@ -90,6 +90,28 @@ constexpr bool culls_by_slab(uint32_t m) { return (m & kFastCommon) == kFastComm
 // binary32, untextured and never the occlusion engine, which is what a key of t and place alone takes for granted.
 // Every other kernel keeps the result words and the fold, and compiles to what it was.
 constexpr bool folds_by_min(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+// Three trims of the same kernels' instruction text that leave the arithmetic on every value as it is (NOTES.md, "Fast
+// list kernels: votes, 24-bit addresses, fold colours").  RTMI_TRIM is a bit per trim so that each can be built and
+// censused alone (tools/loop_census.py --extra -DRTMI_TRIM=1); the product has all three.
+//   1  trims_votes: a wave vote on a compare takes its lane mask from the compare itself (trace_helpers.h: wave_all_in,
+//      wave_ballot_nz ...) where __all / ballot send it through a register of 0 / 1 and a second compare.
+//   2  trims_mul24: the LDS address of a staged TriPts record is one 24-bit multiply-add (full rate; the 32-bit
+//      multiply issues at a quarter), kept opaque so that it is formed once (closest_hit.h: load_tri_pts).  The
+//      product's bound is asserted where the layout is made (kernels.hip: make_cfg).  The id stack's addresses keep
+//      the 32-bit multiply: with the 24-bit one the chains kernel spilled a sixth scalar (NOTES.md).
+//   4  trims_fold_rgb: the radiance fold reads a layer's colour from a table of 16 rows of 16 bytes at a fixed LDS
+//      address (kFoldRgbOff, staged from the material records), so a nibble of the id stack is its row's address after
+//      one AND (high half) or a shift and an AND (low half).  make_cfg leaves room for it in front of the id stack of
+//      every F_TRIS launch with nibble ids and a staged material table, whichever kernel that launch gets.
+// Every other kernel compiles to what it was.
+#ifndef RTMI_TRIM
+#define RTMI_TRIM 7
+#endif
+constexpr bool trims_votes(uint32_t m) { return (RTMI_TRIM & 1) && (m & kFastCommon) == kFastCommon; }
+constexpr bool trims_mul24(uint32_t m) { return (RTMI_TRIM & 2) && (m & kFastCommon) == kFastCommon; }
+constexpr bool trims_fold_rgb(uint32_t m) { return (RTMI_TRIM & 4) && (m & kFastCommon) == kFastCommon; }
+constexpr int kFoldRgbOff = 512;    // == 16 x sizeof(MatRec): behind the largest material table nibble ids can name
+constexpr int kFoldRgbBytes = 256;  // 16 rows of r, g, b, pad
 // The tasks that sent their flush through the ordered steps are counted in counters[kOrderedTasksWord], a word only
 // -DRTMI_STATS builds of mesh kernels used (rtmi_debug_counters).  closest_hit sees the words from [2] on.
 constexpr int kOrderedTasksWord = 16;

@@ -620,6 +620,15 @@ static LaunchCfg make_cfg(uint32_t variant, const SceneDev &sc, const FrameDev &
   lc.lds_mats = mats_in_lds && sc.n_mats <= kLdsMats ? sc.n_mats : 0;
   lc.wide_ids = sc.n_mats > 256 ? 1 : sc.n_mats <= 16 ? 2 : 0;
   size_t off = ((size_t)lc.lds_mats * sizeof(MatRec) + 15) & ~(size_t)15;
+  // The fold's colour table of the common list frame's kernels (kernels.h: trims_fold_rgb) at its fixed place, in every
+  // launch whose facts can pick them (fast_path_mode: variant F_TRIS, nibble ids, the material table staged): the id
+  // stack starts behind it.  The general kernel reads stack_off as it always did and leaves the table alone.
+  static_assert(kFoldRgbOff == 16 * sizeof(MatRec) && kFoldRgbOff % 16 == 0, "behind the largest table nibble ids can name");
+  if (variant == (uint32_t)F_TRIS && lc.wide_ids == 2 && lc.lds_mats > 0 && id_stack) off = (size_t)kFoldRgbOff + kFoldRgbBytes;
+  // The 24-bit product of the same kernels (kernels.h: trims_mul24; closest_hit.h: load_tri_pts): record index x record
+  // size of the staged TriPts table.
+  static_assert((uint64_t)(2 * kLdsPairs + 2) * sizeof(TriPts) < (1u << 24) && sizeof(TriPts) == 48,
+                "staged TriPts records: index (one pair of padding included) x 48 bytes is a 24-bit product");
   lc.stack_off = (int32_t)off;
   const size_t levels = (size_t)(fr.max_depth > 0 ? fr.max_depth : 1);
   // image-textured variants: one 32-bit word per level (material id, or the sampled texel)
@@ -844,6 +853,8 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
       const bool chains = fast == kFastChains && !probe && lc.chain_next && lc.tile_cost && fr.k_begin > 0 && d_ray_counts;
       const bool queue = fast == kFastQueue && !lc.chain_next;
       if (fast != 0u && (!lc.prio_tab || lc.lane_stride != 1 || !(chains || queue))) return hipErrorInvalidValue;
+      // ... and of the layout: the fold's colour table has its room in front of the id stack (make_cfg)
+      if (fast != 0u && lc.stack_off != kFoldRgbOff + kFoldRgbBytes) return hipErrorInvalidValue;
       // the three kernels below cull against the PairSlab table (kernels.h: culls_by_slab) and read it where the others
       // read the PairBox records (scene_dev.h: PairSlab)
       static_assert(culls_by_slab(kFastChains) && culls_by_slab(kFastQueue) && !culls_by_slab(0u), "which kernels read the slab table");

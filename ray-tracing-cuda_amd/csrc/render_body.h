@@ -21,6 +21,8 @@ __device__ __forceinline__ QueryHit resolve_hit(const SceneDev &sc, const QueryD
 
 // ================================================================== trace kernel
 // Dynamic LDS: [ material records: lds_mats * 32 B ][ id stack: max_depth * blockDim entries ]
+// (F_TRIS launches with nibble ids and staged materials: the fold's colour table, 256 B at byte kFoldRgbOff, between the
+// two -- kernels.hip: make_cfg)
 // The id stack is laid out [depth][thread] so the lanes of a wave touch consecutive
 // bytes; entries are 4 bits when there are at most 16 materials (two levels per byte, lc.wide_ids == 2:
 // half the LDS, which is what lets a sixth wave per SIMD of the list kernel in at depth 50), uint8 when
@@ -250,6 +252,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   const uint32_t n_threads = (uint32_t)lc.threads;
   const uint32_t ids_shift = !(M & PIN_NIBBLE_IDS) && lc.wide_ids == 1 ? 1u : 0u;
   const bool nibble_ids = (M & PIN_NIBBLE_IDS) || lc.wide_ids == 2;
+  // (M) the trims of the common list frame's kernels (kernels.h): votes as one compare, the fold's colour table
+  constexpr bool VOTE = trims_votes(M), FOLD_RGB = trims_fold_rgb(M);
+  static_assert(!FOLD_RGB || ((M & PIN_NIBBLE_IDS) && (M & PIN_LDS_TABLES)), "the table's rows are named by nibbles and staged with the materials");
   auto ids_offset = [&](int level) -> uint32_t {  // (nibble_ids: the byte of levels 2k and 2k + 1 is row k)
     return (uint32_t)lc.stack_off + (((uint32_t)level * n_threads + threadIdx.x) << ids_shift);
   };
@@ -292,7 +297,19 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.mats);
     uint32_t *dst = reinterpret_cast<uint32_t *>(s_mats);
     for (int w = threadIdx.x; w < lc.lds_mats * 8; w += blockDim.x) dst[w] = src[w];
+    if constexpr (FOLD_RGB) {  // the fold's table: row m = words 0..2 of material m and a zero (rows past the last: zeros)
+      uint32_t *rgb = reinterpret_cast<uint32_t *>(smem + kFoldRgbOff);
+      for (int w = threadIdx.x; w < kFoldRgbBytes / 4; w += blockDim.x)
+        rgb[w] = (w & 3) != 3 && (w >> 2) < lc.lds_mats ? src[(w >> 2) * 8 + (w & 3)] : 0u;
+    }
   }
+  // (FOLD_RGB) the colour whose row is `row16` bytes into that table: an LDS address proper, the table's place a constant
+  // of the instruction (lds_byte says why the offset is the address)
+  auto fold_rgb = [&](uint32_t row16) -> V3 {
+    typedef float f32x3 __attribute__((ext_vector_type(3)));  // (12 of the row's 16 bytes: three registers per colour in flight)
+    const f32x3 c = *(const RT_LDS f32x3 *)(uintptr_t)((uint32_t)kFoldRgbOff + row16);
+    return mk(c[0], c[1], c[2]);
+  };
   if ((F & F_BVH) && lc.lds_nodes > 0) {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.nodes);
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + lc.nodes_off);
@@ -412,7 +429,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       k_end_px = (int)(b < (uint32_t)fr.spp ? b : (uint32_t)fr.spp);
       if (k_end_px <= 0) return false;
     } else if (idx < 0 || fr.spp <= 0) {
-      out[q * 3 + 0] = 0.f, out[q * 3 + 1] = 0.f, out[q * 3 + 2] = 0.f;
+      // (the trimmed kernels: the zero is formed here, opaque to the compiler.  Left to itself it keeps three zeros for
+      // this store in registers across the whole trace loop, and with the trims' text parks them in scratch.)
+      float zero = 0.f;
+      if constexpr (VOTE || FOLD_RGB) asm volatile("" : "+v"(zero));
+      out[q * 3 + 0] = zero, out[q * 3 + 1] = zero, out[q * 3 + 2] = zero;
       if ((M & PIN_CHAINS) || ray_counts) ray_counts[q] = 0;
       return false;
     }
@@ -760,7 +781,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     // before the depth limit can end its path, so no mark outlives its ray.
     if constexpr (DEFER) {
       if (depth < 0) {
-        d = unit3_rn_twice(d);
+        d = unit3_rn_twice<VOTE>(d);
         depth &= ~kOwesBit;
       }
     }
@@ -829,7 +850,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         V3 p = o + h.t * d;  // ray_tracing.cu:32 and the materials' own `p`
         if (kind == RUN_SKY) {
           // sky.cu:9-14: Scatter false; Emit(p) = gradient on normalize(p)
-          V3 dir = unit3_rn(p);
+          V3 dir = unit3_rn<VOTE>(p);
           float tg = (float)(0.5 * ((double)dir.y + 1.0));
           float w0 = 1.0f - tg;
           result = mk(w0 * 1.0f + tg * 0.5f, w0 * 1.0f + tg * 0.7f, w0 * 1.0f + tg * 1.0f);
@@ -936,10 +957,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               if (!(dn >= 0.f)) {
                 float sum;
                 V3 s = ball_sample(rng, sum);
-                s = sampler_on_sphere(s, sum);  // l = (float)pow((double)sum, 0.5); vec /= l (lambertian.cu:25-29)
+                s = sampler_on_sphere<VOTE>(s, sum);  // l = (float)pow((double)sum, 0.5); vec /= l (lambertian.cu:25-29)
                 // normalize(S + n), then Ray's constructor (lambertian.cu:41-42) (DEFER: at the top of the loop)
                 // (STEP: normalize(S + n) alone -- the next step's Ray normalises again)
-                nd = STEP ? unit3_rn(s + nrm) : DEFER ? s + nrm : unit3_rn_twice(s + nrm);
+                nd = STEP ? unit3_rn(s + nrm) : DEFER ? s + nrm : unit3_rn_twice<VOTE>(s + nrm);
                 scattered = true;
               }
             } else if (m.kind == MAT_METAL) {  // metal.cu:12-25
@@ -952,7 +973,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 } else {
                   nd = refl;
                 }
-                if (!STEP) nd = unit3_rn(nd);  // Ray's constructor (STEP: the next step's)
+                if (!STEP) nd = unit3_rn<VOTE>(nd);  // Ray's constructor (STEP: the next step's)
                 scattered = true;
               }
             } else {  // MAT_DIELECTRIC, dielectric.cu:16-44
@@ -963,7 +984,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               bool zero = (nd.x == 0.f && nd.y == 0.f && nd.z == 0.f);
               bool nan = (nd.x != nd.x) || (nd.y != nd.y) || (nd.z != nd.z);
               scattered = !(zero || nan);
-              if (!STEP && scattered) nd = unit3_rn(nd);  // Ray's constructor (STEP: the next step's)
+              if (!STEP && scattered) nd = unit3_rn<VOTE>(nd);  // Ray's constructor (STEP: the next step's)
             }
             if constexpr (STEP) {  // the layer itself instead of its place on the stack: what the fold would read of it
               if (scattered) {
@@ -1040,26 +1061,50 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           const uint32_t step = n_threads;
           if (nibble_ids) {
             uint32_t at = ids_offset(i >= 0 ? i >> 1 : 0);
-            if (i >= 0 && !(i & 1)) {  // an even top level sits alone in the low half of its byte
-              const int m0 = lds_byte(at) & 15;
-              { const V3 a_ = lds_rgb(m0); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
-              i--, at -= step;
-            }
-            for (; i >= 3; i -= 4, at -= 2u * step) {  // i odd: bytes (i >> 1) and (i >> 1) - 1 hold levels i, i - 1 and i - 2, i - 3
-              const uint32_t b0 = lds_byte(at), b1 = lds_byte(at - step);
-              const int m0 = b0 >> 4, m1 = b0 & 15, m2 = b1 >> 4, m3 = b1 & 15;
-              const V3 a0 = lds_rgb(m0), a1 = lds_rgb(m1);
-              const V3 a2 = lds_rgb(m2), a3 = lds_rgb(m3);
-              result = mk(a0.x * result.x, a0.y * result.y, a0.z * result.z);
-              result = mk(a1.x * result.x, a1.y * result.y, a1.z * result.z);
-              result = mk(a2.x * result.x, a2.y * result.y, a2.z * result.z);
-              result = mk(a3.x * result.x, a3.y * result.y, a3.z * result.z);
-            }
-            for (; i >= 1; i -= 2, at -= step) {
-              const uint32_t b0 = lds_byte(at);
-              const int m0 = b0 >> 4, m1 = b0 & 15;
-              { const V3 a_ = lds_rgb(m0); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
-              { const V3 a_ = lds_rgb(m1); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+            if constexpr (FOLD_RGB) {
+              // the same levels, multiplications and order; a level's colour comes from the 16-byte rows of the fold's
+              // own table, where the nibble is its row's address after one AND (high half) or a shift and an AND (low
+              // half): the 32-byte material records take a mask, a shift and the addition of the array's base -- zero
+              if (i >= 0 && !(i & 1)) {
+                { const V3 a_ = fold_rgb((lds_byte(at) << 4) & 0xf0u); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+                i--, at -= step;
+              }
+              for (; i >= 3; i -= 4, at -= 2u * step) {
+                const uint32_t b0 = lds_byte(at), b1 = lds_byte(at - step);
+                const V3 a0 = fold_rgb(b0 & 0xf0u), a1 = fold_rgb((b0 << 4) & 0xf0u);
+                const V3 a2 = fold_rgb(b1 & 0xf0u), a3 = fold_rgb((b1 << 4) & 0xf0u);
+                result = mk(a0.x * result.x, a0.y * result.y, a0.z * result.z);
+                result = mk(a1.x * result.x, a1.y * result.y, a1.z * result.z);
+                result = mk(a2.x * result.x, a2.y * result.y, a2.z * result.z);
+                result = mk(a3.x * result.x, a3.y * result.y, a3.z * result.z);
+              }
+              for (; i >= 1; i -= 2, at -= step) {
+                const uint32_t b0 = lds_byte(at);
+                { const V3 a_ = fold_rgb(b0 & 0xf0u); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+                { const V3 a_ = fold_rgb((b0 << 4) & 0xf0u); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+              }
+            } else {
+              if (i >= 0 && !(i & 1)) {  // an even top level sits alone in the low half of its byte
+                const int m0 = lds_byte(at) & 15;
+                { const V3 a_ = lds_rgb(m0); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+                i--, at -= step;
+              }
+              for (; i >= 3; i -= 4, at -= 2u * step) {  // i odd: bytes (i >> 1) and (i >> 1) - 1 hold levels i, i - 1 and i - 2, i - 3
+                const uint32_t b0 = lds_byte(at), b1 = lds_byte(at - step);
+                const int m0 = b0 >> 4, m1 = b0 & 15, m2 = b1 >> 4, m3 = b1 & 15;
+                const V3 a0 = lds_rgb(m0), a1 = lds_rgb(m1);
+                const V3 a2 = lds_rgb(m2), a3 = lds_rgb(m3);
+                result = mk(a0.x * result.x, a0.y * result.y, a0.z * result.z);
+                result = mk(a1.x * result.x, a1.y * result.y, a1.z * result.z);
+                result = mk(a2.x * result.x, a2.y * result.y, a2.z * result.z);
+                result = mk(a3.x * result.x, a3.y * result.y, a3.z * result.z);
+              }
+              for (; i >= 1; i -= 2, at -= step) {
+                const uint32_t b0 = lds_byte(at);
+                const int m0 = b0 >> 4, m1 = b0 & 15;
+                { const V3 a_ = lds_rgb(m0); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+                { const V3 a_ = lds_rgb(m1); result = mk(a_.x * result.x, a_.y * result.y, a_.z * result.z); }
+              }
             }
           } else {
             uint32_t at = ids_offset(i >= 0 ? i : 0);

@@ -51,6 +51,34 @@ __device__ __forceinline__ float sqrt_rn_core(float x) {
   const float d = __builtin_fmaf(-g, g, x);
   return __builtin_fmaf(d, h, g);
 }
+// Wave votes on a compare.  __all(a >= b) and ballot(m != 0) compile to the compare, a v_cndmask_b32 of 0 / 1 on its
+// lane mask and a v_cmp_ne_u32 of that register against zero (with the wait state between them): the mask the first
+// compare wrote is the answer already.  With ONE (kernels.h: trims_votes) the vote is spelt as the compare intrinsic,
+// whose result IS the lane mask -- zero in lanes that are switched off -- and the rest is scalar.  A vote decides
+// wave-uniform control flow only, so no value changes; without ONE every helper is the spelling it replaces.
+// (The predicate numbers are LLVM's: FCMP_OGE 3, FCMP_OLT 4, FCMP_UGE 11, FCMP_ULT 12, ICMP_NE 33, ICMP_SLE 41.)
+template <bool ONE>
+__device__ __forceinline__ unsigned long long wave_ballot_nz(uint32_t v) {  // the lanes whose v is not zero
+  if constexpr (ONE) return __builtin_amdgcn_uicmp(v, 0u, 33);
+  else return __builtin_amdgcn_ballot_w64(v != 0u);
+}
+template <bool ONE>
+__device__ __forceinline__ bool wave_all_in(float x, float lo, float hi) {  // lo <= x < hi in every lane that is on
+  // (ONE) no lane has !(x >= lo) or !(x < hi): the unordered compares, true for a NaN as the negations are
+  if constexpr (ONE) return (__builtin_amdgcn_fcmpf(x, lo, 12) | __builtin_amdgcn_fcmpf(x, hi, 11)) == 0ull;
+  else return __all(x >= lo && x < hi);
+}
+template <bool ONE>
+__device__ __forceinline__ bool wave_all_ge(float x, float lo) {  // x >= lo in every lane that is on
+  if constexpr (ONE) return __builtin_amdgcn_fcmpf(x, lo, 12) == 0ull;
+  else return __all(x >= lo);
+}
+template <bool ONE>
+__device__ __forceinline__ bool wave_all_lt(float x, float hi) {  // x < hi in every lane that is on
+  if constexpr (ONE) return __builtin_amdgcn_fcmpf(x, hi, 11) == 0ull;
+  else return __all(x < hi);
+}
+
 // sqrtf(x), wave-cooperative: the short form when every lane's operand is inside its domain.
 #ifndef RTMI_OPT_SQRT
 #define RTMI_OPT_SQRT 1
@@ -58,9 +86,10 @@ __device__ __forceinline__ float sqrt_rn_core(float x) {
 #ifndef RTMI_OPT_DIV3
 #define RTMI_OPT_DIV3 1
 #endif
+template <bool ONE = false>
 __device__ __forceinline__ float sqrt_rn(float x) {
 #if RTMI_OPT_SQRT
-  if (__all(x >= SQRT_RN_LO && x < SQRT_RN_HI)) return sqrt_rn_core(x);
+  if (wave_all_in<ONE>(x, SQRT_RN_LO, SQRT_RN_HI)) return sqrt_rn_core(x);
 #endif
   return sqrtf(x);
 }
@@ -84,16 +113,17 @@ __device__ __forceinline__ float div_rn_core(float a, float b, float y) {
 // multiples of 2^-24 in [-1, 1] (rng_pm1_of), sum = x*x + y*y + z*z <= 1 + 2^-23.  One wave-uniform domain check for
 // the square root and the three quotients: sum >= 2^-80 (false only for the point (0, 0, 0), probability 2^-72,
 // which takes the IEEE forms with the rest of its wave); then l >= 2^-40 and every nonzero |coordinate| >= 2^-24.
+template <bool ONE = false>
 __device__ __forceinline__ V3 sampler_on_sphere(V3 a, float sum) {
 #if RTMI_OPT_DIV3
-  if (__all(sum >= 0x1p-80f)) {
+  if (wave_all_ge<ONE>(sum, 0x1p-80f)) {
     const float l = sqrt_rn_core(sum);
     const float y = rcp_rn(l);
     return mk(div_rn_core(a.x, l, y), div_rn_core(a.y, l, y), div_rn_core(a.z, l, y));
   }
   const float l = sqrtf(sum);
 #else
-  const float l = sqrt_rn(sum);
+  const float l = sqrt_rn<ONE>(sum);
 #endif
   return mk(a.x / l, a.y / l, a.z / l);
 }
@@ -101,12 +131,13 @@ __device__ __forceinline__ V3 sampler_on_sphere(V3 a, float sum) {
 // glm::normalize = v * (1 / sqrt(v.v)) (vec.h: unit3) with the reciprocal taken by rcp_rn: a
 // positive normal square root always lies inside rcp_rn's domain (2^-75 < sqrt(x) < 2^64); a
 // zero, NaN or infinite one sends the whole wave through the division.
+template <bool ONE = false>
 __device__ __forceinline__ V3 unit3_rn(V3 v) {
   const float dd = dot3(v, v);
   float inv;
 #if RTMI_OPT_SQRT
   // one wave-uniform check for both short forms: 2^-100 <= v.v < 2^100 puts the square root inside rcp_rn's domain
-  if (__all(dd >= SQRT_RN_LO && dd < SQRT_RN_HI)) {
+  if (wave_all_in<ONE>(dd, SQRT_RN_LO, SQRT_RN_HI)) {
     inv = rcp_rn(sqrt_rn_core(dd));
   } else {
     inv = 1.0f / sqrtf(dd);
@@ -128,17 +159,18 @@ __device__ __forceinline__ V3 unit3_rn(V3 v) {
 // for the camera rays it has just formed and the Lambertian directions the iteration before left raw, in one issue.
 // A pure function of v: the wave-uniform check only picks between two forms that both round correctly, so the lanes
 // that share a call do not matter to any of them.
+template <bool ONE = false>
 __device__ __forceinline__ V3 unit3_rn_twice(V3 v) {
 #if RTMI_OPT_SQRT
   const float dd = dot3(v, v);
-  if (__all(dd >= SQRT_RN_LO && dd < SQRT_RN_HI)) {
+  if (wave_all_in<ONE>(dd, SQRT_RN_LO, SQRT_RN_HI)) {
     const V3 u = v * rcp_rn(sqrt_rn_core(dd));
     return u * rcp_rn(sqrt_rn_core(dot3(u, u)));
   }
   const V3 u = v * (1.0f / sqrtf(dd));
   return u * (1.0f / sqrtf(dot3(u, u)));
 #else
-  return unit3_rn(unit3_rn(v));
+  return unit3_rn<ONE>(unit3_rn<ONE>(v));
 #endif
 }
 
@@ -174,7 +206,8 @@ __device__ __forceinline__ bool tri_test(V3 p0, V3 e1, V3 e2, V3 o, V3 d, T t_to
 // `det_safe` (wave-uniform, SceneDev::det_safe): the scene's edges bound |det| below rcp_rn's limit for every
 // unit direction, so no lane can need the division (a NaN direction gives NaN either way) and the wave-wide
 // check -- a vector compare the scalar branch has to wait for -- is skipped.
-template <typename T>
+// ONE (kernels.h: trims_votes): the wave-wide check as one compare (wave_all_lt).
+template <typename T, bool ONE = false>
 __device__ __forceinline__ bool tri_test_flat(V3 p0, V3 e1, V3 e2, V3 pvec, V3 o, V3 d, T t_to, float &t, float &u,
                                               float &v, bool det_safe = false) {
   float det = dot3(e1, pvec);
@@ -183,7 +216,7 @@ __device__ __forceinline__ bool tri_test_flat(V3 p0, V3 e1, V3 e2, V3 pvec, V3 o
   // for the others rcp_rn is the IEEE quotient unless some |det| >= 2^126 (or NaN), in which
   // case the whole wave divides.
   float inv;
-  if (det_safe || __all(fabsf(det) < RCP_RN_LIMIT)) {
+  if (det_safe || wave_all_lt<ONE>(fabsf(det), RCP_RN_LIMIT)) {
     inv = rcp_rn(det);
   } else {
     inv = 1.0f / det;
