@@ -602,6 +602,103 @@ int rtmi_bounce_list(const rtmi_scene *s, int64_t n, const uint32_t *d_list /* n
                      float *d_emitted, float *d_attenuation, rtmi_hit *d_hits /* nullable */,
                      uint32_t *d_steps /* nullable */, unsigned long long *d_work, void *stream);
 
+/* ----------------------------------------------------------- path advance --
+ * A wavefront render that stays full.  The loop of "camera rays" below renders one sample of every pixel at a time:
+ * max_depth steps on a list that drains, a fold, an add, and only then the next camera rays.  rtmi_path_advance finishes
+ * the paths that have ended and refills them IN PLACE with their pixel's next camera ray, so every step of the loop
+ *     advance(identity list);  compact;  repeat { rtmi_bounce_list(list);  rtmi_path_advance(the same list);
+ *                                                 rtmi_path_compact(from that list) }  until the compaction's count is 0
+ * runs on a list of paths that all have work.  Added without a version change: a caller detects it by the symbol
+ * rtmi_path_advance.  Every other entry is what it was.
+ *
+ * The call runs after each rtmi_bounce_list of the loop, on that step's list, and once before the first step (on the
+ * identity list) to start the paths.  Its arguments travel in a size-checked struct:
+ *   - s: committed; only its camera is read, by value at enqueue time as rtmi_camera_rays reads it.  f: the frame, with
+ *     post_process == 0;  items = rtmi_frame_work_items(f) is the n of every array, all indexed by work item, tile-major.
+ *   - proj (nullable: RTMI_PROJ_CAMERA), d_budget (nullable: f->spp everywhere): as rtmi_camera_rays and
+ *     rtmi_render_budget take them.
+ *   - (d_list, n_list, d_count): exactly rtmi_bounce_list's candidates.  A null list is the identity (then
+ *     n_list <= items); an entry >= items is dropped before anything is addressed with it; the entries are distinct.
+ *   - d_origins, d_dirs float[items][3];  d_states the render's layout, RTMI_STATE_WORDS planes of stride items;
+ *     d_steps uint32[items]: the arrays rtmi_bounce_list steps.
+ *   - d_emitted, d_attenuation float[items][3]: ONE layer, the same one handed to every rtmi_bounce_list of the loop.
+ *   - d_emitted_stack, d_attenuation_stack float[max_depth][items][3]: each path's own layers.  Neither read nor written
+ *     when max_depth == 0, and may then be null.
+ *   - d_cursor uint32[items][2], zeroed by the caller before a render.  Word 0: the low 31 bits k = samples started, bit
+ *     31 F = a path is in flight.  Word 1: P = the layers of that path on the stacks.
+ *   - d_sum, d_sq (nullable), d_samples, d_ray_counts (nullable): rtmi_render_budget's, and they accumulate as there.
+ *   - d_counts (nullable; device, three unsigned long long): [0] += samples finished, [1] += the closest-hit queries of the
+ *     finished samples, [2] += camera rays made.  One atomic per wave and counter, after a wave reduction.
+ *
+ * The rule for candidate q, in binary32 with every operation rounded on its own (no fused multiply-add):
+ *   1. PADDING.  rtmi_frame_pixel_of(f, q) < 0: d_dirs[q] becomes three +0.0f; nothing else of the item is read or written.
+ *   2. Otherwise b = min(d_budget ? d_budget[q] : spp, spp).
+ *   3. PUSH.  If F and d_steps[q] == P + 1 -- the step just made stepped the path -- d_emitted[q] and d_attenuation[q] are
+ *      copied to layer P of the stacks, then P += 1.  The copy happens only while P < max_depth, so every access stays in
+ *      bounds whatever the caller did to d_steps.
+ *   4. LOOP, at most b - k + 1 times (it never waits on memory):
+ *      FINISH, if F.  The path is finished when its ray is not live (rtmi_path_compact's predicate) or when
+ *      d_steps[q] >= max_depth; if it is not finished, the loop stops: the next step steps it.  Finished, with
+ *      c = min(d_steps[q], max_depth):
+ *        - radiance x = rtmi_path_fold's rule over the item's layers 0 .. c - 1 and d_dirs[q]: a zero vector is an ended
+ *          path, start from E[c-1]; otherwise start from 0;
+ *        - queries = 0 for a fresh path (c == 0) whose ray is not live -- rtmi_trace leaves such a ray out --, otherwise
+ *          c + (d_dirs[q] is not the zero vector ? 1 : 0);
+ *        - rtmi_sample_add's additions of an active item: d_sum[q] += x;  d_sq[q] += x * x (product and sum rounded
+ *          separately);  d_samples[q] += 1;  d_ray_counts[q] += queries;
+ *        - F is cleared.
+ *      REFILL, if not F.  If k < b: the pixel's next camera ray exactly as rtmi_camera_rays makes an active item's -- the
+ *      same draws from d_states[q], advanced in place, the same projection rules, a direction normalised once -- is
+ *      written to d_origins[q], d_dirs[q];  d_steps[q] = 0, P = 0, k += 1, F is set; and the loop goes round again (a
+ *      fisheye ray outside the image circle, and any ray when max_depth == 0, finishes at once and the pixel goes on to
+ *      its next sample in the same call).  Otherwise d_dirs[q] becomes three +0.0f and the loop stops: the next compaction
+ *      drops the item for good.
+ *   5. The cursor is written back.  An item that is not a candidate keeps every word.
+ *
+ * What follows from the rule:
+ *   - After a call every candidate pixel either holds a live in-flight ray or has no samples left and a zero direction,
+ *     so *d_count_out == 0 from the following rtmi_path_compact means the render is complete.  The call itself never
+ *     synchronises with the host.
+ *   - From a zeroed cursor, zeroed d_steps and zeroed d_dirs the loop above is bit for bit
+ *     rtmi_render_budget(s, f, d_budget, ...) in sums, second moments, sample counts, ray counts and final states -- a
+ *     pixel's samples are one serial chain on one RNG state, and the loop keeps that order per pixel -- and so, from zeroed
+ *     accumulators, rtmi_render with post_process = 0.  The one exception is rtmi_bounce's documented bad scattered ray:
+ *     it ends the sample as an alive path of c steps, exactly as a fold over rtmi_bounce's steps takes it.
+ *   - Between two steps the caller holds every path's vertex (d_hits of the step), at whatever depth each path is.
+ *   - An ascending list -- what rtmi_path_compact makes from the identity -- makes the layer reads and writes coalesced.
+ *   - Next-event estimation inside this loop is not offered: rtmi_direct_sample takes ONE step number per call and tells
+ *     "stepped by this step" from d_steps[i] == step + 1, and here the paths of a list are at different depths.
+ *   - Memory per work item beside the render's: 24 (rays) + 4 (steps) + 24 (the layer) + 8 (cursor) + 24 max_depth bytes.
+ *
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call for a null scene, a bad frame, null args, a wrong
+ * args->size or a non-zero args->reserved, a bad projection (as rtmi_camera_rays), post_process != 0, n_list negative or
+ * above 2^31 - 1, a null d_list with n_list > items, a null required array with n_list > 0 (d_budget, d_list, d_count,
+ * d_sq, d_ray_counts, d_counts, proj are the optional ones; the stacks are required when max_depth > 0), an uncommitted
+ * scene; RTMI_ERR_DEPTH for max_depth outside [0, RTMI_MAX_DEPTH]; then RTMI_ERR_INVALID when the current device is not
+ * the scene's.  n_list == 0 or items == 0 launches nothing. */
+struct rtmi_projection;
+typedef struct rtmi_path_advance_args {
+  int32_t size;      /* sizeof(rtmi_path_advance_args) of the caller: must match the library's */
+  int32_t reserved;  /* 0 */
+  const struct rtmi_projection *proj; /* nullable: RTMI_PROJ_CAMERA */
+  const uint32_t *d_budget;           /* nullable */
+  const uint32_t *d_list;             /* nullable: the identity */
+  int64_t n_list;
+  const uint32_t *d_count;            /* nullable */
+  float *d_origins, *d_dirs;
+  void *d_states;
+  uint32_t *d_steps;
+  const float *d_emitted, *d_attenuation;
+  float *d_emitted_stack, *d_attenuation_stack; /* null only with max_depth == 0 */
+  uint32_t *d_cursor;
+  float *d_sum;
+  float *d_sq;                        /* nullable */
+  uint32_t *d_samples;
+  uint32_t *d_ray_counts;             /* nullable */
+  unsigned long long *d_counts;       /* nullable */
+} rtmi_path_advance_args;
+int rtmi_path_advance(const rtmi_scene *s, const rtmi_frame *f, const rtmi_path_advance_args *args, void *stream);
+
 /* ----------------------------------------------------------------- direct --
  * Next-event estimation for wavefront paths: a light table made at rtmi_scene_commit, one step that samples it, and a fold
  * that knows the extra term.  A loop of rtmi_bounce_list, rtmi_direct_sample, rtmi_occluded and one rtmi_path_fold_direct

@@ -3,17 +3,12 @@
 // rtmi_trace between them, once per sample, the two compose bit for bit to rtmi_render_budget.  Every binary32 + - * below
 // is one operation: the file is compiled without contraction like the rest of the library.
 #pragma once
-// (included by kernels.hip inside namespace rtmi, after trace_helpers.h: rng_01, rng_range, unit3_rn)
+// (included by kernels.hip inside namespace rtmi, after path_shared.h: camera_ray)
 
-enum : int32_t { PROJ_CAMERA = 0, PROJ_ORTHOGRAPHIC = 1, PROJ_EQUIRECT = 2, PROJ_FISHEYE = 3 };  // RTMI_PROJ_*
-
-// The camera rides beside CameraDev, not in it: the render's argument block is sized by CameraDev.
+// The camera rides beside CameraDev, not in it (path_shared.h: CameraProj, PROJ_*).
 struct CameraRaysArgs {
   FrameDev fr;
-  CameraDev cam;
-  V3 w;                    // the camera frame's third axis (kinds 1..3)
-  int32_t kind;            // PROJ_*
-  float fov;               // PROJ_FISHEYE: the full angle of the image circle
+  CameraProj proj;
   uint32_t sample;
   const uint32_t *budget;  // nullable: every pixel has fr.spp
   uint32_t *states;        // RTMI_STATE_WORDS planes of uint32[items]
@@ -50,54 +45,7 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs a) {
     Rng rng;
     rng.d = a.states[0 * n + q], rng.v0 = a.states[1 * n + q], rng.v1 = a.states[2 * n + q];
     rng.v2 = a.states[3 * n + q], rng.v3 = a.states[4 * n + q], rng.v4 = a.states[5 * n + q];
-    const int i = (int)(idx / a.fr.width), j = (int)(idx % a.fr.width);
-    // The render's jitter (render_body.h, "ray_tracing.cu:68-74 + camera.cu:57-70"), restated: one function for both
-    // changed the instructions of thirteen trace-loop kernels, so the render keeps its source.  Its
-    // binary32 form for power-of-two frames is proven equal to this one bit for bit there
-    // (tests/test_host_logic.py::test_jitter_in_binary32_for_power_of_two_frames), so the binary64 form serves every frame.
-    const float r1 = rng_01(rng);
-    const float r2 = rng_01(rng);
-    double x = ((double)r1 + (double)j) / (double)a.fr.width;
-    double y = ((double)r2 + (double)(a.fr.height - i)) / (double)a.fr.height;  // (quirk g1: H - i)
-    x = 2 * x - 1, y = 2 * y - 1;
-    x = (x + 1) / 2, y = (y + 1) / 2;
-    const float xf = (float)x, yf = (float)y;
-    const V3 target = a.cam.llc + xf * a.cam.horizontal + yf * a.cam.vertical;
-    o = a.cam.position;
-    if (a.kind == PROJ_CAMERA) {
-      if (a.cam.defocus) {  // camera.cu:63-65,74-77
-        const float ox = rng_range(0.f, a.cam.lens_radius, rng);
-        const float oy = rng_range(0.f, a.cam.lens_radius, rng);
-        o = a.cam.position + a.cam.u * ox + a.cam.v * oy;
-      }
-      d = unit3_rn(target - o);  // RayAt's normalisation; Ray's constructor, the second, is rtmi_trace's
-    } else if (a.kind == PROJ_ORTHOGRAPHIC) {
-      o = target;
-      d = unit3_rn(-a.w);
-    } else {
-      const double ux = a.cam.u.x, uy = a.cam.u.y, uz = a.cam.u.z, vx = a.cam.v.x, vy = a.cam.v.y, vz = a.cam.v.z;
-      const double wx = a.w.x, wy = a.w.y, wz = a.w.z;
-      double cu, cv, cw;  // D = cu u + cv v - cw w
-      bool inside = true;
-      if (a.kind == PROJ_EQUIRECT) {
-        const double phi = ((double)xf - 0.5) * 6.283185307179586, theta = ((double)yf - 0.5) * 3.141592653589793;
-        cu = cos(theta) * sin(phi), cv = sin(theta), cw = cos(theta) * cos(phi);
-      } else {  // PROJ_FISHEYE, equidistant
-        const double sx = 2 * (double)xf - 1, sy = 2 * (double)yf - 1, r = sqrt(sx * sx + sy * sy);
-        inside = !(r > 1);
-        if (r == 0) {
-          cu = 0, cv = 0, cw = 1;
-        } else {
-          const double t = r * (double)a.fov / 2;
-          cu = sin(t) * (sx / r), cv = sin(t) * (sy / r), cw = cos(t);
-        }
-      }
-      if (inside) {
-        const V3 D = mk((float)((cu * ux + cv * vx) - cw * wx), (float)((cu * uy + cv * vy) - cw * wy),
-                        (float)((cu * uz + cv * vz) - cw * wz));
-        d = unit3_rn(D);
-      }  // (outside the image circle: the zero direction of an active item, which has made its two draws)
-    }
+    camera_ray(a.fr, a.proj, idx, rng, o, d);  // (path_shared.h: rtmi_path_advance makes its rays by the same function)
     a.states[0 * n + q] = rng.d, a.states[1 * n + q] = rng.v0, a.states[2 * n + q] = rng.v1;
     a.states[3 * n + q] = rng.v2, a.states[4 * n + q] = rng.v3, a.states[5 * n + q] = rng.v4;
   }
@@ -126,7 +74,7 @@ hipError_t launch_camera_rays(const FrameDev &fr, const CameraDev &cam, const fl
                               float *d_dirs, hipStream_t stream) {
   if (fr.items == 0) return hipSuccess;
   CameraRaysArgs a{};
-  a.fr = fr, a.cam = cam, a.w = mk(w[0], w[1], w[2]), a.kind = kind, a.fov = fov, a.sample = sample;
+  a.fr = fr, a.proj.cam = cam, a.proj.w = mk(w[0], w[1], w[2]), a.proj.kind = kind, a.proj.fov = fov, a.sample = sample;
   a.budget = d_budget, a.states = d_states, a.origins = d_origins, a.dirs = d_dirs;
   hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)cdiv(fr.items, 256)), dim3(256), 0, stream, a);
   return hipGetLastError();

@@ -1553,13 +1553,9 @@ static bool camera_frame_orthonormal(const V3 &u, const V3 &v, const V3 &w) {
   return true;
 }
 
-int rtmi_camera_rays(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_projection *proj, const uint32_t *d_budget,
-                     uint32_t sample, void *d_states, float *d_origins, float *d_dirs, void *stream) {
+// What rtmi_camera_rays and rtmi_path_advance check of their projection on scene s, without a HIP call.
+static int check_projection(const rtmi_projection *proj, const Scene *s, int *kind_out, float *fov_out) {
   static_assert(sizeof(rtmi_projection) == 16, "rtmi_projection is 16 bytes");
-  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  FrameDev d;
-  int rc = budget_frame(f, d_states && d_origins && d_dirs, "null state, origin or direction array", &d);
-  if (rc) return rc;
   int kind = RTMI_PROJ_CAMERA;
   float fov = 0.f;
   if (proj) {
@@ -1572,10 +1568,23 @@ int rtmi_camera_rays(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_proje
     if (kind == RTMI_PROJ_FISHEYE && !(std::isfinite(fov) && fov > 0.f && fov <= 6.283185307179586f))
       return fail(RTMI_ERR_INVALID, "rtmi_projection.fov of a fisheye must be finite, above 0 and at most 2 pi");
   }
-  const Scene *s = S(sp);
   if (kind != RTMI_PROJ_CAMERA && !(s->has_camera && camera_frame_orthonormal(s->cam.u, s->cam.v, s->cam_w)))
     return fail(RTMI_ERR_INVALID, "this projection needs a camera whose u, v, w are finite and orthonormal "
                                   "(rtmi_camera_raw installs none)");
+  *kind_out = kind, *fov_out = fov;
+  return RTMI_OK;
+}
+
+int rtmi_camera_rays(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_projection *proj, const uint32_t *d_budget,
+                     uint32_t sample, void *d_states, float *d_origins, float *d_dirs, void *stream) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  FrameDev d;
+  int rc = budget_frame(f, d_states && d_origins && d_dirs, "null state, origin or direction array", &d);
+  if (rc) return rc;
+  int kind = RTMI_PROJ_CAMERA;
+  float fov = 0.f;
+  const Scene *s = S(sp);
+  if ((rc = check_projection(proj, s, &kind, &fov))) return rc;
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   if ((rc = scene_device(s, nullptr))) return rc;
   // the camera is the scene's host record now, by value: a later rtmi_camera_update does not reach this launch
@@ -1593,6 +1602,46 @@ int rtmi_sample_add(const rtmi_frame *f, const uint32_t *d_budget, uint32_t samp
   if (rc) return rc;
   HIP_TRY(launch_sample_add(d, d_budget, sample, d_radiance, d_trace_counts, d_sum, d_sq, d_samples, d_ray_counts,
                             (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ ended paths finished and refilled in place
+// The arguments first, without a HIP call, then the scene's device (as rtmi_camera_rays and rtmi_bounce_list refuse).
+int rtmi_path_advance(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_path_advance_args *a, void *stream) {
+  static_assert(sizeof(rtmi_path_advance_args) == 160, "rtmi_path_advance_args is 160 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  FrameDev d;
+  if (!make_frame(f, &d)) return fail(RTMI_ERR_INVALID, frame_why("bad frame"));
+  if (!a) return fail(RTMI_ERR_INVALID, "null rtmi_path_advance_args");
+  if (a->size != (int32_t)sizeof(rtmi_path_advance_args) || a->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_path_advance_args.size does not match this library, or reserved is not 0");
+  const Scene *s = S(sp);
+  int kind = RTMI_PROJ_CAMERA;
+  float fov = 0.f;
+  int rc = check_projection(a->proj, s, &kind, &fov);
+  if (rc) return rc;
+  if (d.post) return fail(RTMI_ERR_INVALID, "post_process must be 0: per-pixel sample counts have no uniform division (rtmi_resolve)");
+  if ((rc = check_depth(d.max_depth))) return rc;
+  if ((rc = check_list(d.items, a->d_list, a->n_list))) return rc;
+  if (a->n_list > 0 && !(a->d_origins && a->d_dirs && a->d_states && a->d_steps && a->d_emitted && a->d_attenuation &&
+                         a->d_cursor && a->d_sum && a->d_samples))
+    return fail(RTMI_ERR_INVALID, "null ray, state, step, emitted, attenuation, cursor, sum or sample-count array");
+  if (a->n_list > 0 && d.max_depth > 0 && !(a->d_emitted_stack && a->d_attenuation_stack))
+    return fail(RTMI_ERR_INVALID, "null emitted or attenuation stack with max_depth > 0");
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  const bool work = d.items > 0 && a->n_list > 0;
+  int n_cu = 0;
+  if ((rc = scene_device(s, work ? &n_cu : nullptr))) return rc;
+  if (!work) return RTMI_OK;
+  AdvanceCall c{};
+  c.budget = a->d_budget, c.list = a->d_list, c.count = a->d_count, c.n_list = a->n_list;
+  c.origins = a->d_origins, c.dirs = a->d_dirs, c.states = reinterpret_cast<uint32_t *>(a->d_states), c.steps = a->d_steps;
+  c.emitted = a->d_emitted, c.attenuation = a->d_attenuation;
+  c.emitted_stack = a->d_emitted_stack, c.attenuation_stack = a->d_attenuation_stack, c.cursor = a->d_cursor;
+  c.sum = a->d_sum, c.sq = a->d_sq, c.samples = a->d_samples, c.ray_counts = a->d_ray_counts, c.counts = a->d_counts;
+  // the camera is the scene's host record now, by value: a later rtmi_camera_update does not reach this launch
+  const float w[3] = {s->cam_w.x, s->cam_w.y, s->cam_w.z};
+  HIP_TRY(launch_path_advance(d, s->dev.cam, w, kind, fov, c, n_cu, (hipStream_t)stream));
   return RTMI_OK;
 }
 

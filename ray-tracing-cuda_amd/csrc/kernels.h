@@ -319,6 +319,23 @@ hipError_t launch_camera_rays(const FrameDev &fr, const CameraDev &cam, const fl
 hipError_t launch_sample_add(const FrameDev &fr, const uint32_t *d_budget, uint32_t sample, const float *d_radiance,
                              const uint32_t *d_trace_counts, float *d_sum, float *d_sq, uint32_t *d_samples,
                              uint32_t *d_ray_counts, hipStream_t stream);
+// Ended paths finished and refilled in place (rtmi_path_advance; advance.hip, advance_body.h): the caller's arrays as
+// include/rtmi.h names them, every pointer checked by capi.hip.  The camera and the projection as launch_camera_rays takes
+// them.  n_list >= 1.
+struct AdvanceCall {
+  const uint32_t *budget, *list, *count;  // nullable
+  int64_t n_list;
+  float *origins, *dirs;
+  uint32_t *states, *steps;
+  const float *emitted, *attenuation;
+  float *emitted_stack, *attenuation_stack;  // null only with max_depth == 0
+  uint32_t *cursor;
+  float *sum, *sq;                 // sq nullable
+  uint32_t *samples, *ray_counts;  // ray_counts nullable
+  unsigned long long *counts;      // nullable
+};
+hipError_t launch_path_advance(const FrameDev &fr, const CameraDev &cam, const float w[3], int kind, float fov,
+                               const AdvanceCall &c, int n_cu, hipStream_t stream);
 #ifdef RTMI_STATS
 hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnostic builds only
 #endif

@@ -58,16 +58,7 @@
 namespace rtmi {
 
 // ------------------------------------------------------------------ frame math
-__host__ __device__ __forceinline__ int64_t frame_pixel_of_rank(const FrameDev &fr, int rank, int64_t q) {
-  int64_t lt = q >> 6;
-  int w = (int)(q & 63);
-  int64_t gt = lt * fr.world + rank;
-  if (gt >= fr.n_tiles) return -1;
-  int ty = (int)(gt / fr.tiles_x), tx = (int)(gt % fr.tiles_x);
-  int i = ty * 8 + (w >> 3), j = tx * 8 + (w & 7);
-  if (i >= fr.height || j >= fr.width) return -1;
-  return (int64_t)i * fr.width + j;
-}
+#include "frame_math.h"
 
 int64_t frame_pixel_of(const FrameDev &fr, int rank, int64_t q) { return frame_pixel_of_rank(fr, rank, q); }
 
@@ -119,6 +110,7 @@ __global__ __launch_bounds__(256) void rng_init_kernel(uint64_t seed, FrameDev f
 }
 
 #include "trace_helpers.h"
+#include "path_shared.h"
 #include "mesh_search.h"
 #include "closest_hit.h"
 #include "render_body.h"
@@ -1114,18 +1106,7 @@ struct CompactArgs {
   const uint32_t *count_in;     // nullable: a device word that cuts the candidates short
   uint32_t n, n_list;
 };
-// Whether a step would step the ray (ro, rd): finite, and a direction that Ray's constructor (ray.cu:8-10) normalises to a
-// finite non-zero vector.  A RESTATEMENT of the predicate in render_body.h's take_item, line for line: with one
-// __device__ function called from both sites, all eight trace_kernel<F> and all eight bounce_kernel<F> compiled to other
-// instructions (and bounce_kernel<23> spilled four more SGPRs), and the existing kernels are not this feature's to
-// change.  tests/test_gpu_bounce_list.py holds the two to each other: a compaction's count is the next step's d_work[1].
-__device__ __forceinline__ bool live_ray(V3 ro, V3 rd) {
-  bool live = finite3(ro) && finite3(rd) && (rd.x != 0.f || rd.y != 0.f || rd.z != 0.f);
-  V3 nd = splat(0.f);
-  if (live) nd = unit3_rn(rd);
-  live = live && finite3(nd) && (nd.x != 0.f || nd.y != 0.f || nd.z != 0.f);
-  return live;
-}
+// (live_ray, whether a step would step a ray: path_shared.h, which rtmi_path_advance's unit includes too)
 // Entry e of the candidates: its path, and whether the next step would step it.
 __device__ __forceinline__ bool compact_live(const CompactArgs &a, uint32_t e, uint32_t end, uint32_t &path) {
   path = 0u;
@@ -1243,17 +1224,8 @@ __global__ __launch_bounds__(256) void path_fold_kernel(int64_t n, uint32_t laye
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= n) return;
   const uint32_t s = steps[q];
-  int k = (int)(s < layers ? s : layers) - 1;
-  V3 r = splat(0.f);
-  if (k >= 0 && dirs[q * 3 + 0] == 0.f && dirs[q * 3 + 1] == 0.f && dirs[q * 3 + 2] == 0.f) {  // the path ended in layer k
-    const float *e = emitted + ((int64_t)k * n + q) * 3;
-    r = mk(e[0], e[1], e[2]);
-    k--;
-  }
-  for (; k >= 0; k--) {
-    const float *e = emitted + ((int64_t)k * n + q) * 3, *a = attenuation + ((int64_t)k * n + q) * 3;
-    r = mk(__fadd_rn(e[0], __fmul_rn(a[0], r.x)), __fadd_rn(e[1], __fmul_rn(a[1], r.y)), __fadd_rn(e[2], __fmul_rn(a[2], r.z)));
-  }
+  const bool ended = dirs[q * 3 + 0] == 0.f && dirs[q * 3 + 1] == 0.f && dirs[q * 3 + 2] == 0.f;
+  const V3 r = fold_layers(emitted, attenuation, n, q, (int)(s < layers ? s : layers), ended);  // (path_shared.h)
   radiance[q * 3 + 0] = r.x, radiance[q * 3 + 1] = r.y, radiance[q * 3 + 2] = r.z;
 }
 hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,

@@ -139,9 +139,7 @@ __device__ __forceinline__ void wave_priority_leave(uint32_t *tab) {
     __hip_atomic_store(tab + row * 16u + (hw & 15u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ bool finite3(V3 v) {
-  return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
-}
+// (finite3: path_shared.h)
 
 // Everything a kernel around render_body is told lives in ONE block of device memory (written by params_write_kernel,
 // stream-ordered, just before the launch) and the kernel's only argument is its address.  By-value kernel arguments are

@@ -113,6 +113,16 @@ def projection(kind="camera", fov=0.0):
     return Projection(C.sizeof(Projection), PROJECTIONS[kind], float(fov), 0)
 
 
+class PathAdvanceArgs(C.Structure):
+    """rtmi_path_advance_args of include/rtmi.h (the arrays of one rtmi_path_advance call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("proj", C.POINTER(Projection)), ("d_budget", C.c_void_p),
+                ("d_list", C.c_void_p), ("n_list", C.c_int64), ("d_count", C.c_void_p), ("d_origins", C.c_void_p),
+                ("d_dirs", C.c_void_p), ("d_states", C.c_void_p), ("d_steps", C.c_void_p), ("d_emitted", C.c_void_p),
+                ("d_attenuation", C.c_void_p), ("d_emitted_stack", C.c_void_p), ("d_attenuation_stack", C.c_void_p),
+                ("d_cursor", C.c_void_p), ("d_sum", C.c_void_p), ("d_sq", C.c_void_p), ("d_samples", C.c_void_p),
+                ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
 class DenoiseOpts(C.Structure):
     """rtmi_denoise_opts of include/rtmi.h."""
     _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
@@ -253,6 +263,7 @@ SYMBOLS = [
                                     [C.c_void_p] * 14),
     ("rtmi_path_fold_direct", C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8),
     ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
+    ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
 ]
 
 # rtmi_light of include/rtmi.h, as a numpy record (88 bytes)
@@ -1535,6 +1546,176 @@ class Renderer:
             n = int(self.budget_abandoned.item())  # (waits for the loop, as Trace.check does)
         if n:
             raise RtmiError("rtmi_trace abandoned %d mesh search(es): the sums are incomplete" % n)
+        return self
+
+    # -------------------------------------------------------------- a wavefront that stays full
+    def path_advance(self, paths, origins, directions, steps, emitted, attenuation, stacks, cursor, budget=None,
+                     projection=None, counts=None, count_rays=True):
+        """Finish the ended paths among ``paths`` and refill them in place with their pixel's next camera ray
+        (rtmi_path_advance; include/rtmi.h states the rule), enqueued on torch's current stream.
+
+        ``paths``: the ``Paths`` the last ``SceneBuilder.bounce_list`` stepped, or None for all items (the call that
+        starts a render).  ``origins`` / ``directions`` (items, 3) float32 and ``steps`` (items,) int32: the arrays the
+        steps step, with the renderer's ``states``.  ``emitted`` / ``attenuation`` (items, 3) float32: the ONE layer every
+        step writes.  ``stacks``: a pair of (max_depth, items, 3) float32 tensors, each path's own layers (None when the
+        frame's max_depth is 0).  ``cursor``: (items, 2) int32, zeroed before a render.  ``budget`` / ``projection``: as
+        ``camera_rays``.  ``counts``: an optional (3,) int64 tensor: += samples finished, their closest-hit queries, camera
+        rays made.  Finished samples are added to ``sum``, ``sq``, ``samples`` and -- with ``count_rays`` --
+        ``budget_rays`` (the buffers of ``render_budget``, zeroed on first use).  All tensors contiguous, on the
+        renderer's device.  Returns ``self``."""
+        a, keep = self._advance_args(paths, origins, directions, steps, emitted, attenuation, stacks, cursor, budget, projection,
+                                     counts, count_rays)
+        with self.torch.cuda.device(self.device):
+            _check(self.L.rtmi_path_advance(self.scene.h, C.byref(self.frame), C.byref(a), self._stream()), "rtmi_path_advance")
+        return self
+
+    def _advance_args(self, paths, origins, directions, steps, emitted, attenuation, stacks, cursor, budget, projection, counts,
+                      count_rays):
+        """The checked rtmi_path_advance_args of ``path_advance``'s arguments, and what it points into (to be kept alive)."""
+        torch = self.torch
+        n, dev, depth = self.items, self.device, int(self.frame.max_depth)
+        idx, n_list, cnt = _list_args(paths, n, dev)
+        if projection is not None and not isinstance(projection, Projection):
+            raise RtmiError("projection must be an rtmi.projection(...)")
+        for name, t in (("origins", origins), ("directions", directions), ("emitted", emitted), ("attenuation", attenuation)):
+            if not _is_buffer(t, (n, 3), dev, torch.float32):
+                raise RtmiError("%s must be a contiguous CUDA float32 tensor of shape (items, 3) on the renderer's device" % name)
+        if not _is_buffer(steps, (n,), dev, torch.int32):
+            raise RtmiError("steps must be a contiguous CUDA int32 tensor of shape (items,) on the renderer's device")
+        if not _is_buffer(cursor, (n, 2), dev, torch.int32):
+            raise RtmiError("cursor must be a contiguous CUDA int32 tensor of shape (items, 2) on the renderer's device")
+        if stacks is None:
+            stacks = (None, None)
+        if not (isinstance(stacks, (tuple, list)) and len(stacks) == 2):
+            raise RtmiError("stacks must be a pair of (max_depth, items, 3) float32 CUDA tensors, or None at max_depth 0")
+        for t in stacks:
+            if not (t is None and depth == 0) and not _is_buffer(t, (depth, n, 3), dev, torch.float32):
+                raise RtmiError("stacks must be a pair of contiguous CUDA float32 tensors of shape (max_depth, items, 3)")
+        if counts is not None and not _is_buffer(counts, (3,), dev, torch.int64):
+            raise RtmiError("counts must be a CUDA int64 tensor of shape (3,) on the renderer's device")
+        d_budget = self._budget_arg(budget)
+        self._budget_buffers()
+        val = lambda t: t.data_ptr() if t is not None else None
+        a = PathAdvanceArgs()
+        a.size, a.reserved = C.sizeof(PathAdvanceArgs), 0
+        a.proj = C.pointer(projection) if projection is not None else None
+        a.d_budget = d_budget
+        a.d_list, a.n_list, a.d_count = val(idx), n_list, val(cnt)
+        a.d_origins, a.d_dirs, a.d_states, a.d_steps = val(origins), val(directions), val(self.states), val(steps)
+        a.d_emitted, a.d_attenuation = val(emitted), val(attenuation)
+        a.d_emitted_stack, a.d_attenuation_stack = val(stacks[0]), val(stacks[1])
+        a.d_cursor = val(cursor)
+        a.d_sum, a.d_sq, a.d_samples = val(self.sum), val(self.sq), val(self.samples)
+        a.d_ray_counts = val(self.budget_rays) if count_rays else None
+        a.d_counts = val(counts)
+        return a, (paths, origins, directions, steps, emitted, attenuation, stacks, cursor, budget, projection, counts)
+
+    def render_wavefront(self, budget=None, projection=None, count_rays=True, each=None, poll=8):
+        """``render_budget(budget)`` as a wavefront that stays full, on torch's current stream: ``path_advance`` on all
+        items starts every pixel's first path, then every iteration is one ``SceneBuilder.bounce_list`` on the live paths,
+        one ``path_advance`` on the same list -- which finishes the paths that ended and gives their pixels the next
+        sample's camera ray in place -- and one ``path_compact`` from that list, two ``Paths`` ping-ponged.  Bit for bit
+        ``render_budget``'s sums, moments, sample and ray counts and states (a pixel's samples stay one serial chain on its
+        RNG state).  Its steps run on fuller lists than the per-sample loop's, but on an MI355X the whole loop is not faster
+        than ``render_rays`` or the ``trace_steps`` loop (DESIGN.md 2.16 has the figures): use it for what it holds between
+        two steps -- every path's vertex, at whatever depth -- not for speed.
+
+        ``budget``: None for the frame's spp everywhere; the largest active budget is read back once before the loop (it
+        bounds the loop).  ``projection``: an ``rtmi.projection(...)``.  ``each(iteration, result)`` gets each step's
+        ``Bounce`` (with hits, and ``result.paths`` the list it stepped) after its advance is enqueued: between two steps
+        the caller holds every path's vertex, whatever its depth.  ``poll``: the live count is read back once every
+        ``poll`` iterations, the loop's only synchronisation; the iterations enqueued after the last path has ended run on
+        an empty list and change nothing.  The loop makes at most (largest active budget) x max(max_depth, 1) + 1
+        iterations and raises ``RtmiError`` if paths are still live then.  Adds the finished samples' closest-hit queries
+        to ``rays_total``, every step's abandoned mesh searches to ``budget_abandoned`` (``check()`` raises on them) and
+        the call's counters to ``wavefront_counts`` ((3,) int64: samples finished, their queries, camera rays made);
+        ``wavefront_iterations`` is how many iterations this call enqueued.  The frame must have been made with
+        ``post=False``.  Returns ``self``: ``resolve``, ``plan``, ``resolve_variance`` and ``denoise`` follow unchanged."""
+        torch = self.torch
+        if self.frame.post_process:
+            raise RtmiError("render_wavefront needs a frame made with post=False: per-pixel sample counts have no uniform division (resolve)")
+        poll = int(poll)
+        if poll < 1:
+            raise RtmiError("poll must be at least 1")
+        self._budget_arg(budget)
+        self._budget_buffers()
+        n, dev, depth, spp = self.items, self.device, int(self.frame.max_depth), int(self.frame.spp)
+        if not 0 <= depth <= MAX_DEPTH:
+            raise RtmiError("max_depth %d outside [0, %d]" % (depth, MAX_DEPTH))
+        if getattr(self, "rays_total", None) is None:
+            self.rays_total = torch.zeros((), dtype=torch.int64, device=dev)
+        if getattr(self, "wavefront_counts", None) is None:
+            self.wavefront_counts = torch.zeros((3,), dtype=torch.int64, device=dev)
+        most = spp
+        if budget is not None:  # (the budget words are uint32: a negative int32 is a large one)
+            most = min(spp, int((budget.to(torch.int64) & 0xffffffff).max().item())) if n else 0
+        bound = most * max(depth, 1) + 1
+        self.wavefront_iterations = 0
+        with torch.cuda.device(dev):
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            origins, dirs = zeros(n, 3), zeros(n, 3)
+            steps = torch.zeros((n,), dtype=torch.int32, device=dev)
+            cursor = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+            emitted, attenuation = zeros(n, 3), zeros(n, 3)
+            stacks = None
+            if depth > 0:
+                stacks = (torch.empty((depth, n, 3), dtype=torch.float32, device=dev),
+                          torch.empty((depth, n, 3), dtype=torch.float32, device=dev))
+            queries_before = self.wavefront_counts[1].clone()
+            lists = [Paths(torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+                     for _ in range(2)]
+            # Everything an iteration passes is checked and turned into ctypes values ONCE: with them an iteration is three
+            # foreign calls, and the loop is bound by the device, not by the interpreter (DESIGN.md 2.16 has the figures).
+            L, h, fr, stream = self.L, self.scene.h, C.byref(self.frame), self.scene._stream(dev)
+            rest = (origins, dirs, steps, emitted, attenuation, stacks, cursor, budget, projection, self.wavefront_counts, count_rays)
+            start, keep = self._advance_args(None, *rest)
+            adv = [self._advance_args(p, *rest)[0] for p in lists]
+            p_o, p_d, p_st, p_steps = _ptr(origins), _ptr(dirs), _ptr(self.states), _ptr(steps)
+            p_em, p_at = _ptr(emitted), _ptr(attenuation)
+            p_idx, p_cnt = [_ptr(p.index) for p in lists], [_ptr(p.count) for p in lists]
+            scratch = torch.empty((max(L.rtmi_path_compact_scratch_bytes(n) // 4, 1),), dtype=torch.int32, device=dev)
+            p_scratch = _ptr(scratch)  # (one scratch: the compactions follow each other on one stream)
+            # the steps' work blocks: a ring, its abandoned searches summed and the ring cleared whenever it has gone round
+            ring = torch.zeros((64, TRACE_WORK_WORDS), dtype=torch.int64, device=dev)
+            p_work = [C.c_void_p(ring.data_ptr() + j * TRACE_WORK_WORDS * 8) for j in range(ring.shape[0])]
+            _check(L.rtmi_path_advance(h, fr, C.byref(start), stream), "rtmi_path_advance")
+            _check(L.rtmi_path_compact(n, p_o, p_d, None, n, None, p_idx[0], p_cnt[0], p_scratch, stream), "rtmi_path_compact")
+            def flush():  # (stream-ordered; a block no step used holds zeros)
+                self.budget_abandoned += ring[:, 0].sum()
+                ring.zero_()
+
+            it, c, cur = 0, 0, lists[0]
+            while True:
+                if each is None and it and it % len(p_work) == 0:
+                    flush()  # the ring is about to be used again from its first block
+                if it % poll == 0 or it >= bound:
+                    live = int(cur.count.item())  # (a device-to-host copy: the loop's one synchronisation)
+                    if live == 0:
+                        flush()
+                        break
+                    if it >= bound:
+                        flush()
+                        raise RtmiError("render_wavefront: %d path(s) still live after %d iterations (the bound for a "
+                                        "largest budget of %d at max_depth %d)" % (live, it, most, depth))
+                if each is None:
+                    _check(L.rtmi_bounce_list(h, n, p_idx[c], n, p_cnt[c], p_o, p_d, p_st, p_em, p_at, None, p_steps,
+                                              p_work[it % len(p_work)], stream), "rtmi_bounce_list")
+                    _check(L.rtmi_path_advance(h, fr, C.byref(adv[c]), stream), "rtmi_path_advance")
+                else:  # the step through the binding: its Bounce, hit records and a work block of its own for the hook
+                    r = self.scene.bounce_list(cur, origins, dirs, self.states, emitted=emitted, attenuation=attenuation,
+                                               hits=True, steps=steps)
+                    self.budget_abandoned += r.work[0]  # (stream-ordered)
+                    _check(L.rtmi_path_advance(h, fr, C.byref(adv[c]), stream), "rtmi_path_advance")
+                    each(it, r)
+                it += 1
+                _check(L.rtmi_path_compact(n, p_o, p_d, p_idx[c], n, p_cnt[c], p_idx[c ^ 1], p_cnt[c ^ 1], p_scratch, stream),
+                       "rtmi_path_compact")
+                c ^= 1
+                cur = lists[c]
+            cur._keep = (origins, dirs, scratch, keep)
+            self.wavefront_iterations = it
+            self.rays_total += self.wavefront_counts[1] - queries_before
+            self.wavefront_cursor, self.wavefront_paths = cursor, cur  # (what the loop left: every k == b, an empty list)
         return self
 
     def resolve_features(self):
