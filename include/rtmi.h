@@ -789,6 +789,71 @@ int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint
                           const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded, float *d_radiance,
                           void *stream);
 
+/* rtmi_direct_sample_mis.  rtmi_direct_sample with multiple importance sampling: the light a vertex samples and the light
+ * its scattered ray then finds are BOTH kept, each weighted by the balance heuristic, instead of the second being dropped.
+ * rtmi_direct_sample's estimate albedo * Le * cs * cl / d2 * scale is unbounded where a light lies close to a diffuse
+ * surface; the weighted one is at most albedo * Le.  Added without a version change: a caller detects it by the symbol
+ * rtmi_direct_sample_mis.  rtmi_direct_sample and every other entry are what they were.
+ *
+ * The weights.  At a Lambertian vertex the scattered ray has the solid-angle density cs / pi; the light sample has
+ * P_j * d2 / (cl * area_j) with P_j the light's selection probability.  scale_j = area_j / (P_j * pi), so with
+ * a = cs * cl * scale_j the ratio of the two densities is a : d2 and pi has cancelled:
+ *     the light sample's weight is d2 / (a + d2), the scattered ray's is a / (a + d2), and they sum to 1.
+ * The weighted light sample albedo * Le * (a / d2) * d2 / (a + d2) = albedo * Le * a / (a + d2).
+ *
+ * The light of a hit is the table light j with lights[j].entry == hit.entry and, for hit.kind == RTMI_HIT_PARALLELEPIPED,
+ * also lights[j].element == hit.element (the first such j); both triangles of a PARALLELOGRAM (element 0 or 1) are the one
+ * light.  A hit of any other kind than TRIANGLE, PARALLELOGRAM or PARALLELEPIPED, one with entry < 0 and one whose entry
+ * has no table light has no light.  A map from (entry, face) to j is made at rtmi_scene_commit.
+ *
+ * The arguments travel in a size-checked struct: every array and scalar of rtmi_direct_sample with the same meaning, shape
+ * and candidates, and d_carry float[n][4], 16-byte aligned: per path the scattered direction of its last sampling vertex and
+ * that vertex's N . d.  The caller allocates it once for a loop and never needs to initialise it: a word is read only from
+ * a path whose flag the call before set, which wrote it.
+ * Per candidate i, in binary32, every operation rounded on its own, sums of three as (x + y) + z, IEEE division and sqrt, in
+ * this order:
+ *   - NOT STEPPED: exactly rtmi_direct_sample's rule.  The carry keeps every word.
+ *   - WEIGH (in DROP's place): if the flag's bit 0 was set and the hit has a light j: c = d_carry[i];
+ *     cl = fabs((n_j.x c.x + n_j.y c.y) + n_j.z c.z);  t = d_hits[i].t;  d2 = t * t;  a = (c.w * cl) * scale_j;
+ *     w = (a > 0 && d2 > 0 && a + d2 < +inf) ? a / (a + d2) : +0.0f (a NaN gives +0.0f);
+ *     d_emitted[i][ch] = d_emitted[i][ch] * w where w came from the division, three +0.0f otherwise;  d_counts[1] += 1.
+ *     A flagged path whose hit has no light keeps its emission bit for bit: an emissive sphere or mesh face that shares a
+ *     table light's material is not a table light, and no vertex sampled it.
+ *   - SAMPLE: rtmi_direct_sample's condition, draws, j, flip, q, w, d2, dist, wi, cs, cl, validity, shadow ray and t_max.
+ *     Valid: a = (cs * cl) * scale_j;  g = a / (a + d2);  d_direct[i][ch] = (d_attenuation[i][ch] * emission_j[ch]) * g.
+ *     Valid or not: d_carry[i] = (d.x, d.y, d.z, (N.x d.x + N.y d.y) + N.z d.z) with d = d_dirs[i], the scattered direction as
+ *     rtmi_bounce left it, and N = d_hits[i].normal.  The flag is set and d_counts[0] += 1.
+ *   - OTHERWISE: as rtmi_direct_sample.  The carry keeps every word.
+ * The last step of a loop passes sample = 0 and only weighs.  The path states are never touched, and rtmi_path_fold_direct
+ * folds the result unchanged.  For every visible light point the two weights sum to 1, and a Metal or Dielectric vertex
+ * clears the flag, so the light it reflects arrives unweighted: the loop's radiance has rtmi_trace's expectation by the
+ * argument above.  d_counts[1] counts the emissions weighed.
+ *
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: a null scene or args, a wrong args->size, a non-zero
+ * args->reserved, every case of rtmi_direct_sample, and a null d_carry or one that is not 16-byte aligned with n_list > 0;
+ * then also when the current device is not the scene's.  n == 0 or n_list == 0 launches nothing. */
+typedef struct rtmi_direct_sample_mis_args {
+  int32_t size;      /* sizeof(rtmi_direct_sample_mis_args) of the caller: must match the library's */
+  int32_t reserved;  /* 0 */
+  int64_t n;
+  const uint32_t *d_list;             /* nullable: the identity */
+  int64_t n_list;
+  const uint32_t *d_count;            /* nullable */
+  uint32_t step;
+  int32_t sample;
+  const float *d_origins, *d_dirs;
+  const rtmi_hit *d_hits;
+  const uint32_t *d_steps;
+  float *d_emitted;
+  const float *d_attenuation;
+  void *d_light_states;
+  uint32_t *d_flags;
+  float *d_shadow_origins, *d_shadow_dirs, *d_shadow_t_max, *d_direct;
+  float *d_carry;                     /* float[n][4], 16-byte aligned */
+  unsigned long long *d_counts;       /* nullable */
+} rtmi_direct_sample_mis_args;
+int rtmi_direct_sample_mis(const rtmi_scene *s, const rtmi_direct_sample_mis_args *args, void *stream);
+
 /* rtmi_occluded_list.  rtmi_occluded for the candidates of (d_list, n_list, d_count) only: the visibility query of a loop
  * whose other steps take a live-path list, and of any caller who shoots shadow or ambient-occlusion rays from the vertices
  * rtmi_bounce_list leaves behind.  Added without a version change: a caller detects it by the symbol rtmi_occluded_list.

@@ -532,6 +532,9 @@ int rtmi_scene_commit(rtmi_scene *sp) {
     if ((rc = upload(s, cdf, &l.cdf))) return rc;
     if ((rc = upload(s, light_mats, &l.light_mats))) return rc;
     l.n_lights = (int32_t)s->lights.size(), l.n_mats = (int32_t)s->mat_recs.size();
+    std::vector<int32_t> hit_light;  // (rtmi_direct_sample_mis only)
+    build_hit_light_map(s->lights, &hit_light, &l.n_entries);
+    if ((rc = upload(s, hit_light, &l.hit_light))) return rc;
     s->ldev = l;
   }
   void *c = nullptr;
@@ -1353,11 +1356,12 @@ int rtmi_scene_lights(const rtmi_scene *sp, rtmi_light *out, int64_t n) {
   return RTMI_OK;
 }
 
-int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+// The checks and the argument block the two steps share: *work says whether anything is to be launched.
+static int direct_args(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
                        uint32_t step, int sample, const float *d_origins, const float *d_dirs, const rtmi_hit *d_hits,
                        const uint32_t *d_steps, float *d_emitted, const float *d_attenuation, void *d_light_states,
                        uint32_t *d_flags, float *d_shadow_origins, float *d_shadow_dirs, float *d_shadow_t_max, float *d_direct,
-                       unsigned long long *d_counts, void *stream) {
+                       unsigned long long *d_counts, const float *d_carry, bool mis, DirectArgs *out, int *n_cu, bool *work) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
   if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
   if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
@@ -1366,13 +1370,15 @@ int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, 
   if (n_list > 0 && !(d_origins && d_dirs && d_hits && d_steps && d_emitted && d_attenuation && d_light_states && d_flags &&
                       d_shadow_origins && d_shadow_dirs && d_shadow_t_max && d_direct))
     return fail(RTMI_ERR_INVALID, "null ray, hit, step, emitted, attenuation, light state, flag, shadow ray or direct array");
+  if (mis && n_list > 0 && (!d_carry || (reinterpret_cast<uintptr_t>(d_carry) & 15u)))
+    return fail(RTMI_ERR_INVALID, "null carry array, or one that is not 16-byte aligned");
   const Scene *s = S(sp);
   if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  const bool work = n > 0 && n_list > 0;
-  int n_cu = 0;
-  if (const int rc = scene_device(s, work ? &n_cu : nullptr)) return rc;
-  if (!work) return RTMI_OK;
-  DirectArgs a{};
+  *work = n > 0 && n_list > 0;
+  *n_cu = 0;
+  if (const int rc = scene_device(s, *work ? n_cu : nullptr)) return rc;
+  if (!*work) return RTMI_OK;
+  DirectArgs &a = *out;
   a.lt = s->ldev, a.mats = s->dev.mats;
   a.list = d_list, a.count = d_count;
   a.n = (uint32_t)n, a.n_list = (uint32_t)n_list, a.step = step, a.sample = sample != 0 ? 1u : 0u;
@@ -1381,7 +1387,43 @@ int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, 
   a.light_states = reinterpret_cast<uint32_t *>(d_light_states), a.flags = d_flags;
   a.shadow_o = d_shadow_origins, a.shadow_d = d_shadow_dirs, a.shadow_t = d_shadow_t_max, a.direct = d_direct;
   a.counts = d_counts;
+  return RTMI_OK;
+}
+
+int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
+                       uint32_t step, int sample, const float *d_origins, const float *d_dirs, const rtmi_hit *d_hits,
+                       const uint32_t *d_steps, float *d_emitted, const float *d_attenuation, void *d_light_states,
+                       uint32_t *d_flags, float *d_shadow_origins, float *d_shadow_dirs, float *d_shadow_t_max, float *d_direct,
+                       unsigned long long *d_counts, void *stream) {
+  DirectArgs a{};
+  int n_cu = 0;
+  bool work = false;
+  if (const int rc = direct_args(sp, n, d_list, n_list, d_count, step, sample, d_origins, d_dirs, d_hits, d_steps, d_emitted,
+                                 d_attenuation, d_light_states, d_flags, d_shadow_origins, d_shadow_dirs, d_shadow_t_max,
+                                 d_direct, d_counts, nullptr, false, &a, &n_cu, &work))
+    return rc;
+  if (!work) return RTMI_OK;
   HIP_TRY(launch_direct_sample(a, n_cu, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_direct_sample_mis(const rtmi_scene *sp, const rtmi_direct_sample_mis_args *p, void *stream) {
+  static_assert(sizeof(rtmi_direct_sample_mis_args) == 160, "rtmi_direct_sample_mis_args is 160 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!p) return fail(RTMI_ERR_INVALID, "null rtmi_direct_sample_mis_args");
+  if (p->size != (int32_t)sizeof(rtmi_direct_sample_mis_args) || p->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_direct_sample_mis_args.size does not match this library, or reserved is not 0");
+  DirectMisArgs a{};
+  int n_cu = 0;
+  bool work = false;
+  if (const int rc = direct_args(sp, p->n, p->d_list, p->n_list, p->d_count, p->step, p->sample, p->d_origins, p->d_dirs, p->d_hits,
+                                 p->d_steps, p->d_emitted, p->d_attenuation, p->d_light_states, p->d_flags, p->d_shadow_origins,
+                                 p->d_shadow_dirs, p->d_shadow_t_max, p->d_direct, p->d_counts, p->d_carry, true, &a, &n_cu, &work))
+    return rc;
+  if (!work) return RTMI_OK;
+  const Scene *s = S(sp);
+  a.hit_light = s->ldev.hit_light, a.n_entries = s->ldev.n_entries, a.carry = p->d_carry;
+  HIP_TRY(launch_direct_sample_mis(a, n_cu, (hipStream_t)stream));
   return RTMI_OK;
 }
 

@@ -1,5 +1,5 @@
 // Next-event estimation for wavefront paths: the light table (host, at commit), the step kernel and the fold
-// (rtmi_direct_sample, rtmi_path_fold_direct; direct_body.h).  A translation unit of its own: no kernel of kernels.hip is
+// (rtmi_direct_sample, rtmi_direct_sample_mis, rtmi_path_fold_direct; direct_body.h).  A translation unit of its own: no kernel of kernels.hip is
 // compiled differently for it.
 #include "direct_body.h"
 
@@ -75,10 +75,33 @@ void light_records(const std::vector<rtmi_light> &lights, std::vector<LightRec> 
   }
 }
 
+// The light of a hit (rtmi_direct_sample_mis; direct_body.h: LightDev::hit_light): per entry up to the largest one of a
+// table light, the light of each box face and the first light of the entry, -1 where there is none.
+void build_hit_light_map(const std::vector<rtmi_light> &lights, std::vector<int32_t> *map, int32_t *n_entries) {
+  int32_t rows = 0;
+  for (const rtmi_light &l : lights)
+    if (l.entry >= rows) rows = l.entry + 1;
+  map->assign((size_t)rows * kHitLightCols, -1);
+  for (size_t j = 0; j < lights.size(); j++) {
+    const rtmi_light &l = lights[j];
+    if (l.entry < 0) continue;
+    int32_t *row = map->data() + (size_t)l.entry * kHitLightCols;
+    if (l.element >= 0 && l.element < kHitLightAny && row[l.element] < 0) row[l.element] = (int32_t)j;
+    if (row[kHitLightAny] < 0) row[kHitLightAny] = (int32_t)j;
+  }
+  *n_entries = rows;
+}
+
 // ------------------------------------------------------------------ the step (rtmi_direct_sample)
 __global__ __launch_bounds__(kDirectThreads) void direct_sample_kernel(DirectArgs a) {
   __shared__ float s_cdf[kLdsLights];
-  direct_body(a, s_cdf);
+  direct_body<false>(a, s_cdf);
+}
+
+// rtmi_direct_sample_mis: the same body with the balance heuristic's weights.
+__global__ __launch_bounds__(kDirectThreads) void direct_sample_mis_kernel(DirectMisArgs a) {
+  __shared__ float s_cdf[kLdsLights];
+  direct_body<true>(a, s_cdf);
 }
 
 // One lane per candidate: the grid covers the host's bound n_list, capped at 8 workgroups per compute unit (a wave then
@@ -87,6 +110,12 @@ hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t strea
   const int64_t want = cdiv64((int64_t)a.n_list, kDirectThreads);
   const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * kDirectBlocksPerCu;
   hipLaunchKernelGGL(direct_sample_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kDirectThreads), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_t stream) {
+  const int64_t want = cdiv64((int64_t)a.n_list, kDirectThreads);
+  const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * kDirectBlocksPerCu;
+  hipLaunchKernelGGL(direct_sample_mis_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kDirectThreads), 0, stream, a);
   return hipGetLastError();
 }
 

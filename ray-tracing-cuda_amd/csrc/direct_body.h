@@ -3,6 +3,8 @@
 // is a DiffuseLight on a constant texture -- is made on the host at commit (direct.hip: build_light_table); the step
 // kernel below picks one light per path by its share of area x emission, a point on it, and leaves the shadow ray and the
 // unoccluded contribution; rtmi_occluded answers the shadow rays and the fold adds what is visible.
+// rtmi_direct_sample_mis is the same body with the balance heuristic (direct_body<true>): the light sample and the
+// emission the scattered ray finds on a table light are both kept, weighted a / (a + d2) each from its own side.
 //
 // Every operation is one binary32 rounding in the order written (the translation unit is compiled with
 // -ffp-contract=off; division and sqrt are IEEE): tests/directlib.py restates the step in numpy and the two agree bit for
@@ -30,12 +32,25 @@ struct alignas(128) LightRec {
 };
 static_assert(sizeof(LightRec) == 128, "LightRec is 128 bytes");
 
-// The table on the device, beside QueryDev: SceneDev keeps its layout.
-struct LightDev {
+// The table as rtmi_direct_sample's argument block carries it (32 bytes: DirectArgs keeps its layout).
+struct LightTable {
   const LightRec *recs;
   const float *cdf;            // per light, ascending, the last 1.0f: the search reads 4 bytes a probe, not a record
   const uint32_t *light_mats;  // one bit per material: some table light has it
   int32_t n_lights, n_mats;
+};
+
+// The light of a hit (rtmi_direct_sample_mis): one row of kHitLightCols words per entry 0 .. n_entries - 1, -1 for none.
+// Column f < 6: the table light with that entry and element f (a hit of kind PARALLELEPIPED on face f); column 6: the
+// first table light with that entry (a TRIANGLE or PARALLELOGRAM hit, whichever of its triangles); column 7 pads the row
+// to 32 bytes.
+constexpr int kHitLightCols = 8;
+constexpr int kHitLightAny = 6;
+
+// The table on the device, beside QueryDev: SceneDev keeps its layout.
+struct LightDev : LightTable {
+  const int32_t *hit_light;  // int32[n_entries][kHitLightCols]
+  int32_t n_entries;         // 1 + the largest entry of a table light (0: no table light)
 };
 
 constexpr int kLdsLights = 1024;  // at most this many cdf entries are staged in LDS (4 KiB); longer tables search global memory
@@ -43,7 +58,7 @@ constexpr int kDirectThreads = 256;
 constexpr int kDirectBlocksPerCu = 8;  // the grid's cap: longer lists are walked in strides of the grid's lanes
 
 struct DirectArgs {
-  LightDev lt;
+  LightTable lt;
   const MatRec *mats;
   const uint32_t *list, *count;  // rtmi_bounce_list's candidates (both nullable)
   uint32_t n, n_list, step, sample;
@@ -55,6 +70,13 @@ struct DirectArgs {
   uint32_t *light_states, *flags;
   float *shadow_o, *shadow_d, *shadow_t, *direct;
   unsigned long long *counts;  // nullable
+};
+
+// rtmi_direct_sample_mis: the same block, and behind it the hit -> light map and the carry.
+struct DirectMisArgs : DirectArgs {
+  const int32_t *hit_light;
+  float *carry;  // float[n][4], 16-byte aligned: the scattered direction and N . d of a path's last sampling vertex
+  int32_t n_entries;
 };
 
 // The smallest j with r0 <= cdf[j]; the last entry is 1 and r0 <= 1, so one exists.  j stays in [0, n - 1] whatever the
@@ -69,8 +91,12 @@ __device__ __forceinline__ int light_pick(const float *cdf, int n, float r0) {
   return lo;
 }
 
-__device__ __forceinline__ void direct_body(const DirectArgs &a, float *s_cdf) {
-  const LightDev &lt = a.lt;
+// MIS = false: rtmi_direct_sample (Args = DirectArgs).  MIS = true: rtmi_direct_sample_mis (Args = DirectMisArgs), the
+// balance heuristic between the light sample and the scattered ray: WEIGH takes DROP's place (n_dropped counts the
+// emissions weighed) and SAMPLE's g is a / (a + d2) with a = (cs * cl) * scale.
+template <bool MIS, class Args>
+__device__ __forceinline__ void direct_body(const Args &a, float *s_cdf) {
+  const LightTable &lt = a.lt;
   const bool staged = lt.n_lights > 0 && lt.n_lights <= kLdsLights;  // (wave-uniform)
   if (staged) {
     for (int i = (int)threadIdx.x; i < lt.n_lights; i += (int)blockDim.x) s_cdf[i] = lt.cdf[i];
@@ -108,7 +134,31 @@ __device__ __forceinline__ void direct_body(const DirectArgs &a, float *s_cdf) {
         const int4 h0 = hp[0], h1 = hp[1];  // t u v nx | ny nz material kind  (the third 16 bytes name the hitable)
         const int32_t mat = h1.z, kind = h1.w;
         const bool mat_ok = mat >= 0 && mat < lt.n_mats;
-        if (was && mat_ok && (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM || kind == QHIT_PARALLELEPIPED) &&
+        if constexpr (MIS) {
+          // WEIGH: the light of the hit by its entry (and face), every index checked before it addresses anything
+          const int4 h2 = hp[2];  // entry element reserved
+          const int32_t entry = h2.x, face = h2.y;
+          int32_t col = -1;
+          if (kind == QHIT_PARALLELEPIPED) col = face >= 0 && face < kHitLightAny ? face : -1;
+          else if (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM) col = kHitLightAny;
+          int32_t j = -1;
+          if (was && col >= 0 && entry >= 0 && entry < a.n_entries) j = a.hit_light[(int64_t)entry * kHitLightCols + col];
+          if (j >= 0 && j < lt.n_lights) {
+            const float4 c = reinterpret_cast<const float4 *>(a.carry)[i];
+            const float4 *lp = reinterpret_cast<const float4 *>(lt.recs + j);
+            const float4 l2 = lp[2], l3 = lp[3];  // e2.z n | emission scale
+            const float cl = fabsf(dot3(mk(l2.y, l2.z, l2.w), mk(c.x, c.y, c.z)));
+            const float t = __int_as_float(h0.x);
+            const float d2 = t * t;
+            const float av = (c.w * cl) * l3.w;
+            const float sum = av + d2;
+            const bool div = av > 0.f && d2 > 0.f && sum < INFINITY;
+            const float w = av / sum;
+            const V3 e = mk(a.emitted[i3 + 0], a.emitted[i3 + 1], a.emitted[i3 + 2]);
+            a.emitted[i3 + 0] = div ? e.x * w : 0.f, a.emitted[i3 + 1] = div ? e.y * w : 0.f, a.emitted[i3 + 2] = div ? e.z * w : 0.f;
+            dropped = true;
+          }
+        } else if (was && mat_ok && (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM || kind == QHIT_PARALLELEPIPED) &&
             lt.light_mats != nullptr && ((lt.light_mats[mat >> 5] >> (mat & 31)) & 1u)) {
           a.emitted[i3 + 0] = 0.f, a.emitted[i3 + 1] = 0.f, a.emitted[i3 + 2] = 0.f;
           dropped = true;
@@ -145,13 +195,20 @@ __device__ __forceinline__ void direct_body(const DirectArgs &a, float *s_cdf) {
           const float cl = fabsf(dot3(ln, wi));
           valid = d2 > 0.f && cs > 0.f && cl > 0.f && dist < INFINITY;
           if (valid) {
-            const float g = ((cs * cl) / d2) * l3.w;
+            float g;
+            if constexpr (MIS) {
+              const float av = (cs * cl) * l3.w;
+              g = av / (av + d2);
+            } else {
+              g = ((cs * cl) / d2) * l3.w;
+            }
             const V3 att = mk(a.attenuation[i3 + 0], a.attenuation[i3 + 1], a.attenuation[i3 + 2]);
             dir = (att * mk(l3.x, l3.y, l3.z)) * g;
             t_max = dist * 0.999f;
           } else {
             wi = splat(0.f);
           }
+          if constexpr (MIS) reinterpret_cast<float4 *>(a.carry)[i] = make_float4(d.x, d.y, d.z, dot3(N, d));
         }
       }
       if (valid) a.shadow_o[i3 + 0] = x.x, a.shadow_o[i3 + 1] = x.y, a.shadow_o[i3 + 2] = x.z;

@@ -260,6 +260,10 @@ void build_light_table(const Scene &s, std::vector<rtmi_light> *lights, std::vec
 void light_records(const std::vector<rtmi_light> &lights, std::vector<LightRec> *recs, std::vector<float> *cdf);
 // The step for the candidates of a.list (rtmi_direct_sample): a.n_list >= 1.
 hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t stream);
+// The light of a hit, per entry and box face (rtmi_direct_sample_mis; direct_body.h: LightDev::hit_light), and that step.
+struct DirectMisArgs;
+void build_hit_light_map(const std::vector<rtmi_light> &lights, std::vector<int32_t> *map, int32_t *n_entries);
+hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_t stream);
 // rtmi_path_fold with T[k] = d_occluded[k] ? E[k] : E[k] + D[k] for E[k] (rtmi_path_fold_direct).
 hipError_t launch_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                                    const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded,

@@ -123,6 +123,16 @@ class PathAdvanceArgs(C.Structure):
                 ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
+class DirectSampleMisArgs(C.Structure):
+    """rtmi_direct_sample_mis_args of include/rtmi.h (the arrays of one rtmi_direct_sample_mis call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("d_list", C.c_void_p), ("n_list", C.c_int64),
+                ("d_count", C.c_void_p), ("step", C.c_uint32), ("sample", C.c_int32), ("d_origins", C.c_void_p),
+                ("d_dirs", C.c_void_p), ("d_hits", C.c_void_p), ("d_steps", C.c_void_p), ("d_emitted", C.c_void_p),
+                ("d_attenuation", C.c_void_p), ("d_light_states", C.c_void_p), ("d_flags", C.c_void_p),
+                ("d_shadow_origins", C.c_void_p), ("d_shadow_dirs", C.c_void_p), ("d_shadow_t_max", C.c_void_p),
+                ("d_direct", C.c_void_p), ("d_carry", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
 class DenoiseOpts(C.Structure):
     """rtmi_denoise_opts of include/rtmi.h."""
     _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
@@ -262,6 +272,7 @@ SYMBOLS = [
     ("rtmi_direct_sample", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int] +
                                     [C.c_void_p] * 14),
     ("rtmi_path_fold_direct", C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8),
+    ("rtmi_direct_sample_mis", C.c_int, [C.c_void_p, C.POINTER(DirectSampleMisArgs), C.c_void_p]),
     ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
     ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
 ]
@@ -434,7 +445,11 @@ class Steps(collections.namedtuple("Steps", "rgb steps alive origins directions 
     rtmi_trace's ray count); ``origins`` / ``directions``: the loop's own copies of the rays as the last step left them;
     ``emitted`` / ``attenuation``: the (max(max_depth, 1), N, 3) float32 layer stacks; ``works``: every step's work words.
     With ``direct=True`` also ``direct`` (layers, N, 3) float32, ``occluded`` (layers, N) uint8 -- the stacks
-    ``path_fold_direct`` read -- and ``flags`` (N,) int32; else None.  ``check()`` waits for the loop and raises when a step abandoned a mesh search."""
+    ``path_fold_direct`` read -- and ``flags`` (N,) int32; else None.  With ``direct="mis"`` the attribute ``carry`` is the
+    loop's one (N, 4) float32 carry tensor, else None: an attribute beside the tuple's fields, so that unpacking a ``Steps``
+    gives what it gave.  ``check()`` waits for the loop and raises when a step abandoned a mesh search."""
+
+    carry = None
 
     def check(self):
         for k, w in enumerate(self.works):
@@ -507,10 +522,11 @@ def path_fold_direct(directions, steps, emitted_stack, attenuation_stack, direct
     return out
 
 
-DirectSample = collections.namedtuple("DirectSample", "origins directions t_max direct flags counts")
+DirectSample = collections.namedtuple("DirectSample", "origins directions t_max direct flags counts carry", defaults=(None,))
 """What ``SceneBuilder.direct_sample`` returns: the shadow rays ``origins`` / ``directions`` (N, 3) float32 and ``t_max``
 (N,) float32 -- a zero direction where a path has none, which ``occluded`` answers "clear" --, ``direct`` (N, 3) float32,
-the unoccluded contribution, ``flags`` (N,) int32 and ``counts`` (2,) int64: paths sampled, emissions dropped."""
+the unoccluded contribution, ``flags`` (N,) int32 and ``counts`` (2,) int64: paths sampled, emissions dropped (with
+``mis=True``: weighed); ``carry`` (N, 4) float32 with ``mis=True``, else None."""
 
 
 class Paths:
@@ -961,7 +977,7 @@ class SceneBuilder:
         _check(self.L.rtmi_scene_lights(self.h, out.ctypes.data_as(C.c_void_p), n), "rtmi_scene_lights")
         return out
 
-    def direct_sample(self, step, result, light_states, flags, sample=True, out=None, counts=None):
+    def direct_sample(self, step, result, light_states, flags, sample=True, out=None, counts=None, mis=False, carry=None):
         """Next-event estimation after step number ``step`` of a loop (rtmi_direct_sample), on torch's current stream.
 
         ``result``: the ``Bounce`` of that step, made with ``hits=True``, ``steps`` and the layer tensors ``emitted`` /
@@ -971,7 +987,12 @@ class SceneBuilder:
         ``sample=False`` (a loop's last step) only drops.  A path that hits a table light after its previous vertex
         sampled the lights has ``result.emitted`` zeroed.  ``out``: an optional ``(origins, directions, t_max, direct)`` of
         (N, 3), (N, 3), (N,), (N, 3) float32 tensors to write into (tensors made here start as zeros); ``counts``: an
-        optional (2,) int64 tensor to add into.  Returns ``DirectSample``."""
+        optional (2,) int64 tensor to add into.  Returns ``DirectSample``.
+
+        ``mis=True`` is rtmi_direct_sample_mis: the light a vertex samples and the light its scattered ray then finds are
+        both kept, weighted by the balance heuristic (``result.emitted`` of such a hit is scaled, not zeroed, and
+        ``counts[1]`` counts the emissions weighed).  ``carry``: the loop's (N, 4) float32 tensor, the same one in every call
+        of a loop; made here when None and returned in the result."""
         import torch
         if not isinstance(result, Bounce) or result.hits is None or result.steps is None:
             raise RtmiError("result must be the Bounce of a step made with hits=True and steps")
@@ -997,6 +1018,24 @@ class SceneBuilder:
             if not _is_buffer(t, shape, dev, torch.float32):
                 raise RtmiError("out's %s must be a contiguous CUDA float32 tensor of shape %s on the rays' device" % (name, shape))
         stream = self._stream(dev)
+        if mis:
+            if carry is None:
+                carry = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+            elif not _is_buffer(carry, (n, 4), dev, torch.float32):
+                raise RtmiError("carry must be a contiguous CUDA float32 tensor of shape (N, 4) on the rays' device")
+            a = DirectSampleMisArgs()
+            a.size, a.reserved, a.n, a.n_list, a.step, a.sample = C.sizeof(DirectSampleMisArgs), 0, n, n_list, step, 1 if sample else 0
+            val = lambda t: t.data_ptr() if t is not None else None
+            a.d_list, a.d_count, a.d_origins, a.d_dirs = val(idx), val(cnt), val(o), val(d)
+            a.d_hits, a.d_steps, a.d_emitted, a.d_attenuation = val(result.hits.raw), val(result.steps), val(result.emitted), val(result.attenuation)
+            a.d_light_states, a.d_flags = val(light_states), val(flags)
+            a.d_shadow_origins, a.d_shadow_dirs, a.d_shadow_t_max, a.d_direct = val(so), val(sd), val(st), val(dd)
+            a.d_carry, a.d_counts = val(carry), val(counts)
+            with torch.cuda.device(dev):
+                _check(self.L.rtmi_direct_sample_mis(self.h, C.byref(a), stream), "rtmi_direct_sample_mis")
+            return DirectSample(so, sd, st, dd, flags, counts, carry)
+        if carry is not None:
+            raise RtmiError("carry is rtmi_direct_sample_mis's: pass mis=True")
         with torch.cuda.device(dev):
             _check(self.L.rtmi_direct_sample(self.h, n, _ptr(idx), n_list, _ptr(cnt), step, 1 if sample else 0, _ptr(o), _ptr(d),
                                              _ptr(result.hits.raw), _ptr(result.steps), _ptr(result.emitted),
@@ -1193,6 +1232,11 @@ class SceneBuilder:
         plain loop's bit for bit, and the radiance has ``trace``'s expectation.  ``each`` runs after the step's direct
         sampling.
 
+        ``direct="mis"`` is the ``direct=True`` loop with ``direct_sample(mis=True)``: one carry tensor for the loop
+        (``Steps.carry``), ``shadow`` and the fold as with ``direct=True``.  The light a vertex samples and the light its
+        scattered ray finds are weighted by the balance heuristic, so a light close to a diffuse surface no longer gives
+        unbounded samples; the paths are still the plain loop's and the expectation ``trace``'s.
+
         ``shadow`` chooses the visibility query of ``direct=True``: ``"all"`` is ``occluded`` over all N shadow rays,
         ``"list"`` is ``occluded_list`` on the list the step used (``result.paths``), valid only with ``compact`` and
         ``direct=True``; None (the default) is ``SHADOW_DEFAULT`` where ``"list"`` is valid, else ``"all"``.  Every output
@@ -1204,6 +1248,8 @@ class SceneBuilder:
         direction that does not normalise: it may sample, leaves the list alive, and ``"all"`` answers its stale shadow
         ray again in the layers after its last, which no fold reads.)"""
         import torch
+        if not (direct is False or direct is True or direct == "mis"):
+            raise RtmiError("direct must be False, True or \"mis\"")
         if direct and light_states is None:
             raise RtmiError("direct=True needs light_states: RNG states of their own, e.g. rng_states(seed, N, first=N)")
         if not (compact is False or compact is True or compact == "full"):
@@ -1227,7 +1273,8 @@ class SceneBuilder:
         A = torch.empty((layers, n, 3), dtype=torch.float32, device=dev)
         steps = torch.zeros((n,), dtype=torch.int32, device=dev)
         want_hits = (each is not None) if hits is None else bool(hits)
-        Dk = occ = flags = rays = None
+        mis = direct == "mis"
+        Dk = occ = flags = rays = carry = None
         if direct:
             want_hits = True
             if not _is_buffer(light_states, (STATE_WORDS, n), dev, torch.int32):
@@ -1238,6 +1285,8 @@ class SceneBuilder:
             rays = (torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
                     torch.zeros((n,), dtype=torch.float32, device=dev))  # (the shadow rays: one set, rewritten every step)
             counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+            if mis:
+                carry = torch.zeros((n, 4), dtype=torch.float32, device=dev)  # (one for the loop)
         works = []
         lists, cur = None, None
         if compact and max_depth > 0:
@@ -1251,7 +1300,8 @@ class SceneBuilder:
                 r = self.bounce(o, d, states, emitted=E[k], attenuation=A[k], hits=want_hits, steps=steps)
             works.append(r.work)
             if direct:
-                self.direct_sample(k, r, light_states, flags, sample=k + 1 < max_depth, out=rays + (Dk[k],), counts=counts)
+                self.direct_sample(k, r, light_states, flags, sample=k + 1 < max_depth, out=rays + (Dk[k],), counts=counts,
+                                   mis=mis, carry=carry)
                 if shadow == "list":
                     q = self.occluded_list(r.paths, rays[0], rays[1], rays[2], out=occ[k])
                 else:
@@ -1267,7 +1317,9 @@ class SceneBuilder:
                     cur = _path_compact(n, o, d, cur.index, n, cur.count, nxt, dev)
         if direct:
             rgb = path_fold_direct(d, steps, E, A, Dk, occ)
-            return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works, Dk, occ, flags)
+            st = Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works, Dk, occ, flags)
+            st.carry = carry
+            return st
         rgb = path_fold(d, steps, E, A)
         return Steps(rgb, steps, (d != 0).any(dim=1), o, d, E, A, works)
 
@@ -1502,7 +1554,8 @@ class Renderer:
         shadow query is that loop's default, ``SHADOW_DEFAULT``; the sums are the same with either): the same
         paths with next-event estimation, the same expectation and less variance where small lights light the scene; the
         sums are then not ``render_budget``'s.  Its light states are seeded from the renderer's seed with first = items on
-        the first such call and carried on."""
+        the first such call and carried on.  ``direct="mis"`` is passed through to ``trace_steps`` in the same way
+        (multiple importance sampling); ``self.carry`` is then the last sample's carry tensor, else None."""
         torch = self.torch
         if self.frame.post_process:
             raise RtmiError("render_rays needs a frame made with post=False: per-pixel sample counts have no uniform division (resolve)")
@@ -1528,8 +1581,9 @@ class Renderer:
                 if direct:
                     if getattr(self, "light_states", None) is None:
                         self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
-                    st = self.scene.trace_steps(origins, dirs, self.states, int(self.frame.max_depth), compact=True, direct=True,
+                    st = self.scene.trace_steps(origins, dirs, self.states, int(self.frame.max_depth), compact=True, direct=direct,
                                                 light_states=self.light_states)
+                    self.carry = st.carry
                     for w in st.works:
                         self.budget_abandoned += w[0]
                     queries = st.steps + st.alive.to(torch.int32)
