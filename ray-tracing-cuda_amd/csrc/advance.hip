@@ -25,20 +25,17 @@ __global__ __launch_bounds__(kAdvanceThreads) void path_advance_kernel(AdvanceAr
   advance_body<CURVED>(a);
 }
 
-// One lane per candidate: the grid covers the host's bound n_list, capped at 8 workgroups per compute unit (a wave then
-// walks further chunks by its number).  n_list >= 1.
+// One lane per candidate: list_grid (kernels.h) over the host's bound n_list.
 hipError_t launch_path_advance(const FrameDev &fr, const CameraDev &cam, const float w[3], int kind, float fov,
                                const AdvanceCall &c, int n_cu, hipStream_t stream) {
   AdvanceArgs a{};
   a.fr = fr, a.proj.cam = cam, a.proj.w = mk(w[0], w[1], w[2]), a.proj.kind = kind, a.proj.fov = fov;
-  a.budget = c.budget, a.list = c.list, a.count = c.count, a.n_list = (uint32_t)c.n_list;
+  a.budget = c.budget, a.list = c.list.list, a.count = c.list.count, a.n_list = c.list.n_list;
   a.origins = c.origins, a.dirs = c.dirs, a.states = c.states, a.steps = c.steps;
   a.emitted = c.emitted, a.attenuation = c.attenuation;
   a.emitted_stack = c.emitted_stack, a.attenuation_stack = c.attenuation_stack, a.cursor = c.cursor;
   a.sum = c.sum, a.sq = c.sq, a.samples = c.samples, a.ray_counts = c.ray_counts, a.counts = c.counts;
-  const int64_t want = (c.n_list + kAdvanceThreads - 1) / kAdvanceThreads;
-  const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * kAdvanceBlocksPerCu;
-  const dim3 grid((unsigned)(want < cap ? want : cap));
+  const dim3 grid(list_grid(a.n_list, kAdvanceThreads, n_cu, kAdvanceBlocksPerCu));
   if (kind == PROJ_EQUIRECT || kind == PROJ_FISHEYE) {
     hipLaunchKernelGGL(path_advance_kernel<true>, grid, dim3(kAdvanceThreads), 0, stream, a);
   } else {

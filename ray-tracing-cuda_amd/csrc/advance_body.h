@@ -9,7 +9,7 @@
 // Every operation is one binary32 rounding in the order written (the translation unit is compiled with
 // -ffp-contract=off): tests/advancelib.py restates the rule in numpy and the two agree word for word.
 #pragma once
-// (included by advance.hip inside namespace rtmi, after path_shared.h: live_ray, fold_layers, camera_ray)
+// (included by advance.hip inside namespace rtmi, after path_shared.h: live_ray, fold_layers, camera_ray; path_list.h)
 
 constexpr int kAdvanceThreads = 256;
 constexpr int kAdvanceBlocksPerCu = 8;  // the grid's cap: longer lists are walked in strides of the grid's lanes
@@ -48,11 +48,8 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs &a) {
   CameraProj proj = a.proj;
   if (!CURVED) proj.kind = proj.kind == PROJ_ORTHOGRAPHIC ? PROJ_ORTHOGRAPHIC : PROJ_CAMERA;
   const uint32_t spp = (uint32_t)a.fr.spp, max_depth = (uint32_t)a.fr.max_depth;
-  uint32_t end = a.n_list;
-  if (a.count) {
-    const uint32_t c = *a.count;
-    end = c < end ? c : end;
-  }
+  const PathList pl{a.list, a.count, a.n_list};  // (the block keeps its layout; the rule is path_list.h's)
+  const uint32_t end = list_end(pl);
   // chunks of 64 entries by wave number, as direct_sample_kernel takes them: no cursor, no atomic
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -61,7 +58,7 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs &a) {
   for (uint64_t at = (uint64_t)wave * 64u; at < end; at += stride) {
     const uint32_t e = (uint32_t)at + lane;
     if (e >= end) continue;
-    const uint32_t item = a.list ? a.list[e] : e;
+    const uint32_t item = list_entry(pl, e);
     if ((int64_t)item >= n) continue;  // (an entry that is no work item is dropped before anything is addressed with it)
     const int64_t q = (int64_t)item, q3 = q * 3;
     const int64_t idx = frame_pixel_of_rank(a.fr, a.fr.rank, q);

@@ -1229,7 +1229,7 @@ static int occluded(const rtmi_scene *sp, int64_t n, const float *d_o, const flo
   if (rc || n == 0) return rc;
   float near_lo[3], near_hi[3], near_short;
   near_box(s, near_lo, near_hi, &near_short);
-  HIP_TRY(launch_occlusion(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, d_o, d_d,
+  HIP_TRY(launch_occlusion(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, nullptr, d_o, d_d,
                            d_t_max, d_occluded, d_counts, d_check, (hipStream_t)stream));
   return RTMI_OK;
 }
@@ -1274,34 +1274,47 @@ int rtmi_bounce(const rtmi_scene *sp, int64_t n, float *d_origins, float *d_dirs
   if (rc || n == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
-  HIP_TRY(launch_bounce(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_origins, d_dirs,
+  HIP_TRY(launch_bounce(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, nullptr, d_origins, d_dirs,
                         reinterpret_cast<uint32_t *>(d_states), d_emitted, d_attenuation, reinterpret_cast<int32_t *>(d_hits),
                         d_steps, d_work, st));
   return RTMI_OK;
 }
 
 // ------------------------------------------------------------------ steps over live paths only
-// What rtmi_path_compact and rtmi_bounce_list check of their list, without a HIP call.
+// What the entries that take the candidates of a list (path_list.h) check, in two pieces with each entry's own checks
+// between them.  The arguments, without a HIP call: the list ...
 static int check_list(int64_t n, const uint32_t *d_list, int64_t n_list) {
   if (n_list < 0) return fail(RTMI_ERR_INVALID, "negative list length");
   if (n_list > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 list entries");
   if (!d_list && n_list > n) return fail(RTMI_ERR_INVALID, "a null list is the paths 0 .. n_list - 1: n_list must not exceed n");
   return RTMI_OK;
 }
+// ... behind n in 0 .. 2^31 - 1, refused in the entry's own words (rtmi_path_advance's n is its frame's items: it checks
+// the list alone).
+static int list_args(int64_t n, const char *negative, const char *too_many, const uint32_t *d_list, int64_t n_list) {
+  if (n < 0) return fail(RTMI_ERR_INVALID, negative);
+  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, too_many);
+  return check_list(n, d_list, n_list);
+}
+// Then the scene: committed, and the current device's.  *n_cu: its compute units when there is work (n > 0 and
+// n_list > 0), else 0.
+static int list_scene(const Scene *s, bool work, int *n_cu) {
+  *n_cu = 0;
+  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
+  return scene_device(s, work ? n_cu : nullptr);
+}
 
 size_t rtmi_path_compact_scratch_bytes(int64_t n_list) { return path_compact_scratch_bytes(n_list); }
 
 int rtmi_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
                       const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, void *d_scratch, void *stream) {
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
-  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
-  if (const int rc = check_list(n, d_list_in, n_list)) return rc;
+  if (const int rc = list_args(n, "negative path count", "more than 2^31 - 1 paths", d_list_in, n_list)) return rc;
   if (n_list > 0 && !(d_origins && d_dirs && d_list_out && d_count_out && d_scratch))
     return fail(RTMI_ERR_INVALID, "null ray, output list, output count or scratch array");
   if (d_list_out && d_list_out == d_list_in) return fail(RTMI_ERR_INVALID, "d_list_out must not be d_list_in: ping-pong two lists");
   if (d_count_out && d_count_out == d_count_in) return fail(RTMI_ERR_INVALID, "d_count_out must not be d_count_in: ping-pong two counts");
   if (!d_count_out) return RTMI_OK;  // (n_list == 0 and nowhere to write the 0)
-  HIP_TRY(launch_path_compact(n, d_origins, d_dirs, d_list_in, n_list, d_count_in, d_list_out, d_count_out,
+  HIP_TRY(launch_path_compact(n, d_origins, d_dirs, PathList{d_list_in, d_count_in, (uint32_t)n_list}, d_list_out, d_count_out,
                               reinterpret_cast<uint32_t *>(d_scratch), (hipStream_t)stream));
   return RTMI_OK;
 }
@@ -1310,20 +1323,20 @@ int rtmi_bounce_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, in
                      float *d_origins, float *d_dirs, void *d_states, float *d_emitted, float *d_attenuation, rtmi_hit *d_hits,
                      uint32_t *d_steps, unsigned long long *d_work, void *stream) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n >= 0 && n <= (int64_t)INT32_MAX)  // (else batch_prologue refuses n itself)
-    if (const int rc = check_list(n, d_list, n_list)) return rc;
-  const Scene *s;
+  if (const int rc = list_args(n, "negative ray count", "more than 2^31 - 1 rays", d_list, n_list)) return rc;
+  if (n > 0 && !(d_origins && d_dirs && d_states && d_emitted && d_attenuation && d_work))
+    return fail(RTMI_ERR_INVALID, "null ray, state, emitted, attenuation or work array");
+  const Scene *s = S(sp);
   int n_cu;
-  const int no_depth = 0;  // (as rtmi_bounce)
-  const int rc = batch_prologue(sp, n, d_origins && d_dirs && d_states && d_emitted && d_attenuation && d_work,
-                                "null ray, state, emitted, attenuation or work array", &no_depth, &s, &n_cu);
+  const int rc = list_scene(s, n > 0 && n_list > 0, &n_cu);
   if (rc || n == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
   if (n_list == 0) return RTMI_OK;                            // (an empty list: no path stepped, and d_work says so)
-  HIP_TRY(launch_bounce_list(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, d_list, n_list, d_count, d_origins, d_dirs,
-                             reinterpret_cast<uint32_t *>(d_states), d_emitted, d_attenuation,
-                             reinterpret_cast<int32_t *>(d_hits), d_steps, d_work, st));
+  const PathList list{d_list, d_count, (uint32_t)n_list};
+  HIP_TRY(launch_bounce(pick_query_variant(s->features), s->dev, s->qdev, n_cu, n, &list, d_origins, d_dirs,
+                        reinterpret_cast<uint32_t *>(d_states), d_emitted, d_attenuation, reinterpret_cast<int32_t *>(d_hits),
+                        d_steps, d_work, st));
   return RTMI_OK;
 }
 
@@ -1363,9 +1376,7 @@ static int direct_args(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, 
                        uint32_t *d_flags, float *d_shadow_origins, float *d_shadow_dirs, float *d_shadow_t_max, float *d_direct,
                        unsigned long long *d_counts, const float *d_carry, bool mis, DirectArgs *out, int *n_cu, bool *work) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count");
-  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths");
-  if (const int rc = check_list(n, d_list, n_list)) return rc;
+  if (const int rc = list_args(n, "negative path count", "more than 2^31 - 1 paths", d_list, n_list)) return rc;
   if (step >= (uint32_t)RTMI_MAX_DEPTH) return fail(RTMI_ERR_INVALID, "step outside 0..RTMI_MAX_DEPTH - 1");
   if (n_list > 0 && !(d_origins && d_dirs && d_hits && d_steps && d_emitted && d_attenuation && d_light_states && d_flags &&
                       d_shadow_origins && d_shadow_dirs && d_shadow_t_max && d_direct))
@@ -1373,10 +1384,8 @@ static int direct_args(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, 
   if (mis && n_list > 0 && (!d_carry || (reinterpret_cast<uintptr_t>(d_carry) & 15u)))
     return fail(RTMI_ERR_INVALID, "null carry array, or one that is not 16-byte aligned");
   const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   *work = n > 0 && n_list > 0;
-  *n_cu = 0;
-  if (const int rc = scene_device(s, *work ? n_cu : nullptr)) return rc;
+  if (const int rc = list_scene(s, *work, n_cu)) return rc;
   if (!*work) return RTMI_OK;
   DirectArgs &a = *out;
   a.lt = s->ldev, a.mats = s->dev.mats;
@@ -1446,20 +1455,18 @@ static int occluded_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list
                          const float *d_o, const float *d_d, const float *d_t_max, uint8_t *d_occluded,
                          unsigned long long *d_counts, unsigned long long *d_check, void *stream) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
-  if (n < 0) return fail(RTMI_ERR_INVALID, "negative path count n");
-  if (n > (int64_t)INT32_MAX) return fail(RTMI_ERR_INVALID, "more than 2^31 - 1 paths n");
-  if (const int rc = check_list(n, d_list, n_list)) return rc;
+  if (const int rc = list_args(n, "negative path count n", "more than 2^31 - 1 paths n", d_list, n_list)) return rc;
   const bool work = n > 0 && n_list > 0;
   if (work && !(d_o && d_d && d_occluded)) return fail(RTMI_ERR_INVALID, "null d_origins, d_dirs or d_occluded");
   const Scene *s = S(sp);
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
-  int n_cu = 0;
-  if (const int rc = scene_device(s, work ? &n_cu : nullptr)) return rc;
+  int n_cu;
+  if (const int rc = list_scene(s, work, &n_cu)) return rc;
   if (!work) return RTMI_OK;
   float near_lo[3], near_hi[3], near_short;
   near_box(s, near_lo, near_hi, &near_short);
-  HIP_TRY(launch_occlusion_list(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, d_list, n_list,
-                                d_count, d_o, d_d, d_t_max, d_occluded, d_counts, d_check, (hipStream_t)stream));
+  const PathList list{d_list, d_count, (uint32_t)n_list};
+  HIP_TRY(launch_occlusion(pick_query_variant(s->features), s->dev, near_lo, near_hi, near_short, n_cu, n, &list, d_o, d_d,
+                           d_t_max, d_occluded, d_counts, d_check, (hipStream_t)stream));
   return RTMI_OK;
 }
 
@@ -1670,13 +1677,12 @@ int rtmi_path_advance(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_path
     return fail(RTMI_ERR_INVALID, "null ray, state, step, emitted, attenuation, cursor, sum or sample-count array");
   if (a->n_list > 0 && d.max_depth > 0 && !(a->d_emitted_stack && a->d_attenuation_stack))
     return fail(RTMI_ERR_INVALID, "null emitted or attenuation stack with max_depth > 0");
-  if (!s->committed) return fail(RTMI_ERR_INVALID, "scene not committed");
   const bool work = d.items > 0 && a->n_list > 0;
-  int n_cu = 0;
-  if ((rc = scene_device(s, work ? &n_cu : nullptr))) return rc;
+  int n_cu;
+  if ((rc = list_scene(s, work, &n_cu))) return rc;
   if (!work) return RTMI_OK;
   AdvanceCall c{};
-  c.budget = a->d_budget, c.list = a->d_list, c.count = a->d_count, c.n_list = a->n_list;
+  c.budget = a->d_budget, c.list = {a->d_list, a->d_count, (uint32_t)a->n_list};
   c.origins = a->d_origins, c.dirs = a->d_dirs, c.states = reinterpret_cast<uint32_t *>(a->d_states), c.steps = a->d_steps;
   c.emitted = a->d_emitted, c.attenuation = a->d_attenuation;
   c.emitted_stack = a->d_emitted_stack, c.attenuation_stack = a->d_attenuation_stack, c.cursor = a->d_cursor;

@@ -104,19 +104,17 @@ __global__ __launch_bounds__(kDirectThreads) void direct_sample_mis_kernel(Direc
   direct_body<true>(a, s_cdf);
 }
 
-// One lane per candidate: the grid covers the host's bound n_list, capped at 8 workgroups per compute unit (a wave then
-// walks further chunks by its number: 2^19 entries a round on 256 compute units).  n_list >= 1.
-hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t stream) {
-  const int64_t want = cdiv64((int64_t)a.n_list, kDirectThreads);
-  const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * kDirectBlocksPerCu;
-  hipLaunchKernelGGL(direct_sample_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kDirectThreads), 0, stream, a);
+// One lane per candidate: list_grid (kernels.h) over the host's bound n_list -- 2^19 entries a round on 256 compute units.
+template <auto Kernel, class Args>
+static hipError_t direct_launch(const Args &a, int n_cu, hipStream_t stream) {
+  hipLaunchKernelGGL(Kernel, dim3(list_grid(a.n_list, kDirectThreads, n_cu, kDirectBlocksPerCu)), dim3(kDirectThreads), 0, stream, a);
   return hipGetLastError();
 }
+hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t stream) {
+  return direct_launch<direct_sample_kernel>(a, n_cu, stream);
+}
 hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_t stream) {
-  const int64_t want = cdiv64((int64_t)a.n_list, kDirectThreads);
-  const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * kDirectBlocksPerCu;
-  hipLaunchKernelGGL(direct_sample_mis_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kDirectThreads), 0, stream, a);
-  return hipGetLastError();
+  return direct_launch<direct_sample_mis_kernel>(a, n_cu, stream);
 }
 
 // ------------------------------------------------------------------ the fold (rtmi_path_fold_direct)

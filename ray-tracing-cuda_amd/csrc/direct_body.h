@@ -18,6 +18,8 @@
 
 namespace rtmi {
 
+#include "path_list.h"
+
 // One light, 128 aligned bytes.  The step gathers the first 80 per lane as five 16-byte loads: words 0..15 the geometry,
 // emission and scale, words 16..19 the kind.  The rest is the host's (rtmi_scene_lights) and travels along so that one
 // record says everything about a light.
@@ -102,11 +104,8 @@ __device__ __forceinline__ void direct_body(const Args &a, float *s_cdf) {
     for (int i = (int)threadIdx.x; i < lt.n_lights; i += (int)blockDim.x) s_cdf[i] = lt.cdf[i];
     __syncthreads();
   }
-  uint32_t end = a.n_list;
-  if (a.count) {
-    const uint32_t c = *a.count;
-    end = c < end ? c : end;
-  }
+  const PathList pl{a.list, a.count, a.n_list};  // (the block keeps its layout; the rule is path_list.h's)
+  const uint32_t end = list_end(pl);
   // chunks of 64 entries by wave number, as bounce_list_kernel takes them: no cursor, no atomic
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -118,7 +117,7 @@ __device__ __forceinline__ void direct_body(const Args &a, float *s_cdf) {
     uint32_t i = 0u;
     bool cand = e < end;
     if (cand) {
-      i = a.list ? a.list[e] : e;
+      i = list_entry(pl, e);
       cand = i < a.n;  // (an entry that is no path is dropped)
     }
     if (cand) {

@@ -12,6 +12,8 @@
 
 namespace rtmi {
 
+#include "path_list.h"  // PathList: the candidates of a list, as the wavefront launchers below take them
+
 int64_t frame_pixel_of(const FrameDev &fr, int rank, int64_t q);
 
 // first >= 0: fr.items states of subsequences first, first + 1, ... (rtmi_rng_init_n) instead of the frame's pixels
@@ -208,18 +210,13 @@ hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd
 // d_occluded: n bytes; d_t_max, d_counts ({abandoned, fallback rays}), d_check nullable (as launch_query).  Rays whose
 // origin lies inside [near_lo, near_hi] (the padded union of the meshes' root bounds) and whose t_max is not below
 // near_short start the walk from +inf.
+// list (null: every ray): the same query for the listed paths only (rtmi_occluded_list; kernels.hip:
+// occlusion_list_kernel): launch_bounce's list, entries need not be distinct; every array keeps n paths, an unlisted
+// path keeps its byte.  The grid is then sized by list->n_list >= 1.
 hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
-                            float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
+                            float near_short, int n_cu, int64_t n, const PathList *list, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream);
-// The same query for the listed paths only (rtmi_occluded_list; kernels.hip: occlusion_list_kernel): launch_bounce_list's
-// (d_list, n_list, d_count), entries need not be distinct; every array keeps n paths, an unlisted path keeps its byte.
-// The grid is sized by n_list.  n_list >= 1.
-hipError_t launch_occlusion_list(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
-                                 float near_short, int n_cu, int64_t n, const uint32_t *d_list, int64_t n_list,
-                                 const uint32_t *d_count, const float *d_o, const float *d_d, const float *d_t_max,
-                                 uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check,
-                                 hipStream_t stream);
 // Radiance of caller rays (rtmi_trace; kernels.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
 // words, zeroed in stream order before the call -- [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's
 // cursor, and from byte kCallParamsOffset the kernel's argument block (written in stream order just before the launch).
@@ -231,23 +228,22 @@ hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, i
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
 // One iteration of Trace's loop per ray (rtmi_bounce; kernels.hip: bounce_kernel), on the query variants: rays and states
 // are read and written in place; d_hits (n x 12 words, rtmi_hit) and d_steps nullable; d_work as launch_trace's, [1] = the
-// paths stepped.
-hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, float *d_o, float *d_d,
-                         uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
-                         unsigned long long *d_work, hipStream_t stream);
-// The same step for the listed paths only (rtmi_bounce_list; kernels.hip: bounce_list_kernel): d_list (nullable: the
-// identity) holds n_list entries at most, d_count (nullable, a device word) cuts it short; every array keeps n paths.
-// n_list >= 1.
-hipError_t launch_bounce_list(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const uint32_t *d_list,
-                              int64_t n_list, const uint32_t *d_count, float *d_o, float *d_d, uint32_t *d_states,
-                              float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
-                              unsigned long long *d_work, hipStream_t stream);
+// paths stepped.  list (null: every path): the same step for the candidates of the list only (rtmi_bounce_list; kernels.hip:
+// bounce_list_kernel; path_list.h); every array keeps n paths.  list->n_list >= 1.
+hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const PathList *list,
+                         float *d_o, float *d_d, uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits,
+                         uint32_t *d_steps, unsigned long long *d_work, hipStream_t stream);
 // The live candidates' path indices, in the candidates' order, and their number (rtmi_path_compact): three launches, no
 // workgroup waits for another.  d_scratch: path_compact_scratch_bytes(n_list) bytes.
 size_t path_compact_scratch_bytes(int64_t n_list);
-hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
-                               const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, uint32_t *d_scratch,
-                               hipStream_t stream);
+hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const PathList &in, uint32_t *d_list_out,
+                               uint32_t *d_count_out, uint32_t *d_scratch, hipStream_t stream);
+// The grid of the kernels that take one lane per candidate (direct.hip, advance.hip): ceil(n_list / threads) workgroups,
+// capped at blocks_per_cu per compute unit -- a wave then walks further chunks by its number.  n_list >= 1.
+inline unsigned list_grid(uint32_t n_list, int threads, int n_cu, int blocks_per_cu) {
+  const int64_t want = ((int64_t)n_list + threads - 1) / threads, cap = (int64_t)(n_cu > 0 ? n_cu : 1) * blocks_per_cu;
+  return (unsigned)(want < cap ? want : cap);
+}
 // Trace's return expression over the first min(d_steps[i], layers) layers of the stacks float[layers][n][3] (rtmi_path_fold).
 hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                             const float *d_attenuation, float *d_radiance, hipStream_t stream);
@@ -325,10 +321,10 @@ hipError_t launch_sample_add(const FrameDev &fr, const uint32_t *d_budget, uint3
                              uint32_t *d_ray_counts, hipStream_t stream);
 // Ended paths finished and refilled in place (rtmi_path_advance; advance.hip, advance_body.h): the caller's arrays as
 // include/rtmi.h names them, every pointer checked by capi.hip.  The camera and the projection as launch_camera_rays takes
-// them.  n_list >= 1.
+// them.  list.n_list >= 1.
 struct AdvanceCall {
-  const uint32_t *budget, *list, *count;  // nullable
-  int64_t n_list;
+  const uint32_t *budget;  // nullable
+  PathList list;
   float *origins, *dirs;
   uint32_t *states, *steps;
   const float *emitted, *attenuation;

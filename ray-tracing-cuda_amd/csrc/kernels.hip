@@ -942,8 +942,19 @@ __global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlus
   occlusion_body<F>(p);
 }
 
+// rtmi_occluded_list: occlusion_kernel's twin with the LIST flag of the body set, as bounce_list_kernel is bounce_kernel's.
+// A kernel of its own, so that occlusion_kernel stays what it was; the list's words travel behind the argument block the
+// two share.  (Its name must not contain "occlusion_kernel": tests/test_occluded_host.py counts those.)
+template <uint32_t F>
+__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlusion_list_kernel(OcclusionParams p, OcclusionList l) {
+  occlusion_body<F, true>(p, l);
+}
+
+// One launcher for both.  list == nullptr: occlusion_kernel, the grid capped by n.  Else occlusion_list_kernel with the same
+// staging, LDS layout, stand-in words and sizing, the grid capped by the list's capacity (n_list > 0), not by n: a short
+// list over many paths launches few workgroups.
 hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
-                            float near_short, int n_cu, int64_t n, const float *d_o, const float *d_d,
+                            float near_short, int n_cu, int64_t n, const PathList *list, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream) {
   return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
@@ -953,50 +964,19 @@ hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float ne
     p.sc = sc;
     p.lc = query_cfg(F, sc, &lds);
     int blocks = 0;
-    const hipError_t e = query_blocks<occlusion_kernel<F>>(lds, n_cu, n, &blocks);
+    const hipError_t e = list ? query_blocks<occlusion_list_kernel<F>>(lds, n_cu, list->n_list, &blocks)
+                              : query_blocks<occlusion_kernel<F>>(lds, n_cu, n, &blocks);
     if (e != hipSuccess) return e;
     p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
     p.counts = d_counts, p.check = d_check;
     p.dummy_off = (int32_t)(lds - kQueryLdsExtra);
     for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
     p.near_short = near_short;
-    hipLaunchKernelGGL(occlusion_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p);
-    return hipGetLastError();
-  });
-}
-
-// rtmi_occluded_list: occlusion_kernel's twin with the LIST flag of the body set, as bounce_list_kernel is bounce_kernel's.
-// A kernel of its own, so that occlusion_kernel stays what it was; the list's words travel behind the argument block the
-// two share.  (Its name must not contain "occlusion_kernel": tests/test_occluded_host.py counts those.)
-template <uint32_t F>
-__global__ __launch_bounds__(RTMI_MAX_THREADS(F), RTMI_MIN_WAVES(F)) void occlusion_list_kernel(OcclusionParams p, OcclusionList l) {
-  occlusion_body<F, true>(p, l);
-}
-
-// Staging, LDS layout, stand-in words and sizing are launch_occlusion's; the grid is capped by the list's capacity
-// (n_list > 0), not by n: a short list over many paths launches few workgroups.
-hipError_t launch_occlusion_list(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
-                                 float near_short, int n_cu, int64_t n, const uint32_t *d_list, int64_t n_list,
-                                 const uint32_t *d_count, const float *d_o, const float *d_d, const float *d_t_max,
-                                 uint8_t *d_occluded, unsigned long long *d_counts, unsigned long long *d_check,
-                                 hipStream_t stream) {
-  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
-    constexpr uint32_t F = decltype(v)::value;
-    size_t lds = 0;
-    OcclusionParams p;
-    p.sc = sc;
-    p.lc = query_cfg(F, sc, &lds);
-    int blocks = 0;
-    const hipError_t e = query_blocks<occlusion_list_kernel<F>>(lds, n_cu, n_list, &blocks);
-    if (e != hipSuccess) return e;
-    p.n = n, p.origins = d_o, p.dirs = d_d, p.t_max = d_t_max, p.occluded = d_occluded;
-    p.counts = d_counts, p.check = d_check;
-    p.dummy_off = (int32_t)(lds - kQueryLdsExtra);
-    for (int k = 0; k < 3; k++) p.near_lo[k] = near_lo[k], p.near_hi[k] = near_hi[k];
-    p.near_short = near_short;
-    OcclusionList l;
-    l.list = d_list, l.count = d_count, l.n_list = (uint32_t)n_list;
-    hipLaunchKernelGGL(occlusion_list_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p, l);
+    if (list) {
+      hipLaunchKernelGGL(occlusion_list_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p, OcclusionList{*list});
+    } else {
+      hipLaunchKernelGGL(occlusion_kernel<F>, dim3(blocks), dim3(kQueryThreads), lds, stream, p);
+    }
     return hipGetLastError();
   });
 }
@@ -1034,56 +1014,45 @@ static hipError_t launch_call(const SceneDev &sc, const FrameDev &fr, bool tex_l
                               reinterpret_cast<CallParams *>(reinterpret_cast<char *>(d_work) + kCallParamsOffset));
 }
 
+// The frame of a batch of n caller rays or paths: one item each, one sample, the whole batch one rank's.
+static FrameDev batch_frame(int64_t n, int max_depth) {
+  FrameDev fr{};
+  fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
+  fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
+  fr.items = n;
+  return fr;
+}
+
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream) {
   return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
-    FrameDev fr{};
-    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = max_depth, fr.post = 0;
-    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
-    fr.items = n;
     CallExtras ex{};
     ex.rays = {d_o, d_d};
     // (64: the largest batch render_body.h's queue takes: one path per item, 16 times a pixel's atomics)
-    return launch_call<F, trace_kernel<F>>(sc, fr, tex_layers, 64, n_cu, ex, d_states, d_radiance, d_ray_counts, d_work, stream);
+    return launch_call<F, trace_kernel<F>>(sc, batch_frame(n, max_depth), tex_layers, 64, n_cu, ex, d_states, d_radiance,
+                                           d_ray_counts, d_work, stream);
   });
 }
 
 // One iteration of the trace loop per ray (rtmi_bounce; render_body.h: STEP): the item is a path, its depth is the
 // caller's business (fr.max_depth = 1 only opens the loop's depth test), and no layer is stacked -- no id stack in LDS.
-hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, float *d_o, float *d_d,
-                         uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
-                         unsigned long long *d_work, hipStream_t stream) {
+// With a list, the same step for the listed paths (rtmi_bounce_list; render_body.h: LIST).  Every array keeps n paths --
+// fr.items is n, the stride of the RNG planes -- and only the grid is sized by the list: launch_call's occupancy-sized
+// grid, capped by n_list, the host's bound on a length that stays on the device.
+hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const PathList *list,
+                         float *d_o, float *d_d, uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits,
+                         uint32_t *d_steps, unsigned long long *d_work, hipStream_t stream) {
   return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
     constexpr uint32_t F = decltype(v)::value;
-    FrameDev fr{};
-    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = 1, fr.post = 0;
-    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
-    fr.items = n;
+    const FrameDev fr = batch_frame(n, 1);
     CallExtras ex{};
     ex.step = {d_o, d_d, d_emitted, d_attenuation, d_hits, d_steps, qd};
-    return launch_call<F, bounce_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false);
-  });
-}
-
-// The same step for the listed paths (rtmi_bounce_list; render_body.h: LIST).  Every array keeps n paths -- fr.items is n,
-// the stride of the RNG planes -- and only the grid is sized by the list: launch_call's occupancy-sized grid, capped by
-// n_list, the host's bound on a length that stays on the device.
-hipError_t launch_bounce_list(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const uint32_t *d_list,
-                              int64_t n_list, const uint32_t *d_count, float *d_o, float *d_d, uint32_t *d_states,
-                              float *d_emitted, float *d_attenuation, int32_t *d_hits, uint32_t *d_steps,
-                              unsigned long long *d_work, hipStream_t stream) {
-  return with_listed<kQueryVariants>(variant, hipErrorInvalidValue, [&](auto v) {
-    constexpr uint32_t F = decltype(v)::value;
-    FrameDev fr{};
-    fr.height = 1, fr.width = 1, fr.spp = 1, fr.max_depth = 1, fr.post = 0;
-    fr.k_begin = 0, fr.k_end = 1, fr.rank = 0, fr.world = 1;
-    fr.items = n;
-    CallExtras ex{};
-    ex.step = {d_o, d_d, d_emitted, d_attenuation, d_hits, d_steps, qd};
-    ex.list = {d_list, d_count, (uint32_t)n_list};
-    return launch_call<F, bounce_list_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false, n_list);
+    if (!list) return launch_call<F, bounce_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false);
+    ex.list = *list;
+    return launch_call<F, bounce_list_kernel<F>>(sc, fr, false, 64, n_cu, ex, d_states, nullptr, nullptr, d_work, stream, false,
+                                                 list->n_list);
   });
 }
 
@@ -1108,32 +1077,25 @@ struct CompactArgs {
 };
 // (live_ray, whether a step would step a ray: path_shared.h, which rtmi_path_advance's unit includes too)
 // Entry e of the candidates: its path, and whether the next step would step it.
-__device__ __forceinline__ bool compact_live(const CompactArgs &a, uint32_t e, uint32_t end, uint32_t &path) {
+__device__ __forceinline__ bool compact_live(const CompactArgs &a, const PathList &pl, uint32_t e, uint32_t end, uint32_t &path) {
   path = 0u;
   if (e >= end) return false;
-  path = a.list_in ? a.list_in[e] : e;
+  path = list_entry(pl, e);
   if (path >= a.n) return false;  // (not a path: dropped)
   const float *o = a.origins + (int64_t)path * 3, *d = a.dirs + (int64_t)path * 3;
   return live_ray(mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]));
 }
-__device__ __forceinline__ uint32_t compact_end(const CompactArgs &a) {
-  uint32_t end = a.n_list;
-  if (a.count_in) {
-    const uint32_t c = *a.count_in;
-    end = c < end ? c : end;
-  }
-  return end;
-}
 // The live candidates of this lane's kCompactChunks entries: their paths, the chunks' wave masks, and the wave's total.
 __device__ __forceinline__ uint32_t compact_wave(const CompactArgs &a, uint32_t (&path)[kCompactChunks],
                                                  unsigned long long (&mask)[kCompactChunks]) {
-  const uint32_t end = compact_end(a);
+  const PathList pl{a.list_in, a.count_in, a.n_list};  // (the block keeps its layout; the rule is path_list.h's)
+  const uint32_t end = list_end(pl);
   // (entries below 2^31 + kCompactItems: the grid covers n_list <= 2^31 - 1)
   const uint32_t first = blockIdx.x * (uint32_t)kCompactItems + (threadIdx.x >> 6) * (uint32_t)(64 * kCompactChunks) + (threadIdx.x & 63u);
   uint32_t total = 0u;
 #pragma unroll
   for (int c = 0; c < kCompactChunks; c++) {
-    mask[c] = __builtin_amdgcn_ballot_w64(compact_live(a, first + (uint32_t)c * 64u, end, path[c]));
+    mask[c] = __builtin_amdgcn_ballot_w64(compact_live(a, pl, first + (uint32_t)c * 64u, end, path[c]));
     total += (uint32_t)__popcll(mask[c]);
   }
   return total;
@@ -1204,12 +1166,11 @@ size_t path_compact_scratch_bytes(int64_t n_list) {
   return (size_t)(blocks > 0 ? blocks : 1) * sizeof(uint32_t);
 }
 
-hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const uint32_t *d_list_in, int64_t n_list,
-                               const uint32_t *d_count_in, uint32_t *d_list_out, uint32_t *d_count_out, uint32_t *d_scratch,
-                               hipStream_t stream) {
-  if (n_list == 0) return hipMemsetAsync(d_count_out, 0, sizeof(uint32_t), stream);
-  const CompactArgs a = {d_origins, d_dirs, d_list_in, d_count_in, (uint32_t)n, (uint32_t)n_list};
-  const unsigned blocks = (unsigned)cdiv(n_list, (int64_t)kCompactItems);
+hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const PathList &in, uint32_t *d_list_out,
+                               uint32_t *d_count_out, uint32_t *d_scratch, hipStream_t stream) {
+  if (in.n_list == 0) return hipMemsetAsync(d_count_out, 0, sizeof(uint32_t), stream);
+  const CompactArgs a = {d_origins, d_dirs, in.list, in.count, (uint32_t)n, in.n_list};
+  const unsigned blocks = (unsigned)cdiv((int64_t)in.n_list, (int64_t)kCompactItems);
   hipLaunchKernelGGL(compact_count_kernel, dim3(blocks), dim3(kCompactThreads), 0, stream, a, d_scratch);
   hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kCompactScanThreads), 0, stream, (uint32_t)blocks, d_scratch, d_count_out);
   hipLaunchKernelGGL(compact_scatter_kernel, dim3(blocks), dim3(kCompactThreads), 0, stream, a, (const uint32_t *)d_scratch, d_list_out);

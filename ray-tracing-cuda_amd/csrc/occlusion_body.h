@@ -37,10 +37,8 @@ struct OcclusionParams {
 
 // LIST: rtmi_bounce_list's candidates (list, count: both nullable).  Handed over beside OcclusionParams, not inside it: the
 // argument block of occlusion_kernel stays what it was.
-struct OcclusionList {
-  const uint32_t *list, *count;
-  uint32_t n_list;
-};
+// (A type of its own over path_list.h's: it is part of the list kernels' mangled names.)
+struct OcclusionList : PathList {};
 
 // query_body.h's staging (render_body.h's prologue without the materials), as a function: the scene's pair corners,
 // top mesh nodes and leaf paths copied in, and this wave's regions of the dynamic LDS.  The caller waits at a barrier
@@ -137,6 +135,8 @@ __device__ __forceinline__ void occlusion_body(const OcclusionParams &p, const O
                             ((F & F_SGROUP) && q.cands != nullptr);  // wave-uniform
   int64_t end = p.n;
   if constexpr (LIST) {
+    // path_list.h's rule in this site's own text, here and where the entry is looked up below: the end is formed in 64
+    // bits, and with list_end and list_entry all eight occlusion_list_kernel<F> compiled to other instructions.
     end = (int64_t)l.n_list;
     if (l.count != nullptr) {  // (wave-uniform: one word, read once per wave)
       const int64_t c = (int64_t)*l.count;

@@ -6,6 +6,7 @@
 // without contraction.
 #pragma once
 // (included inside namespace rtmi, after trace_helpers.h: rng_01, unit3_rn; xorwow.h: rng_range)
+#include "path_list.h"  // the candidates of a list and their rule
 
 __device__ __forceinline__ bool finite3(V3 v) {
   return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);

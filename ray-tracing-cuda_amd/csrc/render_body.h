@@ -175,11 +175,6 @@ struct StepBufs {
   uint32_t *steps;               // nullable: += 1 per stepped path
   QueryDev qd;                   // the recording order's names of the winner (query_body.h: resolve_hit)
 };
-struct ListBufs {
-  const uint32_t *list;   // nullable: entry e of the list is path list[e] (null: path e)
-  const uint32_t *count;  // nullable: a device word that cuts the list short
-  uint32_t n_list;        // the host's bound on the list's length
-};
 struct CallExtras {
   union {  // one work-item source at a time; either way right behind RenderParams' pointers, which they are loaded with
     RayBufs rays;   // RAYS
@@ -197,7 +192,7 @@ struct CallExtras {
   // STEP (with RAYS, whose `rays` stays unset: the step reads its rays where it writes them)
   StepBufs step;
   // LIST (with STEP): where the step's items come from (rtmi_bounce_list) -- behind everything the other modes read
-  ListBufs list;
+  PathList list;  // (path_list.h)
 };
 struct CallParams {
   RenderParams rp;
@@ -230,7 +225,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const uint32_t *__restrict__ budget = nullptr,
                                             float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr,
                                             const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr,
-                                            const ListBufs *list = nullptr) {
+                                            const PathList *list = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
   static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
   static_assert(!LIST || STEP, "the list is where a step's items come from");
@@ -471,6 +466,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   bool queue_dry = false;                // (wave-uniform) ... and the queue has nothing more to give
   uint32_t list_at = 0u, list_count = 0u, list_stride = 0u;  // (wave-uniform, LIST) the wave's next chunk, the list's end, the grid's lanes
   if constexpr (LIST) {
+    // path_list.h's rule in this site's own text, here and where the entry is looked up below: with list_end and
+    // list_entry bounce_list_kernel<18> compiled to other instructions.
     list_count = list->n_list;
     if (list->count) {  // the device's count cuts the host's bound short, never the other way
       const uint32_t c = *list->count;

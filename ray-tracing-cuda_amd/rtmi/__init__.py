@@ -1058,8 +1058,7 @@ class SceneBuilder:
         abandoned = torch.zeros((1,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             _check(self.L.rtmi_intersect(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
-                                         C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(abandoned.data_ptr()), stream),
+                                         _ptr(t_max), C.c_void_p(out.data_ptr()), C.c_void_p(abandoned.data_ptr()), stream),
                    "rtmi_intersect")
         f = out.view(torch.float32)
         hits = Hits(f[:, 0], f[:, 1:3], f[:, 3:6], out[:, 6], out[:, 7], out[:, 8], out[:, 9])
@@ -1083,8 +1082,7 @@ class SceneBuilder:
         counts = torch.zeros((2,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             _check(self.L.rtmi_occluded(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
-                                        C.c_void_p(t_max.data_ptr()) if t_max is not None else None,
-                                        C.c_void_p(raw.data_ptr()), C.c_void_p(counts.data_ptr()), stream),
+                                        _ptr(t_max), C.c_void_p(raw.data_ptr()), C.c_void_p(counts.data_ptr()), stream),
                    "rtmi_occluded")
         return Occlusion(raw, counts, (origins, directions, t_max))
 
@@ -1138,8 +1136,7 @@ class SceneBuilder:
         with torch.cuda.device(dev):
             _check(self.L.rtmi_trace(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                      max_depth, C.c_void_p(states.data_ptr()), C.c_void_p(out.data_ptr()),
-                                     C.c_void_p(rays.data_ptr()) if rays is not None else None,
-                                     C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
+                                     _ptr(rays), C.c_void_p(work.data_ptr()), stream), "rtmi_trace")
         return Trace(out, rays, work, (origins, directions, states))
 
     def bounce(self, origins, directions, states, emitted=None, attenuation=None, hits=False, steps=None):
@@ -1198,9 +1195,7 @@ class SceneBuilder:
             else:
                 _check(self.L.rtmi_bounce(self.h, n, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                           C.c_void_p(states.data_ptr()), C.c_void_p(emitted.data_ptr()),
-                                          C.c_void_p(attenuation.data_ptr()),
-                                          C.c_void_p(raw.data_ptr()) if raw is not None else None,
-                                          C.c_void_p(steps.data_ptr()) if steps is not None else None,
+                                          C.c_void_p(attenuation.data_ptr()), _ptr(raw), _ptr(steps),
                                           C.c_void_p(work.data_ptr()), stream), "rtmi_bounce")
         rec = None
         if raw is not None:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-symbol comparison of two gfx950 assembly files of kernels.hip (no GPU): which kernels changed by an instruction?
+"""Per-symbol comparison of two gfx950 assembly files of one translation unit (no GPU): which kernels changed by an
+instruction?  Any unit with kernels will do: kernels.hip, direct.hip, advance.hip.
 
 Both files are made as tools/loop_census.py makes its own (the Makefile's flags, --cuda-device-only -S), one from the
 tree before a change and one from the tree after it:
@@ -8,6 +9,16 @@ tree before a change and one from the tree after it:
   (cd /tmp/parent/ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S kernels.hip -o /tmp/before.s)
   (cd ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S kernels.hip -o /tmp/after.s)
   tools/kernel_diff.py /tmp/before.s /tmp/after.s --same 'render_kernel|probe_kernel|trace_kernel|...'
+
+and for the other units, with --same '.' when no symbol at all may move:
+
+  for u in direct advance; do
+    (cd /tmp/parent/ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S $u.hip -o /tmp/before_$u.s)
+    (cd ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S $u.hip -o /tmp/after_$u.s)
+    tools/kernel_diff.py /tmp/before_$u.s /tmp/after_$u.s --same '.'
+  done
+
+The diagnostic flavour (make check1) is the same commands with -DRTMI_CHECK_MARGINS -DRTMI_CHECK_EVERY=1 behind <FLAGS>.
 
 A kernel's text is its instructions and labels with comments, directives and blank lines dropped and the function's
 number taken out of its local labels (.LBB12_3 -> .LBB_3), so that a kernel added or removed elsewhere in the unit does not
