@@ -29,7 +29,7 @@ def main():
     import rtmi
     has_features = hasattr(C.CDLL(rtmi.LIB_PATH), "rtmi_render_features")
     if not has_features:  # an older build: bind what it has
-        rtmi.SYMBOLS = [s for s in rtmi.SYMBOLS if s[0] not in ("rtmi_render_features", "rtmi_resolve_features")]
+        rtmi.SYMBOLS[:] = [s for s in rtmi.SYMBOLS if s[0] not in ("rtmi_render_features", "rtmi_resolve_features")]
     import bench
     import common
 
