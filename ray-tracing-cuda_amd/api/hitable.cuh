@@ -1,6 +1,6 @@
 #pragma once
 // Base of every recorded scene object.  In the reference a Hitable answers ray queries through
-// a virtual Hit() on the device; here intersection lives in librtmi.so (kernels.hip), and a
+// a virtual Hit() on the device; here intersection lives in librtmi.so (csrc/closest_hit.h), and a
 // Hitable is only what the flatten kernel needs to recognise an object the user's InitWorld
 // kernel created with `new`: a type tag (rt_kinds.cuh).  No virtual table is involved, so the
 // objects can be read back by plain layout.

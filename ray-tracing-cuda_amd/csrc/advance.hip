@@ -1,5 +1,5 @@
 // rtmi_path_advance: ended paths finished and refilled in place (advance_body.h).  A translation unit of its own: no
-// kernel of kernels.hip is compiled differently for it.  It shares its three rules with that unit through path_shared.h --
+// kernel of another unit is compiled differently for it.  It shares its three rules with paths.hip and frame.hip through path_shared.h --
 // "live" with rtmi_path_compact, the fold with rtmi_path_fold, the camera ray with rtmi_camera_rays -- and takes the
 // device helpers those are written in (unit3_rn, rng_01) from trace_helpers.h, none of whose other functions it uses.
 #include <hip/hip_runtime.h>

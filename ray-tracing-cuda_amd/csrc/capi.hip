@@ -617,7 +617,7 @@ int64_t rtmi_debug_pair_slabs(const rtmi_scene *sp, int64_t cap, uint32_t *slabs
   return n;
 }
 
-// Diagnostic (as above): 1 when the slab table's reach covers a render from the scene's camera (kernels.hip:
+// Diagnostic (as above): 1 when the slab table's reach covers a render from the scene's camera (render.hip:
 // slab_reach_covers, a condition of the fast list kernels), else 0.
 int rtmi_debug_slab_reach(const rtmi_scene *sp) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
@@ -627,7 +627,7 @@ int rtmi_debug_slab_reach(const rtmi_scene *sp) {
 }
 
 // Diagnostic (as above): bytes of dynamic LDS one workgroup of `threads` lanes asks for when this scene is rendered at
-// max_depth (kernels.hip: make_cfg).  A compute unit has 160 KiB.
+// max_depth (render.hip: make_cfg).  A compute unit has 160 KiB.
 int64_t rtmi_debug_render_lds_bytes(const rtmi_scene *sp, int max_depth, int threads) {
   if (!sp || max_depth < 0 || threads < 64 || threads % 64) return fail(RTMI_ERR_INVALID, "bad arguments");
   Scene tmp;
@@ -1051,7 +1051,7 @@ static int run_plan(const RenderPlan &p, uint32_t *d_states, float *d_tiles, uin
   // shards on one device) then share nothing but the read-only scene.  Without one the scene's own (a cache, not
   // scene state) is used, which ties renders of this scene to one at a time.
   unsigned long long *counters = p.user_scratch ? reinterpret_cast<unsigned long long *>(p.user_scratch) : s->d_counters;
-  // the kernels' argument blocks (kernels.hip: RenderParams): probe pass, real pass
+  // the kernels' argument blocks (render_body.h: RenderParams): probe pass, real pass
   char *params = p.user_scratch ? reinterpret_cast<char *>(p.user_scratch) + sl.params
                                 : reinterpret_cast<char *>(s->d_counters) + kCounterBytes;
   void *scratch = p.user_scratch;

@@ -1,5 +1,5 @@
 // Next-event estimation for wavefront paths: the light table (host, at commit), the step kernel and the fold
-// (rtmi_direct_sample, rtmi_direct_sample_mis, rtmi_path_fold_direct; direct_body.h).  A translation unit of its own: no kernel of kernels.hip is
+// (rtmi_direct_sample, rtmi_direct_sample_mis, rtmi_path_fold_direct; direct_body.h).  A translation unit of its own: no kernel of another unit is
 // compiled differently for it.
 #include "direct_body.h"
 
@@ -118,7 +118,7 @@ hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_
 }
 
 // ------------------------------------------------------------------ the fold (rtmi_path_fold_direct)
-// path_fold_kernel (kernels.hip) with T[k] for E[k]: one lane per path, a layer's reads coalesced over n.
+// path_fold_kernel (paths.hip) with T[k] for E[k]: one lane per path, a layer's reads coalesced over n.
 __global__ __launch_bounds__(256) void path_fold_direct_kernel(int64_t n, uint32_t layers, const float *__restrict__ dirs,
                                                                 const uint32_t *__restrict__ steps, const float *__restrict__ emitted,
                                                                 const float *__restrict__ attenuation, const float *__restrict__ direct,

@@ -1,4 +1,4 @@
-// Which pixel a work item is (rtmi_frame_pixel_of): one definition for kernels.hip and advance.hip.
+// Which pixel a work item is (rtmi_frame_pixel_of): one definition for every unit that asks.
 #pragma once
 // (included inside namespace rtmi, after scene_dev.h: FrameDev)
 

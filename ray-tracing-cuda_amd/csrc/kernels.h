@@ -99,7 +99,7 @@ constexpr bool folds_by_min(uint32_t m) { return (m & kFastCommon) == kFastCommo
 //      wave_ballot_nz ...) where __all / ballot send it through a register of 0 / 1 and a second compare.
 //   2  trims_mul24: the LDS address of a staged TriPts record is one 24-bit multiply-add (full rate; the 32-bit
 //      multiply issues at a quarter), kept opaque so that it is formed once (closest_hit.h: load_tri_pts).  The
-//      product's bound is asserted where the layout is made (kernels.hip: make_cfg).  The id stack's addresses keep
+//      product's bound is asserted where the layout is made (render.hip: make_cfg).  The id stack's addresses keep
 //      the 32-bit multiply: with the 24-bit one the chains kernel spilled a sixth scalar (NOTES.md).
 //   4  trims_fold_rgb: the radiance fold reads a layer's colour from a table of 16 rows of 16 bytes at a fixed LDS
 //      address (kFoldRgbOff, staged from the material records), so a nibble of the id stack is its row's address after
@@ -184,7 +184,7 @@ hipError_t launch_tile_order(uint32_t *d_ray_counts, int n_tiles, uint32_t *d_co
 
 // The per-quarter-tile order the trace kernel's queue follows (4 * n_tiles words): d_order's tiles with their quarters in
 // sequence, or -- d_work != nullptr: mesh frames with a cost probe -- the quarters sorted by probed cost and dealt to the
-// 64-item blocks in a snake (kernels.hip).  d_qcost / d_qsorted: 4 * n_tiles words of scratch each, d_qmax one word.
+// 64-item blocks in a snake (sched.hip).  d_qcost / d_qsorted: 4 * n_tiles words of scratch each, d_qmax one word.
 hipError_t launch_quarter_order(const uint32_t *d_order, const uint32_t *d_work, const uint32_t *d_rays, int n_tiles,
                                 uint32_t *d_qcost, uint32_t *d_qsorted, uint32_t *d_qmax, uint32_t *d_qmap, hipStream_t stream);
 
@@ -200,24 +200,24 @@ hipError_t launch_chain_plan(const uint32_t *d_order, const uint32_t *d_cost, in
 hipError_t launch_untile(const FrameDev &fr, const float *d_tiles, float *d_image, hipStream_t stream);
 hipError_t launch_untile_u32(const FrameDev &fr, const uint32_t *d_tiles, uint32_t *d_image, hipStream_t stream);
 hipError_t launch_post(float *d_img, int64_t n, int spp, hipStream_t stream);
-// Batched closest-hit queries (rtmi_intersect; kernels.hip: query_kernel).  d_hits: n x 12 words (rtmi_hit);
+// Batched closest-hit queries (rtmi_intersect; queries.hip: query_kernel).  d_hits: n x 12 words (rtmi_hit);
 // d_abandoned, d_t_max, d_check nullable (d_check: -DRTMI_CHECK_MARGINS builds only, {re-done, disagreements}).
 uint32_t pick_query_variant(uint32_t features);
 hipError_t launch_query(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const float *d_o,
                         const float *d_d, const float *d_t_max, int32_t *d_hits, unsigned long long *d_abandoned,
                         unsigned long long *d_check, hipStream_t stream);
-// Batched any-hit visibility queries (rtmi_occluded; kernels.hip: occlusion_kernel), on the query variants.
+// Batched any-hit visibility queries (rtmi_occluded; queries.hip: occlusion_kernel), on the query variants.
 // d_occluded: n bytes; d_t_max, d_counts ({abandoned, fallback rays}), d_check nullable (as launch_query).  Rays whose
 // origin lies inside [near_lo, near_hi] (the padded union of the meshes' root bounds) and whose t_max is not below
 // near_short start the walk from +inf.
-// list (null: every ray): the same query for the listed paths only (rtmi_occluded_list; kernels.hip:
+// list (null: every ray): the same query for the listed paths only (rtmi_occluded_list; queries.hip:
 // occlusion_list_kernel): launch_bounce's list, entries need not be distinct; every array keeps n paths, an unlisted
 // path keeps its byte.  The grid is then sized by list->n_list >= 1.
 hipError_t launch_occlusion(uint32_t variant, const SceneDev &sc, const float near_lo[3], const float near_hi[3],
                             float near_short, int n_cu, int64_t n, const PathList *list, const float *d_o, const float *d_d,
                             const float *d_t_max, uint8_t *d_occluded, unsigned long long *d_counts,
                             unsigned long long *d_check, hipStream_t stream);
-// Radiance of caller rays (rtmi_trace; kernels.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
+// Radiance of caller rays (rtmi_trace; calls.hip: trace_kernel), on the query variants.  d_work: RTMI_TRACE_WORK_WORDS
 // words, zeroed in stream order before the call -- [0] abandoned mesh searches, [1] closest-hit queries, [2] the queue's
 // cursor, and from byte kCallParamsOffset the kernel's argument block (written in stream order just before the launch).
 constexpr size_t kCallParamsOffset = 256;  // (a 128-byte line of its own, away from the counter words)
@@ -226,9 +226,9 @@ constexpr size_t kCallParamsOffset = 256;  // (a 128-byte line of its own, away 
 hipError_t launch_trace(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
                         const float *d_o, const float *d_d, uint32_t *d_states, float *d_radiance,
                         uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
-// One iteration of Trace's loop per ray (rtmi_bounce; kernels.hip: bounce_kernel), on the query variants: rays and states
+// One iteration of Trace's loop per ray (rtmi_bounce; calls.hip: bounce_kernel), on the query variants: rays and states
 // are read and written in place; d_hits (n x 12 words, rtmi_hit) and d_steps nullable; d_work as launch_trace's, [1] = the
-// paths stepped.  list (null: every path): the same step for the candidates of the list only (rtmi_bounce_list; kernels.hip:
+// paths stepped.  list (null: every path): the same step for the candidates of the list only (rtmi_bounce_list; calls.hip:
 // bounce_list_kernel; path_list.h); every array keeps n paths.  list->n_list >= 1.
 hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &qd, int n_cu, int64_t n, const PathList *list,
                          float *d_o, float *d_d, uint32_t *d_states, float *d_emitted, float *d_attenuation, int32_t *d_hits,
@@ -238,6 +238,8 @@ hipError_t launch_bounce(uint32_t variant, const SceneDev &sc, const QueryDev &q
 size_t path_compact_scratch_bytes(int64_t n_list);
 hipError_t launch_path_compact(int64_t n, const float *d_origins, const float *d_dirs, const PathList &in, uint32_t *d_list_out,
                                uint32_t *d_count_out, uint32_t *d_scratch, hipStream_t stream);
+// Workgroups of b lanes over a items (the launchers of frame.hip and paths.hip).
+static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // The grid of the kernels that take one lane per candidate (direct.hip, advance.hip): ceil(n_list / threads) workgroups,
 // capped at blocks_per_cu per compute unit -- a wave then walks further chunks by its number.  n_list >= 1.
 inline unsigned list_grid(uint32_t n_list, int threads, int n_cu, int blocks_per_cu) {
@@ -264,7 +266,7 @@ hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_
 hipError_t launch_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                                    const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded,
                                    float *d_radiance, hipStream_t stream);
-// Per-pixel sample budgets (rtmi_render_budget; kernels.hip: budget_kernel), on the query variants with F_DEFOCUS added.
+// Per-pixel sample budgets (rtmi_render_budget; calls.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).
 hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, const FrameDev &fr,
@@ -286,7 +288,7 @@ hipError_t launch_resolve(const FrameDev &fr, const float *d_sum, const uint32_t
 // Per-item variance of the mean from the budget sums (rtmi_resolve_variance; include/rtmi.h states the rule), tile-major.
 hipError_t launch_resolve_variance(const FrameDev &fr, const float *d_sum, const float *d_sq, const uint32_t *d_samples,
                                    float *d_var, hipStream_t stream);
-// The a-trous filter (rtmi_denoise; denoise.hip): row-major whole-frame buffers, every pointer checked by capi.hip.
+// The a-trous filter (rtmi_denoise; filters.hip): row-major whole-frame buffers, every pointer checked by capi.hip.
 struct DenoiseCall {
   int height, width, iterations, normal_squarings, demodulate;
   float sigma_color, sigma_depth;
@@ -296,7 +298,7 @@ struct DenoiseCall {
 };
 size_t denoise_scratch_bytes(int height, int width);
 hipError_t launch_denoise(const DenoiseCall &d, hipStream_t stream);
-// Temporal accumulation (rtmi_accumulate; accumulate_body.h): row-major whole-frame buffers, every pointer checked by
+// Temporal accumulation (rtmi_accumulate; filters.hip): row-major whole-frame buffers, every pointer checked by
 // capi.hip, which also forms the camera terms in binary64 and rounds them.
 struct AccumulateCall {
   int height, width;
@@ -310,7 +312,7 @@ struct AccumulateCall {
 };
 size_t history_bytes(int height, int width);
 hipError_t launch_accumulate(const AccumulateCall &c, hipStream_t stream);
-// The render's primary rays of one sample (rtmi_camera_rays; camera_body.h): kind = RTMI_PROJ_*, w = the camera frame's
+// The render's primary rays of one sample (rtmi_camera_rays; frame.hip): kind = RTMI_PROJ_*, w = the camera frame's
 // third axis, d_budget nullable.  Inactive items get six +0.0f and keep their state.
 hipError_t launch_camera_rays(const FrameDev &fr, const CameraDev &cam, const float w[3], int kind, float fov,
                               const uint32_t *d_budget, uint32_t sample, uint32_t *d_states, float *d_origins,
@@ -342,7 +344,7 @@ hipError_t copy_wave_stats(unsigned long long *host, size_t bytes);  // diagnost
 #ifdef RTMI_CHECK_MARGINS
 hipError_t launch_add_one(unsigned long long *d_word, hipStream_t stream);  // *d_word += 1 (check builds' test hook)
 #endif
-// d_bad[4]: see arithmetic_selftest in kernels.hip.
+// d_bad[4]: see arithmetic_selftest in frame.hip.
 hipError_t launch_arithmetic_selftest(unsigned long long *d_bad, hipStream_t stream);
 
 }  // namespace rtmi

@@ -148,7 +148,8 @@ struct MeshStats {
   unsigned long long calib;  // two stamps back to back, once per search: what a stamp costs
   unsigned long long cyc[11];  // [9] search setup before the first step, [10] between steps (loop control)
 };
-__device__ unsigned long long g_wave_stats[16384][16];  // per wave: life, cyc[0..8], wave_queries, node_steps, face_steps
+// (internal linkage: every unit that includes this header has its own; rtmi_debug_wave_stats reads render.hip's)
+static __device__ unsigned long long g_wave_stats[16384][16];  // per wave: life, cyc[0..8], wave_queries, node_steps, face_steps
 __device__ __forceinline__ unsigned long long stat_real() {
   __builtin_amdgcn_sched_barrier(0);
   unsigned long long t;

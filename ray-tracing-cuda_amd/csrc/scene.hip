@@ -102,7 +102,7 @@ static PairSlab pair_slab(const PairBox &bx, float list_mag) {
     r.c[a] = c, r.h[a] = hf;
   }
   // unbounded (push_pair: a thin triangle), or too large for the arithmetic above: a candidate of every ray -- with
-  // c = 0 the slab test's near and far times are -+inf whatever the ray (its k is finite: kernels.hip, fast_path_facts)
+  // c = 0 the slab test's near and far times are -+inf whatever the ray (its k is finite: render.hip, fast_path_facts)
   bool bounded = true;
   for (int a = 0; a < 3; a++) bounded = bounded && std::isfinite(r.c[a]) && std::isfinite(r.h[a]);
   if (!bounded)

@@ -93,7 +93,7 @@ struct PairBox {  // 32 B
 // pair is c = 0, h = +inf.  The table lies in the allocation of `pair_boxes`, behind its padding record: record i at
 // pair_boxes + n_pairs + 1 + i (pair_slabs_of), one inert record of padding at its end too.  SceneDev, which every
 // kernel's argument block begins with, keeps its layout: a launch of one of those kernels writes the table's address
-// into its block's `pair_boxes` (kernels.hip: launch_render) -- they never read a PairBox, and read the records as they
+// into its block's `pair_boxes` (render.hip: launch_render) -- they never read a PairBox, and read the records as they
 // would read those, eight words at a wave-uniform index: no register holds a second base or the pair count.
 struct PairSlab {  // 32 B
   float c[3], h[3];

@@ -9,7 +9,7 @@ import rtmi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECK_LIB = os.path.join(ROOT, "ray-tracing-cuda_amd", "lib", "librtmi_check1.so")
-QUERY_VARIANTS = 8  # kernels.hip: kQueryVariants
+QUERY_VARIANTS = 8  # launch_cfg.h: kQueryVariants
 F_DEFOCUS = 32      # scene_dev.h
 OK, ERR_INVALID, ERR_DEPTH = 0, -1, -5  # include/rtmi.h
 LIBS = [rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")]

@@ -9,7 +9,7 @@ import rtmi
 from querylib import glm_normalize
 
 P = rtmi.PATH_COMPACT_ITEMS  # list entries one workgroup of the compaction handles (include/rtmi.h: RTMI_PATH_COMPACT_ITEMS)
-SCAN_THREADS = 256           # kernels.hip: kCompactScanThreads -- each lane of the scan sums ceil(workgroups / 256) counts
+SCAN_THREADS = 256           # paths.hip: kCompactScanThreads -- each lane of the scan sums ceil(workgroups / 256) counts
 CANARY_INDEX = 0x5a5a5a5a
 CANARY_F = np.float32(-7.25)
 

@@ -70,19 +70,32 @@ def rel_l2(a, b):
     return float(np.sqrt(((a - b) ** 2).sum()) / max(np.sqrt((b ** 2).sum()), 1e-30))
 
 
-def kernel_notes(lib):
-    """Kernel name -> its block of metadata notes (llvm-readelf --notes) in the gfx950 code object embedded in the
-    shared library at path `lib`."""
+def code_object_notes(lib):
+    """One {kernel name: its block of metadata notes (llvm-readelf --notes)} per gfx950 code object embedded in the
+    shared library at path `lib`: each translation unit with kernels has a bundle of its own in .hip_fatbin."""
     llvm = "/opt/rocm/lib/llvm/bin"
     assert os.path.exists(llvm + "/llvm-readelf"), "llvm-readelf reads the code object's metadata"
     assert os.path.exists(lib), lib + " missing: __graft_entry__.build() builds it"
+    out = []
     with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co.o")
+        fat = os.path.join(tmp, "fatbin")
         subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-        subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
-    return {re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]}
+        data = open(fat, "rb").read()
+        starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data)]
+        for k, at in enumerate(starts):
+            part, co = os.path.join(tmp, "part%d" % k), os.path.join(tmp, "co%d.o" % k)
+            with open(part, "wb") as f:
+                f.write(data[at:starts[k + 1] if k + 1 < len(starts) else len(data)])
+            subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
+                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
+            notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
+            out.append({re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]})
+    return out
+
+
+def kernel_notes(lib):
+    """Kernel name -> its block of metadata notes, over every gfx950 code object of the shared library at path `lib`."""
+    return {name: blk for notes in code_object_notes(lib) for name, blk in notes.items()}
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))

@@ -21,32 +21,6 @@ LAMBERTIAN, LIGHT = 0, 3  # scene_dev.h: MatKind
 SURFACE_KINDS = (rtmi.RTMI_HIT_TRIANGLE, rtmi.RTMI_HIT_PARALLELOGRAM, rtmi.RTMI_HIT_PARALLELEPIPED)
 
 
-# ------------------------------------------------------------------ kernel metadata of every code object
-def kernel_notes_every_object(lib):
-    """common.kernel_notes over EVERY gfx950 code object of the shared library at `lib`: each translation unit with kernels
-    has a bundle of its own in .hip_fatbin, and common.kernel_notes reads the first."""
-    import os
-    import re
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        fat = os.path.join(tmp, "fatbin")
-        subprocess.check_call([llvm + "/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-        data = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data)]
-        for k, at in enumerate(starts):
-            part, co = os.path.join(tmp, "part%d" % k), os.path.join(tmp, "co%d.o" % k)
-            with open(part, "wb") as f:
-                f.write(data[at:starts[k + 1] if k + 1 < len(starts) else len(data)])
-            subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part,
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stderr=subprocess.DEVNULL)
-            notes = subprocess.check_output([llvm + "/llvm-readelf", "--notes", co], text=True)
-            out.update({re.search(r"\.name:\s+(\S+)", blk).group(1): blk for blk in notes.split("- .agpr_count")[1:]})
-    return out
-
-
 # ------------------------------------------------------------------ the generator (XORWOW, curand_uniform)
 def draw01(st, idx):
     """CudaRandomFloat(0, 1) for the rows idx of st ((n, 6) uint32: d, v0..v4), advanced in place: x * 2^-32 + 2^-33 in

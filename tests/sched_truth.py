@@ -1,4 +1,4 @@
-"""The contract of the scheduler's plan kernels (csrc/kernels.hip: tile_cost, tile_order, head_scan / count / plan /
+"""The contract of the scheduler's plan kernels (csrc/sched.hip: tile_cost, tile_order, head_scan / count / plan /
 scatter, expand_order, quarter_cost / sort, snake_map, chain_link), restated in numpy with no GPU.
 
 Every integer quantity is computed in int64 (the kernels: uint32 with 64-bit products); `chain_fut` alone is binary32,

@@ -31,7 +31,7 @@ def test_entries_are_exported_by_both_builds_declared_and_bound():
     for name in NEW:
         assert name in names and re.search(r"\b%s\(" % name, header), name
     assert int(re.search(r"#define RTMI_PATH_COMPACT_ITEMS (\d+)", header).group(1)) == rtmi.PATH_COMPACT_ITEMS == P
-    src = open(os.path.join(ROOT, "ray-tracing-cuda_amd", "csrc", "kernels.hip")).read()
+    src = open(os.path.join(ROOT, "ray-tracing-cuda_amd", "csrc", "paths.hip")).read()
     assert re.search(r"kCompactScanThreads = %d;" % SCAN_THREADS, src)  # what the GPU test's sizes are worked out from
 
 

@@ -9,7 +9,7 @@ import pytest
 
 import rtmi
 from abi_host import DUMMY, LIBS, ROOT, _count, _refused
-from directlib import kernel_notes_every_object
+from common import kernel_notes
 
 ARRAYS = ("d_origins", "d_dirs", "d_hits", "d_steps", "d_emitted", "d_attenuation", "d_light_states", "d_flags",
           "d_shadow_origins", "d_shadow_dirs", "d_shadow_t_max", "d_direct")
@@ -80,7 +80,7 @@ def test_binding_refuses_a_carry_without_mis_and_a_wrong_direct():
 def test_kernel_metadata(lib):
     """direct_sample_mis_kernel is direct_sample_kernel's shape: 4 KiB of LDS for the cdf, no scratch, no spill, and no more
     vector registers than 64 (eight waves per SIMD), as its parent."""
-    notes = kernel_notes_every_object(lib)
+    notes = kernel_notes(lib)
     mis = [v for k, v in notes.items() if "direct_sample_mis_kernel" in k]
     par = [v for k, v in notes.items() if "direct_sample_kernel" in k]
     assert len(mis) == 1 and len(par) == 1

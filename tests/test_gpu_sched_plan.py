@@ -1,4 +1,4 @@
-"""The eleven kernels that plan a scheduled render (csrc/kernels.hip: tile_cost, tile_order, head_scan / count / plan /
+"""The eleven kernels that plan a scheduled render (csrc/sched.hip: tile_cost, tile_order, head_scan / count / plan /
 scatter, expand_order, quarter_cost / sort, snake_map, chain_link) against tests/sched_truth.py, through
 rtmi_debug_schedule -- the scheduler step of rtmi_render_ex on synthetic counts -- and, for run_plan's wiring of it, on
 the scratch one list render and one mesh render leave behind.

@@ -284,7 +284,7 @@ def test_trace_kernels_declare_no_static_lds():
     that is only right while the array starts at LDS address 0, i.e. while no trace kernel declares static LDS
     (group_segment_fixed_size == 0 in the code object's metadata).  Checked on the product AND on the diagnostic
     margin-check build (a __shared__ added under one of its macros would make the fold read wrong ids without a fault);
-    the launcher asks the same of whatever build is loaded (kernels.hip: hipFuncGetAttributes, once per variant)."""
+    the launcher asks the same of whatever build is loaded (launch_cfg.h: hipFuncGetAttributes, once per variant)."""
     for lib in (rtmi.LIB_PATH, os.path.join(os.path.dirname(rtmi.LIB_PATH), "librtmi_check1.so")):
         seen = 0
         for name, blk in common.kernel_notes(lib).items():

@@ -14,7 +14,7 @@ import rtmi
 from abi_host import DUMMY, ERR_DEPTH, ERR_INVALID, LIBS, ROOT, _count, _frame, _refused
 from advancelib import IN_FLIGHT, Wavefront, advance, camera_ray, draw01, live_items, toy_step
 from bouncelib import fold
-from directlib import kernel_notes_every_object
+from common import kernel_notes
 from parity import bits
 
 LIB_DIR = os.path.dirname(rtmi.LIB_PATH)
@@ -145,7 +145,7 @@ def test_kernels_spill_no_vgpr_and_use_no_scratch_or_lds():
     """Two kernels in both builds: path_advance_kernel<false> for the CAMERA and ORTHOGRAPHIC kinds, without the binary64
     sines and cosines of the curved kinds and at four waves per SIMD or more, and path_advance_kernel<true>."""
     for lib in LIBS:
-        blk = {n: b for n, b in kernel_notes_every_object(lib).items() if "path_advance_kernel" in n}
+        blk = {n: b for n, b in kernel_notes(lib).items() if "path_advance_kernel" in n}
         assert len(blk) == 2, (lib, sorted(blk))
         for n, b in blk.items():
             assert _count(b, "vgpr_spill_count") == 0, (lib, n)

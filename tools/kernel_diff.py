@@ -1,22 +1,19 @@
 #!/usr/bin/env python3
-"""Per-symbol comparison of two gfx950 assembly files of one translation unit (no GPU): which kernels changed by an
-instruction?  Any unit with kernels will do: kernels.hip, direct.hip, advance.hip.
+"""Per-symbol comparison of two gfx950 assembly files (no GPU): which kernels changed by an instruction?  Any unit with
+kernels will do: render.hip, calls.hip, queries.hip, sched.hip, frame.hip, paths.hip, filters.hip, direct.hip, advance.hip.
 
 Both files are made as tools/loop_census.py makes its own (the Makefile's flags, --cuda-device-only -S), one from the
-tree before a change and one from the tree after it:
+tree before a change and one from the tree after it, unit by unit, with --same '.' when no symbol at all may move:
 
   git archive <parent> ray-tracing-cuda_amd/csrc include | tar -x -C /tmp/parent
-  (cd /tmp/parent/ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S kernels.hip -o /tmp/before.s)
-  (cd ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S kernels.hip -o /tmp/after.s)
-  tools/kernel_diff.py /tmp/before.s /tmp/after.s --same 'render_kernel|probe_kernel|trace_kernel|...'
-
-and for the other units, with --same '.' when no symbol at all may move:
-
-  for u in direct advance; do
+  for u in render calls queries sched frame paths filters direct advance; do
     (cd /tmp/parent/ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S $u.hip -o /tmp/before_$u.s)
     (cd ray-tracing-cuda_amd/csrc && hipcc <FLAGS> --cuda-device-only -S $u.hip -o /tmp/after_$u.s)
-    tools/kernel_diff.py /tmp/before_$u.s /tmp/after_$u.s --same '.'
+    tools/kernel_diff.py /tmp/before_$u.s /tmp/after_$u.s --same 'render_kernel|probe_kernel'
   done
+
+A kernel that moved from one unit to another is compared through the units' assembly files concatenated (cat) on
+either side: every symbol is found by its name, wherever in the text it stands.
 
 The diagnostic flavour (make check1) is the same commands with -DRTMI_CHECK_MARGINS -DRTMI_CHECK_EVERY=1 behind <FLAGS>.
 

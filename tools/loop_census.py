@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Static instruction census of one kernel of kernels.hip, whole body and main loop.
+"""Static instruction census of one kernel of a translation unit of csrc/ (--unit, default render), whole body and main loop.
 
-Builds ray-tracing-cuda_amd/csrc/kernels.hip to gfx950 assembly with the Makefile's flags (no GPU needed) -- or reads
+Builds ray-tracing-cuda_amd/csrc/<unit>.hip to gfx950 assembly with the Makefile's flags (no GPU needed) -- or reads
 an assembly file made that way (--asm) -- and prints, for every kernel whose symbol holds --kernel:
 
   * the code object's metadata: VGPRs, SGPRs, spilled VGPR dwords / SGPRs, scratch bytes, static LDS, occupancy;
@@ -11,7 +11,7 @@ an assembly file made that way (--asm) -- and prints, for every kernel whose sym
 These are STATIC counts -- instructions in the text, not instructions executed: a branch not taken, or a loop inside the
 main loop, counts once.  They say what the compiler emitted for a mode, not what a query costs.
 
-  tools/loop_census.py --kernel 'render_kernelILj2ELj0E' [--asm kernels.s] [--label before] [--json out.json]
+  tools/loop_census.py --kernel 'render_kernelILj2ELj0E' [--unit render] [--asm render.s] [--label before] [--json out.json]
 
 --json merges the result into the file under --label (profiles/list_fast_census.json keeps before and after).
 """
@@ -37,9 +37,9 @@ def makefile_flags():
     raise SystemExit("no FLAGS in csrc/Makefile")
 
 
-def build_asm(out, extra):
+def build_asm(unit, out, extra):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc] + makefile_flags() + extra + ["--cuda-device-only", "-S", "kernels.hip", "-o", out]
+    cmd = [hipcc] + makefile_flags() + extra + ["--cuda-device-only", "-S", unit + ".hip", "-o", out]
     subprocess.run(cmd, cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
 
 
@@ -135,7 +135,8 @@ def metadata(asm_text, symbol):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", required=True, help="substring of the mangled kernel symbol")
-    ap.add_argument("--asm", help="assembly of kernels.hip made with the Makefile's flags (default: build it)")
+    ap.add_argument("--unit", default="render", help="the translation unit of csrc/ to build: render, calls, queries, ...")
+    ap.add_argument("--asm", help="assembly of a unit made with the Makefile's flags (default: build --unit)")
     ap.add_argument("--extra", default="", help="extra hipcc flags for the build")
     ap.add_argument("--json", help="merge the result into this JSON file")
     ap.add_argument("--label", default="census", help="key of the result in --json")
@@ -143,8 +144,8 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         path = a.asm
         if not path:
-            path = os.path.join(tmp, "kernels.s")
-            build_asm(path, a.extra.split())
+            path = os.path.join(tmp, a.unit + ".s")
+            build_asm(a.unit, path, a.extra.split())
         text = open(path).read()
     found = {k: v for k, v in kernel_bodies(text).items() if a.kernel in k}
     if not found:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Offline: how evenly does the planned-chain deal (kernels.hip: chain_link_kernel -- tiles in longest-first order dealt
+"""Offline: how evenly does the planned-chain deal (sched.hip: chain_link_kernel -- tiles in longest-first order dealt
 to the SIMDs in a snake, a SIMD's share to its six waves in a snake again) load the SIMDs, as a function of how good the
 cost estimate is?  Input: the per-pixel ray counts of real frames (gpurun_out/shard_waves_*.npz, written by
 tools/gpu_shard_waves.py).  A pixel's estimate from s1 probe samples is modelled as true x (1 + 1.2 / sqrt(s1) x N(0, 1));
