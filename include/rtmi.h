@@ -388,6 +388,13 @@ int rtmi_render_mode_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_ren
  * kernel's).  RTMI_ERR_INVALID for a null argument. */
 #define RTMI_FAST_PATH_FACTS 14
 int rtmi_fast_path_kernel(const int32_t facts[RTMI_FAST_PATH_FACTS]);
+/* Which trace kernels a render of this frame would launch, as the compile-time mode words they were built with (csrc/
+ * kernels.h: PIN_*): out = {the first pass's (0 also when the frame has none), the finishing launch's}.  0 is the general
+ * kernel; 383 draws from the work queue and 255 walks planned chains, as rtmi_fast_path_kernel's 1 and 2; with 512 added
+ * (895, 767) it is the same kernel compiled for a scene whose materials are all Lambertians or lights without image
+ * textures.  One more material of another kind anywhere in the table, used or not, and the scene keeps 383 / 255.
+ * Informational: same pixels either way.  Added without a version change: a caller detects it by the symbol. */
+int rtmi_render_pins(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, uint32_t out[2]);
 /* rtmi_render with per-call options (opts == NULL: the defaults). */
 int rtmi_render_ex(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_opts *opts, void *d_states,
                    float *d_tiles, uint32_t *d_ray_counts, void *stream);

@@ -430,6 +430,14 @@ int rtmi_camera_get(const rtmi_scene *s, float out[21]) {
   return RTMI_OK;
 }
 
+// SceneDev::diffuse_only: every material is a Lambertian or a light, and none takes its colour from an image texture.
+// Such a scene's fast list launches get the kernels compiled with PIN_DIFFUSE (kernels.h: render_pins).
+static int diffuse_only(const std::vector<MatRec> &mats) {
+  for (const MatRec &m : mats)
+    if ((m.kind != MAT_LAMBERTIAN && m.kind != MAT_LIGHT) || m.tex >= 0) return 0;
+  return 1;
+}
+
 int rtmi_scene_commit(rtmi_scene *sp) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
   Scene *s = S(sp);
@@ -511,6 +519,7 @@ int rtmi_scene_commit(rtmi_scene *sp) {
       if (bits >> 31) d.unsigned_colours = 0;
     }
   }
+  d.diffuse_only = diffuse_only(s->mat_recs);
   d.cam = s->cam;
   s->dev = d;
   QueryDev q{};  // (rtmi_intersect only)
@@ -624,6 +633,14 @@ int rtmi_debug_slab_reach(const rtmi_scene *sp) {
   Scene tmp;
   if (int rc = flattened(sp, &tmp)) return rc;
   return slab_reach_covers(tmp.list_mag, tmp.cam) ? 1 : 0;
+}
+
+// Diagnostic (as above): SceneDev::diffuse_only as a commit of this scene would set it.
+int rtmi_debug_diffuse_only(const rtmi_scene *sp) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  Scene tmp;
+  if (int rc = flattened(sp, &tmp)) return rc;
+  return diffuse_only(tmp.mat_recs);
 }
 
 // Diagnostic (as above): bytes of dynamic LDS one workgroup of `threads` lanes asks for when this scene is rendered at
@@ -989,6 +1006,16 @@ int rtmi_render_mode_ex(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_re
   const int32_t out[RTMI_MODE_FIELDS] = {p.scheduled, p.scheduled ? p.probe_spp : 0, p.resume, p.chains, p.prio ? p.tune.prio_every : 0,
                                          p.ls.lane_stride, p.waves, p.d.local_tiles, p.finish_fast != 0u};
   for (int i = 0; i < n && i < RTMI_MODE_FIELDS; i++) dst[i] = out[i];
+  return RTMI_OK;
+}
+
+int rtmi_render_pins(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_opts *opts, uint32_t out[2]) {
+  if (!sp || !out) return fail(RTMI_ERR_INVALID, "null argument");
+  RenderPlan p;
+  int rc;
+  if ((rc = render_prologue(sp, f, opts, &p)) || (rc = plan_render(&p))) return rc;
+  out[0] = p.scheduled ? render_pins(p.first_fast, p.s->dev) : 0u;
+  out[1] = render_pins(p.finish_fast, p.s->dev);
   return RTMI_OK;
 }
 

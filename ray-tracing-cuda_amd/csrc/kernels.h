@@ -69,6 +69,7 @@ enum : uint32_t {
   PIN_PRIORITIES = 1u << 6,    // lc.prio_tab != nullptr
   PIN_CHAINS = 1u << 7,        // planned chains on a resumed pass: lc.chain_next, lc.tile_cost, ray_counts set, fr.k_begin > 0
   PIN_QUEUE = 1u << 8,         // the wave draws from the queue: lc.chain_next == nullptr
+  PIN_DIFFUSE = 1u << 9,       // sc.diffuse_only: every material is a Lambertian or a light, none textured (with kFastCommon)
 };
 constexpr uint32_t kFastCommon = PIN_NIBBLE_IDS | PIN_LDS_TABLES | PIN_UNSIGNED | PIN_DET_SAFE | PIN_POW2_FRAME |
                                  PIN_EVERY_LANE | PIN_PRIORITIES;
@@ -112,6 +113,24 @@ constexpr bool folds_by_min(uint32_t m) { return (m & kFastCommon) == kFastCommo
 constexpr bool trims_votes(uint32_t m) { return (RTMI_TRIM & 1) && (m & kFastCommon) == kFastCommon; }
 constexpr bool trims_mul24(uint32_t m) { return (RTMI_TRIM & 2) && (m & kFastCommon) == kFastCommon; }
 constexpr bool trims_fold_rgb(uint32_t m) { return (RTMI_TRIM & 4) && (m & kFastCommon) == kFastCommon; }
+// A scene whose materials are all Lambertians or lights, none textured (SceneDev::diffuse_only: the Cornell box), gets
+// the same kernels once more with PIN_DIFFUSE, whose shading path is written for that scene (render_body.h).  RTMI_DIFFUSE
+// is a bit per step so that each can be built and censused alone (tools/loop_census.py --extra -DRTMI_DIFFUSE=1); step 4
+// stands on step 1.  (Bit 2 was a bounce without the material record's read; it did not pay and is gone: NOTES.md, "Trace
+// loop: diffuse scenes".)
+//   1  diffuse_scatter: metal and dielectric are not compiled: every scatter is Lambertian, so every active lane at the
+//      top of the loop owes the normalisation and kOwesBit is neither set nor tested.
+//   4  diffuse_restarts: a lane whose path ends and whose pixel has samples left takes the next sample's two camera
+//      draws with the first trip of the rejection sampler, and starts that sample behind it.  The camera block at the
+//      top is left with the lanes that have just taken a pixel.
+// The kernels without PIN_DIFFUSE compile to what they were.
+#ifndef RTMI_DIFFUSE
+#define RTMI_DIFFUSE 5
+#endif
+constexpr bool diffuse_scatter(uint32_t m) { return (RTMI_DIFFUSE & 1) && (m & PIN_DIFFUSE) && (m & kFastCommon) == kFastCommon; }
+constexpr bool diffuse_restarts(uint32_t m) { return (RTMI_DIFFUSE & 4) && diffuse_scatter(m); }
+// The mode word launch_render gives a launch whose plan says `fast` (0, kFastChains or kFastQueue) in this scene.
+inline uint32_t render_pins(uint32_t fast, const SceneDev &sc) { return fast != 0u && sc.diffuse_only ? fast | PIN_DIFFUSE : fast; }
 constexpr int kFoldRgbOff = 512;    // == 16 x sizeof(MatRec): behind the largest material table nibble ids can name
 constexpr int kFoldRgbBytes = 256;  // 16 rows of r, g, b, pad
 // The tasks that sent their flush through the ordered steps are counted in counters[kOrderedTasksWord], a word only

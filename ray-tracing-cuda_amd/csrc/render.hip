@@ -209,8 +209,13 @@ int render_occupancy(uint32_t variant, const SceneDev &sc, const FrameDev &fr, i
       // the grid must fit whichever it is (all three are built for the same waves per SIMD and use the same LDS)
       if (fast_path) {
         int nc = 0, nq = 0;
-        (void)kernel_occupancy<render_kernel<F, kFastChains>>(threads, lds, &nc);
-        (void)kernel_occupancy<render_kernel<F, kFastQueue>>(threads, lds, &nq);
+        if (sc.diffuse_only) {  // (kernels.h: render_pins)
+          (void)kernel_occupancy<render_kernel<F, kFastChains | PIN_DIFFUSE>>(threads, lds, &nc);
+          (void)kernel_occupancy<render_kernel<F, kFastQueue | PIN_DIFFUSE>>(threads, lds, &nq);
+        } else {
+          (void)kernel_occupancy<render_kernel<F, kFastChains>>(threads, lds, &nc);
+          (void)kernel_occupancy<render_kernel<F, kFastQueue>>(threads, lds, &nq);
+        }
         nb = nb < nc ? nb : nc, nb = nb < nq ? nb : nq;
       }
     }
@@ -278,6 +283,12 @@ hipError_t launch_render(uint32_t variant, const SceneDev &sc, const FrameDev &f
       // read the PairBox records (scene_dev.h: PairSlab)
       static_assert(culls_by_slab(kFastChains) && culls_by_slab(kFastQueue) && !culls_by_slab(0u), "which kernels read the slab table");
       if (chains || queue) rp.sc.pair_boxes = pair_slabs_of(sc.pair_boxes, sc.n_pairs);
+      // a scene of Lambertians and lights alone: the same three kernels compiled for it (kernels.h: PIN_DIFFUSE)
+      if (render_pins(fast, sc) & PIN_DIFFUSE) {
+        if (chains) return launch_block<render_kernel<F, kFastChains | PIN_DIFFUSE>>(at, rp, dp);
+        if (queue && !probe) return launch_block<render_kernel<F, kFastQueue | PIN_DIFFUSE>>(at, rp, dp);
+        if (queue) return launch_block<probe_kernel<F, kFastQueue | PIN_DIFFUSE>>(at, rp, dp);
+      }
       if (chains) return launch_block<render_kernel<F, kFastChains>>(at, rp, dp);
       if (queue && !probe) return launch_block<render_kernel<F, kFastQueue>>(at, rp, dp);
       if (queue) return launch_block<probe_kernel<F, kFastQueue>>(at, rp, dp);

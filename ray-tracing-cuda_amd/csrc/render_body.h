@@ -349,6 +349,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // Kernels that do not defer (kernels.h: defers_unit) never set it and normalise at both sites as before.
   constexpr bool DEFER = defers_unit(M);
   constexpr int kOwesBit = (int)0x80000000u;
+  // (M) the kernels of scenes that hold Lambertians and lights alone (kernels.h: PIN_DIFFUSE).  Every ray of theirs is a new
+  // camera ray or a Lambertian bounce, so every active lane at the top of the loop owes: no mark is set or tested.
+  constexpr bool DIFF = diffuse_scatter(M), DIFF_RESTARTS = diffuse_restarts(M);
+  static_assert(!DIFF || (DEFER && FOLD4 && (M & PIN_POW2_FRAME)), "the diffuse kernels are fast list kernels");
   // Layer stack of ray_tracing.cuh:9-15.  Layer::emitted is 0 for every material that
   // scatters (only DiffuseLight and Sky emit, and neither scatters), so a layer is its
   // attenuation.  Without image textures the attenuation is the material's constant
@@ -762,7 +766,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           const unsigned long long have = (unsigned long long)rays * (unsigned)lc.probe_spp, per = (unsigned long long)k;
           if (have >= thr16 * per) cls = have >= thr64 * per ? 64 : have >= thr32 * per ? 32 : 16;
         }
-        depth = DEFER ? kOwesBit : 0;  // (DEFER: depth 0, normalisation owed)
+        depth = DEFER && !DIFF ? kOwesBit : 0;  // (DEFER: depth 0, normalisation owed; DIFF: every active lane owes)
         active = true;
       }
     }
@@ -774,7 +778,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     // lanes share the call cannot change a bit.  Metal, dielectric, the caller's rays and take_item's first ray
     // normalise once, where they are formed, and never set the mark; a lane that owes is active and reaches this line
     // before the depth limit can end its path, so no mark outlives its ray.
-    if constexpr (DEFER) {
+    if constexpr (DIFF) {
+      if (active) d = unit3_rn_twice<VOTE>(d);
+    } else if constexpr (DEFER) {
       if (depth < 0) {
         d = unit3_rn_twice<VOTE>(d);
         depth &= ~kOwesBit;
@@ -839,7 +845,84 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
       V3 result = splat(0.f);
       bool ended = true;
       V3 step_att = splat(0.f), step_o = o, step_d = splat(0.f);  // (STEP) Scatter's attenuation and the vector it hands to Ray
-      if (h.ok && depth < fr.max_depth) {  // ray_tracing.cu:23
+      [[maybe_unused]] bool restart = false;  // (DIFF_RESTARTS) the path ends here and the lane has started its pixel's next sample
+      if constexpr (DIFF) {
+        // A scene of Lambertians and lights (kernels.h: PIN_DIFFUSE; a list of triangles and skies: variant F_TRIS alone).
+        // The same operations on every value as in the general text below, in their order -- the sky, the winner's normal,
+        // Emit, Lambertian::Scatter, the id stack -- without the branches of the other materials.  First what the hit is,
+        // then the draws of every lane that has any to make, at one site.
+        bool scatters = false;
+        V3 p = o, nrm = splat(0.f);
+        uint32_t mat = 0u;
+        if (h.ok && depth < fr.max_depth) {  // ray_tracing.cu:23
+          const uint32_t index = h.win & ID_INDEX_MASK;
+          p = o + h.t * d;
+          if ((h.win >> 29) == RUN_SKY) {  // sky.cu:9-14
+            V3 dir = unit3_rn<VOTE>(p);
+            float tg = (float)(0.5 * ((double)dir.y + 1.0));
+            float w0 = 1.0f - tg;
+            result = mk(w0 * 1.0f + tg * 0.5f, w0 * 1.0f + tg * 0.7f, w0 * 1.0f + tg * 1.0f);
+          } else {  // (RUN_TRIS: the variant has no other kind)
+            const float4 tn = s_nrm[index];
+            const V3 n = mk(tn.x, tn.y, tn.z);
+            mat = (uint32_t)__float_as_int(tn.w) & 0xffffffu;
+            nrm = dot3(d, n) < 0.f ? n : -n;  // utils.cu:80
+            // (the colour and the kind are one 16-byte read; `param` and `tex` are not read at all)
+            const float4 m0 = load_lds<float4>(s_mats + mat);
+            if (__float_as_int(m0.w) == MAT_LIGHT) {  // diffuse_light.cu:5-13
+              result = mk(m0.x, m0.y, m0.z);
+            } else {
+              scatters = !(dot3(d, nrm) >= 0.f);  // lambertian.cu:33-43
+            }
+          }
+        }
+        // The draws.  A lane that scatters rejection-samples the unit ball, three draws per attempt (ball_sample).  With
+        // DIFF_RESTARTS a lane whose path ends here while its pixel has samples left joins the FIRST trip for the two
+        // jitter draws of its next sample (ray_tracing.cu:68-74) and sits out the third: the generator's text is issued
+        // once for both, where the camera block at the top issued it again for a sixth of the wave.  The order of a
+        // pixel's draws is what it was -- two for the camera, three per attempt -- and a lane at its pixel's last sample
+        // draws nothing.
+        if constexpr (DIFF_RESTARTS) restart = !scatters && k < k_end();
+        if (scatters || restart) {
+          // (the first trip stands in front of the loop: with the restarting lanes' test inside it every trip paid for it,
+          // and for five moves of the generator's state -- C2 189.7 ms against 183.4 without the step)
+          [[maybe_unused]] uint32_t ux = 0u, uy = 0u;
+          float sum = 0.f;
+          V3 b = splat(0.f);
+          if constexpr (DIFF_RESTARTS) {
+            ux = rng_next(rng), uy = rng_next(rng);
+            if (scatters) {
+              float x = rng_pm1_of(ux), y = rng_pm1_of(uy), z = rng_pm1(rng);
+              sum = x * x + y * y + z * z;
+              while (sum > BALL_S_MAX) {  // (ball_sample's loop from its second trip on)
+                x = rng_pm1(rng), y = rng_pm1(rng), z = rng_pm1(rng);
+                sum = x * x + y * y + z * z;
+              }
+              b = mk(x, y, z);
+            }
+          } else {
+            b = ball_sample(rng, sum);
+          }
+          if (!DIFF_RESTARTS || scatters) {
+            const V3 s = sampler_on_sphere<VOTE>(b, sum);  // l = (float)pow((double)sum, 0.5); vec /= l (lambertian.cu:25-29)
+            const uint32_t at = ids_offset(depth >> 1);  // this lane's own byte: no other lane writes it
+            const uint32_t old = smem[at];
+            smem[at] = (uint8_t)((depth & 1) ? ((old & 0x0fu) | (mat << 4)) : ((old & 0xf0u) | mat));
+            depth++;
+            o = p;
+            d = s + nrm;  // normalize(S + n), then Ray's constructor (lambertian.cu:41-42): both at the top of the loop
+            ended = false;
+          } else {
+            // the next sample's camera ray (the camera block above, for a power-of-two frame), raw like the bounce's; the
+            // path's own depth stays for the fold below, which resets it
+            const float xf = (rng_01_of(ux) + (float)(pij & 0xffffu)) * (float)inv_w;
+            const float yf = (rng_01_of(uy) + (float)(fr.height - (int)(pij >> 16))) * (float)inv_h;
+            const V3 target = sc.cam.llc + xf * sc.cam.horizontal + yf * sc.cam.vertical;
+            o = sc.cam.position;
+            d = target - sc.cam.position;
+          }
+        }
+      } else if (h.ok && depth < fr.max_depth) {  // ray_tracing.cu:23
         const uint32_t kind = h.win >> 29;
         const uint32_t index = h.win & ID_INDEX_MASK;
         V3 p = o + h.t * d;  // ray_tracing.cu:32 and the materials' own `p`
@@ -1149,7 +1232,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         if constexpr (BUDGET)  // the product and the sum rounded separately, so that a binary32 restatement is exact
           moment = mk(__fadd_rn(moment.x, __fmul_rn(result.x, result.x)), __fadd_rn(moment.y, __fmul_rn(result.y, result.y)),
                       __fadd_rn(moment.z, __fmul_rn(result.z, result.z)));
-        active = false;
+        // (DIFF_RESTARTS: the lane is on its next sample already and o, d hold its camera ray -- the camera block's end)
+        if (DIFF_RESTARTS && restart) k++, depth = 0;
+        else active = false;
       }
     }
     RTMI_STAT(st.cyc[4] += stat_now() - tq2;)

@@ -12,6 +12,7 @@
 //    wave's loads and stores are contiguous;
 //  * the material table is small and indexed per lane -> staged in LDS.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "vec.h"
@@ -261,6 +262,9 @@ struct SceneDev {
   const int32_t *leaf_paths;  // per mesh (BvhRec::path_base): one row of ref_depth node indices per reference leaf,
                               // the nodes below the root on the way to the leaf, -1 past it
   int32_t n_leaf_paths;       // words in leaf_paths
+  int32_t diffuse_only;       // 1: every material is MAT_LAMBERTIAN or MAT_LIGHT and none has a texture (capi.hip: commit).
+                              // Read by the host alone (kernels.h: render_pins).  It lies in what was the padding in
+                              // front of `faces`: the layout of every other field is what it was (static_assert below).
   const FaceRec *faces;
   const float *face_uv;  // 6 floats per face or nullptr
 #ifdef RTMI_CHECK_MARGINS
@@ -280,6 +284,9 @@ struct SceneDev {
                              // product is +0, positive or NaN and `emitted(0) + product` is the product itself
   CameraDev cam;
 };
+static_assert(offsetof(SceneDev, diffuse_only) + sizeof(int32_t) == offsetof(SceneDev, faces) &&
+              offsetof(SceneDev, diffuse_only) == offsetof(SceneDev, n_leaf_paths) + sizeof(int32_t),
+              "diffuse_only fills the padding between n_leaf_paths and faces");
 
 // What only rtmi_intersect reads (query_body.h): the flattened records back to recording order, so that a hit can
 // name its hitable.  Kept apart from SceneDev, whose layout the trace kernels' argument block fixes.

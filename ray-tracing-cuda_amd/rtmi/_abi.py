@@ -214,6 +214,7 @@ SYMBOLS = [
     ("rtmi_render_mode", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), C.POINTER(C.c_int32)]),
     ("rtmi_render_mode_ex", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), C.POINTER(C.c_int32), C.c_int]),
     ("rtmi_fast_path_kernel", C.c_int, [C.POINTER(C.c_int32)]),
+    ("rtmi_render_pins", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderOpts), _u32p]),
     ("rtmi_render_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     ("rtmi_last_ray_total", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     ("rtmi_debug_counters", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_void_p]),
