@@ -717,7 +717,8 @@ int rtmi_path_advance(const rtmi_scene *s, const rtmi_frame *f, const rtmi_path_
  * The light table.  A TABLE LIGHT is a Triangle, a Parallelogram or a face of a Parallelepiped of the world list (nested
  * lists inlined) whose material is a DiffuseLight on a constant texture with three finite, not all zero components, and
  * whose e1 x e2 (in binary64) is finite and non-zero.  Emissive spheres, mesh faces, image-textured lights and Sky are not
- * table lights: their light keeps arriving through hits.  DiffuseLight::Emit ignores the side: lights are two-sided.
+ * table lights (emissive spheres become ones with rtmi_scene_light_kinds, below): their light keeps arriving through
+ * hits.  DiffuseLight::Emit ignores the side: lights are two-sided.
  * One record per Parallelogram or box face (sampled as p0 + u e1 + v e2) and one per lone Triangle, in the order of the
  * flattened world list:
  *   - p0, e1, e2, n: bit for bit those of the hitable's first triangle as the kernels hold it (p0, p1 - p0, p2 - p0 and
@@ -781,7 +782,7 @@ typedef struct rtmi_light {
   float p0[3], e1[3], e2[3], n[3];
   float emission[3];
   float area, cdf, scale;
-  int32_t kind;     /* 0 parallelogram, 1 triangle */
+  int32_t kind;     /* 0 parallelogram, 1 triangle, 2 sphere (rtmi_scene_light_kinds) */
   int32_t entry, element, material;
 } rtmi_light;
 int64_t rtmi_scene_light_count(const rtmi_scene *s);
@@ -860,6 +861,63 @@ typedef struct rtmi_direct_sample_mis_args {
   unsigned long long *d_counts;       /* nullable */
 } rtmi_direct_sample_mis_args;
 int rtmi_direct_sample_mis(const rtmi_scene *s, const rtmi_direct_sample_mis_args *args, void *stream);
+
+/* rtmi_scene_light_kinds.  Emissive spheres as table lights: a bulb is sampled in the cone it subtends from the vertex,
+ * with the balance heuristic in rtmi_direct_sample_mis.  Opt-in, before rtmi_scene_commit; added without a version change:
+ * a caller detects it by the symbol rtmi_scene_light_kinds.  A scene that does not opt in gets the table, the kernels and
+ * the bits it always got.  kinds is RTMI_LIGHTS_FLAT (1, the default: triangles, parallelograms, box faces) or
+ * RTMI_LIGHTS_FLAT | RTMI_LIGHTS_SPHERES (3).  RTMI_ERR_INVALID, with the reason in rtmi_last_error, for a null scene, a
+ * committed scene and every other value (0, 2 and unknown bits included).  Host state only, read at commit.
+ *
+ * The table with kinds == 3: the flat records as ever and in their order, then one record per SPHERE TABLE LIGHT in the
+ * order of the flattened scene's spheres: a Sphere of the world list (nested lists inlined) whose material is a
+ * DiffuseLight on a constant texture with three finite, not all zero components, whose centre is finite, whose binary64
+ * radius r is finite and > 0, and for which R = (float)r and R2 = R * R (binary32) are finite and > 0.  Its record:
+ * kind = 2;  p0 = the centre;  e1[0] = R, e1[1] = R2;  e1[2], e2, n = +0.0f;  emission, material;  entry as rtmi_hit names
+ * a hit on it, element = 0;  area = (float)(4 pi r r) formed in binary64;  w_j = area_j * ((|r| + |g|) + |b|) from the
+ * unrounded area.  W and cdf are formed over the WHOLE table by the expressions above (the last cdf is 1.0f); a flat
+ * record keeps its expression for scale with the new W, a sphere has scale_j = (float)(2 * W / w_j) = 2 / P_j.  The light
+ * of a SPHERE hit is the table light j of kind 2 with lights[j].entry == hit.entry.  Mesh faces, image-textured lights,
+ * Sky and spheres of radius <= 0 stay what they were.
+ *
+ * The step on a scene whose table holds a sphere light (both rtmi_direct_sample and rtmi_direct_sample_mis; same
+ * arguments, same arithmetic rules: one binary32 rounding per operation in the order written, sums of three as
+ * (x + y) + z, IEEE division and sqrt, no fused multiply-add, a NaN makes a comparison false).  For a sphere light j and a
+ * point x the SHARED GEOMETRY is
+ *     wc = c - x;  d2c = (wcx wcx + wcy wcy) + wcz wcz;  outside = d2c > R2;  dc = sqrt(d2c);  s2 = R2 / d2c;
+ *     cm = sqrt((d2c - R2) / d2c);  om = s2 / (1 + cm)  -- 1 - cos(theta_max) of the subtended cone, without cancellation:
+ *     om comes from s2 for a far light, and d2c - R2 is exact for a vertex close to the surface, where 1 - s2 would
+ *     magnify the rounding of s2 (given R2 and d2c, om is within 1.3 ulp of s2 / (1 + sqrt(1 - s2)) in binary64).
+ *   - SAMPLE: the condition is unchanged; r0 is drawn and j picked as ever.  lights[j].kind != 2: the rest is the text
+ *     above, r1 and r2 included.  kind == 2, with x = d_origins[i], N = d_hits[i].normal:
+ *       draws, always and before any validity test: r1 = CudaRandomFloat(0, 1); then repeat a = CudaRandomFloat(-1, 1),
+ *         b = CudaRandomFloat(-1, 1) (each draw01 * 2 + (-1)), s = a a + b b until s > 0 && s <= 1 (no trip cap);
+ *         ls = sqrt(s), cp = a / ls, sp = b / ls.  The light state advances by 2 + 2 * trips.
+ *       polar angle: h = r1 * om;  ct = 1 - h;  st2 = h * (2 - h);  st = sqrt(st2).
+ *       axis and frame (Duff et al.): w = wc / dc per component;  sg = wz >= 0 ? 1 : -1;  ka = -1 / (sg + wz);
+ *         kb = (wx wy) * ka;  u = (1 + (sg * (wx wx)) * ka, sg * kb, (-sg) * wx);  v = (kb, sg + (wy wy) * ka, -wy).
+ *       direction: sc = st * cp;  ss = st * sp;  wi = (ct * w + sc * u) + ss * v per component.
+ *       distance: tc = dc * ct;  q = R2 - d2c * st2;  q = q > 0 ? q : 0;  t = tc - sqrt(q).
+ *       cosine: cs = (Nx wix + Ny wiy) + Nz wiz.
+ *       valid iff outside && cs > 0 && t > 0 && t < +inf.  Valid: a = (cs * om) * scale_j;  g = a for rtmi_direct_sample,
+ *         g = a / (a + 1) for rtmi_direct_sample_mis;  d_direct[i][ch] = (d_attenuation[i][ch] * emission_j[ch]) * g;  the
+ *         shadow ray is (x, wi, t * 0.999f).  Invalid: the invalid outputs above.  Flag, d_counts[0] and, for MIS, the
+ *         carry (d, N . d) as ever, valid or not.
+ *     Why: a direction uniform in the cone has density 1 / (2 pi om), so the estimate (albedo / pi) Le cs / (P_j / (2 pi om))
+ *     is albedo Le cs om scale_j: no 1 / d2 term, bounded without MIS.  The scattered ray's density cs / pi against the
+ *     light's P_j / (2 pi om) is a : 1, so the balance weights are a / (a + 1) and 1 / (a + 1), and pi cancels again.
+ *   - WEIGH (rtmi_direct_sample_mis): the flag's bit 0 was set, d_hits[i].kind == RTMI_HIT_SPHERE and the hit has a light j
+ *     of kind 2.  x = d_origins[i]: a DiffuseLight does not scatter, so rtmi_bounce left the origin at the vertex before.
+ *     !outside: the emission keeps every bit and is not counted -- that vertex could not sample this light.  Otherwise
+ *     a = (carry.w * om) * scale_j;  w = (a > 0 && a + 1 < +inf) ? a / (a + 1) : +0.0f;  d_emitted[i] is multiplied by w
+ *     where w came from the division and is three +0.0f otherwise;  d_counts[1] += 1.  Hits of other kinds: as ever.
+ *   - DROP (rtmi_direct_sample), beside the rule above: the flag was set, the kind is SPHERE, the hit has a light j of kind
+ *     2 and `outside` holds from x = d_origins[i]: d_emitted[i] becomes three +0.0f and d_counts[1] += 1.  The material bit
+ *     cannot say this: a vertex inside an emissive sphere cannot sample it and must keep the light it hits.
+ * rtmi_path_fold_direct, rtmi_occluded and the loop are unchanged. */
+#define RTMI_LIGHTS_FLAT    1u   /* triangles, parallelograms, box faces: what the table always held (default) */
+#define RTMI_LIGHTS_SPHERES 2u
+int rtmi_scene_light_kinds(rtmi_scene *s, uint32_t kinds);
 
 /* rtmi_occluded_list.  rtmi_occluded for the candidates of (d_list, n_list, d_count) only: the visibility query of a loop
  * whose other steps take a live-path list, and of any caller who shoots shadow or ambient-occlusion rays from the vertices

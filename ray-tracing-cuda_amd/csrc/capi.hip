@@ -535,6 +535,8 @@ int rtmi_scene_commit(rtmi_scene *sp) {
     std::vector<LightRec> recs;
     std::vector<float> cdf;
     build_light_table(*s, &s->lights, &light_mats);
+    s->sphere_lights = false;
+    for (const rtmi_light &lt : s->lights) s->sphere_lights = s->sphere_lights || lt.kind == 2;
     light_records(s->lights, &recs, &cdf);
     LightDev l{};
     if ((rc = upload(s, recs, &l.recs))) return rc;
@@ -1396,6 +1398,15 @@ int rtmi_scene_lights(const rtmi_scene *sp, rtmi_light *out, int64_t n) {
   return RTMI_OK;
 }
 
+int rtmi_scene_light_kinds(rtmi_scene *sp, uint32_t kinds) {
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (S(sp)->committed) return fail(RTMI_ERR_INVALID, "rtmi_scene_light_kinds after rtmi_scene_commit: the table is made at commit");
+  if (kinds != RTMI_LIGHTS_FLAT && kinds != (RTMI_LIGHTS_FLAT | RTMI_LIGHTS_SPHERES))
+    return fail(RTMI_ERR_INVALID, "light kinds must be RTMI_LIGHTS_FLAT or RTMI_LIGHTS_FLAT | RTMI_LIGHTS_SPHERES");
+  S(sp)->light_kinds = kinds;
+  return RTMI_OK;
+}
+
 // The checks and the argument block the two steps share: *work says whether anything is to be launched.
 static int direct_args(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,
                        uint32_t step, int sample, const float *d_origins, const float *d_dirs, const rtmi_hit *d_hits,
@@ -1439,6 +1450,14 @@ int rtmi_direct_sample(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, 
                                  d_direct, d_counts, nullptr, false, &a, &n_cu, &work))
     return rc;
   if (!work) return RTMI_OK;
+  const Scene *s = S(sp);
+  if (s->sphere_lights) {
+    DirectMisArgs b{};
+    static_cast<DirectArgs &>(b) = a;
+    b.hit_light = s->ldev.hit_light, b.n_entries = s->ldev.n_entries, b.carry = nullptr;
+    HIP_TRY(launch_direct_sample_sph(b, false, n_cu, (hipStream_t)stream));
+    return RTMI_OK;
+  }
   HIP_TRY(launch_direct_sample(a, n_cu, (hipStream_t)stream));
   return RTMI_OK;
 }
@@ -1459,6 +1478,10 @@ int rtmi_direct_sample_mis(const rtmi_scene *sp, const rtmi_direct_sample_mis_ar
   if (!work) return RTMI_OK;
   const Scene *s = S(sp);
   a.hit_light = s->ldev.hit_light, a.n_entries = s->ldev.n_entries, a.carry = p->d_carry;
+  if (s->sphere_lights) {
+    HIP_TRY(launch_direct_sample_sph(a, true, n_cu, (hipStream_t)stream));
+    return RTMI_OK;
+  }
   HIP_TRY(launch_direct_sample_mis(a, n_cu, (hipStream_t)stream));
   return RTMI_OK;
 }

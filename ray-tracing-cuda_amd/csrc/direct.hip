@@ -18,6 +18,10 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // DiffuseLight on a constant texture with finite, not all zero components and whose e1 x e2 is finite and non-zero, in
 // the order of the pairs.  Everything that is not binary32 data of the scene is formed in binary64 and rounded once
 // (include/rtmi.h states the expressions; tests/directlib.py restates them).
+// A scene that opted in (rtmi_scene_light_kinds with RTMI_LIGHTS_SPHERES) gets, behind those, one record of kind 2 per
+// Sphere on such a material with a finite centre and a finite radius > 0 whose binary32 R and R * R are finite and > 0,
+// in the order of the flattened spheres (tests/spherelightlib.py restates them).  No material bit is set for them: a
+// sphere light is known by its record.
 void build_light_table(const Scene &s, std::vector<rtmi_light> *lights, std::vector<uint32_t> *light_mats) {
   lights->clear();
   light_mats->assign((s.mat_recs.size() + 31) / 32, 0u);
@@ -49,13 +53,42 @@ void build_light_table(const Scene &s, std::vector<rtmi_light> *lights, std::vec
     w.push_back(ar * ((std::fabs((double)m.r) + std::fabs((double)m.g)) + std::fabs((double)m.b)));
     (*light_mats)[(size_t)t.mat >> 5] |= 1u << (t.mat & 31);
   }
+  const size_t n_flat = lights->size();
+  for (size_t i = 0; (s.light_kinds & RTMI_LIGHTS_SPHERES) && i < s.q_sphere_entry.size() && i < s.spheres.size(); i++) {
+    const SphereRec &sp = s.spheres[i];
+    if (sp.mat < 0 || sp.mat >= (int32_t)s.mat_recs.size()) continue;
+    const MatRec &m = s.mat_recs[(size_t)sp.mat];
+    if (m.kind != MAT_LIGHT || m.tex >= 0) continue;
+    if (!(std::isfinite(m.r) && std::isfinite(m.g) && std::isfinite(m.b)) || (m.r == 0.f && m.g == 0.f && m.b == 0.f)) continue;
+    if (!(std::isfinite(sp.cx) && std::isfinite(sp.cy) && std::isfinite(sp.cz))) continue;
+    const double r = sp.radius;
+    if (!(std::isfinite(r) && r > 0.)) continue;
+    const float R = (float)r;
+    const float R2 = R * R;
+    if (!(std::isfinite(R) && R > 0.f && std::isfinite(R2) && R2 > 0.f)) continue;
+    const double ar = 4 * M_PI * r * r;
+    rtmi_light l;
+    memset(&l, 0, sizeof(l));
+    l.p0[0] = sp.cx, l.p0[1] = sp.cy, l.p0[2] = sp.cz;
+    l.e1[0] = R, l.e1[1] = R2;
+    l.emission[0] = m.r, l.emission[1] = m.g, l.emission[2] = m.b;
+    l.area = (float)ar;
+    l.kind = 2;
+    l.entry = s.q_sphere_entry[i];
+    l.element = 0;
+    l.material = sp.mat;
+    lights->push_back(l);
+    area.push_back(ar);
+    w.push_back(ar * ((std::fabs((double)m.r) + std::fabs((double)m.g)) + std::fabs((double)m.b)));
+  }
   double W = 0.;
   for (double x : w) W += x;
   double run = 0.;
   for (size_t j = 0; j < lights->size(); j++) {
     run += w[j];
     (*lights)[j].cdf = (float)(run / W);
-    (*lights)[j].scale = (float)(area[j] * W / (w[j] * M_PI));
+    // a sphere is sampled by solid angle: 2 / P_j takes the place of area / (P_j pi)
+    (*lights)[j].scale = j < n_flat ? (float)(area[j] * W / (w[j] * M_PI)) : (float)(2 * W / w[j]);
   }
   if (!lights->empty()) lights->back().cdf = 1.0f;
 }
@@ -104,6 +137,17 @@ __global__ __launch_bounds__(kDirectThreads) void direct_sample_mis_kernel(Direc
   direct_body<true>(a, s_cdf);
 }
 
+// The twins for a table with sphere lights (direct_body.h: SPH): the only kernels such a scene's steps launch, and no
+// other scene launches them.
+__global__ __launch_bounds__(kDirectThreads) void direct_sample_sph_kernel(DirectMisArgs a) {
+  __shared__ float s_cdf[kLdsLights];
+  direct_body<false, true>(a, s_cdf);
+}
+__global__ __launch_bounds__(kDirectThreads) void direct_sample_mis_sph_kernel(DirectMisArgs a) {
+  __shared__ float s_cdf[kLdsLights];
+  direct_body<true, true>(a, s_cdf);
+}
+
 // One lane per candidate: list_grid (kernels.h) over the host's bound n_list -- 2^19 entries a round on 256 compute units.
 template <auto Kernel, class Args>
 static hipError_t direct_launch(const Args &a, int n_cu, hipStream_t stream) {
@@ -115,6 +159,9 @@ hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t strea
 }
 hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_t stream) {
   return direct_launch<direct_sample_mis_kernel>(a, n_cu, stream);
+}
+hipError_t launch_direct_sample_sph(const DirectMisArgs &a, bool mis, int n_cu, hipStream_t stream) {
+  return mis ? direct_launch<direct_sample_mis_sph_kernel>(a, n_cu, stream) : direct_launch<direct_sample_sph_kernel>(a, n_cu, stream);
 }
 
 // ------------------------------------------------------------------ the fold (rtmi_path_fold_direct)

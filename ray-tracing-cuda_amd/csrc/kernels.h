@@ -281,6 +281,8 @@ hipError_t launch_direct_sample(const DirectArgs &a, int n_cu, hipStream_t strea
 struct DirectMisArgs;
 void build_hit_light_map(const std::vector<rtmi_light> &lights, std::vector<int32_t> *map, int32_t *n_entries);
 hipError_t launch_direct_sample_mis(const DirectMisArgs &a, int n_cu, hipStream_t stream);
+// Either step on a scene whose table holds a sphere light (Scene::sphere_lights): the plain one with a null carry.
+hipError_t launch_direct_sample_sph(const DirectMisArgs &a, bool mis, int n_cu, hipStream_t stream);
 // rtmi_path_fold with T[k] = d_occluded[k] ? E[k] : E[k] + D[k] for E[k] (rtmi_path_fold_direct).
 hipError_t launch_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                                    const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded,

@@ -95,6 +95,8 @@ struct Scene {
   int32_t q_sky_entry = -1;
   // rtmi_direct_sample only (LightDev): the table lights, made at commit (direct.hip: build_light_table)
   std::vector<rtmi_light> lights;
+  uint32_t light_kinds = RTMI_LIGHTS_FLAT;  // rtmi_scene_light_kinds: what build_light_table may put into the table
+  bool sphere_lights = false;               // the table holds a record of kind 2: the steps launch the sphere twins
   LightDev ldev{};
   std::vector<void *> dev_allocs;
   SceneDev dev{};

@@ -272,9 +272,13 @@ SYMBOLS = [
                                     [C.c_void_p] * 14),
     ("rtmi_path_fold_direct", C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8),
     ("rtmi_direct_sample_mis", C.c_int, [C.c_void_p, C.POINTER(DirectSampleMisArgs), C.c_void_p]),
+    ("rtmi_scene_light_kinds", C.c_int, [C.c_void_p, C.c_uint32]),
     ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
     ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
 ]
+
+# RTMI_LIGHTS_* of include/rtmi.h (rtmi_scene_light_kinds)
+LIGHTS_FLAT, LIGHTS_SPHERES = 1, 2
 
 # rtmi_light of include/rtmi.h, as a numpy record (88 bytes)
 LIGHT_DTYPE = np.dtype([("p0", np.float32, 3), ("e1", np.float32, 3), ("e2", np.float32, 3), ("n", np.float32, 3),

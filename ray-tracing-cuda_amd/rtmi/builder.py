@@ -11,7 +11,20 @@ from .wavefront import (Bounce, DirectSample, Hits, Occlusion, Steps, Trace, _li
                         path_fold_direct)
 
 
-class SceneBuilder:
+class _CommitOptions:
+    """What a scene opts into before ``commit``.  A base of ``SceneBuilder``: the options are the builder's methods."""
+
+    def light_kinds(self, spheres=False):
+        """Which hitables the light table may hold (rtmi_scene_light_kinds), to be called before ``commit``: triangles,
+        parallelograms and box faces always; with ``spheres=True`` also emissive spheres of positive radius, sampled in
+        the cone they subtend.  ``lights()``, ``direct_sample``, ``trace_steps(direct=...)`` and
+        ``Renderer.render_rays(direct=...)`` work unchanged on such a scene.  Returns the builder."""
+        _check(self.L.rtmi_scene_light_kinds(self.h, _abi.LIGHTS_FLAT | (_abi.LIGHTS_SPHERES if spheres else 0)),
+               "rtmi_scene_light_kinds")
+        return self
+
+
+class SceneBuilder(_CommitOptions):
     """Builder protocol of rtmi/scenes.py over the C ABI's scene recorder.
 
     ``seed`` seeds the host copy of pixel 0's RNG stream that scene programs may draw
@@ -199,7 +212,8 @@ class SceneBuilder:
     def lights(self):
         """The committed scene's light table (rtmi_scene_lights): a numpy record array of dtype ``LIGHT_DTYPE`` with the
         fields p0, e1, e2, n, emission (each (L, 3) float32), area, cdf, scale (float32), kind, entry, element, material
-        (int32) -- ``lights()["cdf"]`` and so on; length 0 when no world-list triangle or parallelogram emits."""
+        (int32) -- ``lights()["cdf"]`` and so on; length 0 when no world-list triangle or parallelogram emits (and, after
+        ``light_kinds(spheres=True)``, no sphere: such a light has kind 2, p0 its centre, e1 = (R, R * R, 0))."""
         n = _check(self.L.rtmi_scene_light_count(self.h), "rtmi_scene_light_count")
         out = np.zeros((n,), dtype=LIGHT_DTYPE)
         _check(self.L.rtmi_scene_lights(self.h, out.ctypes.data_as(C.c_void_p), n), "rtmi_scene_lights")
