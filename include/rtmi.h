@@ -220,7 +220,12 @@ int rtmi_last_ray_total(const rtmi_scene *s, uint64_t *out_rays, void *stream);
  * step counts of the mesh search from word 4 on; a -DRTMI_CHECK_MARGINS build counts, in [33] / [34], the
  * sampled queries it re-did without the cull and the disagreements it found; [16], in every build, counts the
  * pair tasks of the fast list kernels' culled scan both of whose triangles passed with the second one nearer: the
- * flushes that held one were folded in list order, every other by one minimum per ray).  [2], [33] and [34] count over
+ * flushes that held one were folded in list order, every other by one minimum per ray.  It counts them by the lanes
+ * that met one in a flush, so two such tasks of one flush that fall to the same lane count once; which lane a task
+ * falls to depends on the flush's schedule of rounds, so the word may differ by such coincidences between versions of
+ * the library, never the image.  A -DRTMI_CHECK_MARGINS build without -DRTMI_STATS also counts, in [37] / [38], the
+ * rounds in which those kernels tested a flush's tasks a pair per lane and a triangle per lane, and in [39] the tasks
+ * of that kind met in a pair round, one by one -- words that otherwise only a stats build writes).  [2], [33] and [34] count over
  * both launches of a resumed frame (a first pass the frame keeps, then the rest); the other words are the last
  * launch's, whose [1] is still the whole frame's total because a resumed pixel carries its count on. */
 #define RTMI_COUNTER_WORDS 40

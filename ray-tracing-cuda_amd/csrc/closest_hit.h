@@ -65,7 +65,9 @@ __device__ inline bool bvh_reference_walk(const SceneDev &sc, const BvhRec &br, 
 // begins with them (scene_dev.h).  Returns whether the triangle is there: a lone Triangle has no second one.
 // PAIR: the caller reads both records of a pair, `which` a constant: with trims_mul24 the address is formed from the
 // pair's first record, so the two calls share one product and the second record is 48 bytes on.
-template <uint32_t M, bool PAIR = false>
+// NARROW (staged records only): the third read fetches the words that are used and no more -- e2's last, and behind a
+// pair's second record its flag: a b32 / b64 read where the plain form reads a b128.
+template <uint32_t M, bool PAIR = false, bool NARROW = false>
 __device__ __forceinline__ bool load_tri_pts(const SceneDev &sc, const float4 *s_tris, int rec, int which, V3 &p0, V3 &e1, V3 &e2) {
   float4 qa, qb, qc;
   bool present;
@@ -79,7 +81,13 @@ __device__ __forceinline__ bool load_tri_pts(const SceneDev &sc, const float4 *s
       asm volatile("" : "+v"(at));
       pp = (const float4 *)(const RT_LDS float4 *)(uintptr_t)at + (PAIR ? 3 * which : 0);
     }
-    qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1), qc = load_lds<float4>(pp + 2);
+    qa = load_lds<float4>(pp), qb = load_lds<float4>(pp + 1);
+    if (NARROW) {
+      const float2 q2 = which == 0 ? make_float2(*(const RT_LDS float *)(pp + 2), 0.f) : load_lds<float2>(pp + 2);  // (the first record is never absent)
+      qc = make_float4(q2.x, q2.y, 0.f, 0.f);
+    } else {
+      qc = load_lds<float4>(pp + 2);
+    }
     present = !(__float_as_int(qc.y) & TRIPTS_ABSENT);
   } else {  // a list too long for the staging: per-lane gather of 64 bytes (L1 / L2 resident)
     const float4 *pp = reinterpret_cast<const float4 *>(sc.tris + rec);
@@ -90,6 +98,48 @@ __device__ __forceinline__ bool load_tri_pts(const SceneDev &sc, const float4 *s
   p0 = mk(qa.x, qa.y, qa.z), e1 = mk(qa.w, qb.x, qb.y), e2 = mk(qb.z, qb.w, qc.x);
   return present;
 }
+
+// Both triangles of the pair whose first record is `rec` against one ray and one bound, for the own-first test and the
+// pair rounds of the culled scan: the two records read through one address product, then the reference's test on each.
+// Declares hit_a, ta, ua, va, hit_b, tb, ub, vb in the caller's block.
+// SHARED false (a lane's own ray): both records are read at once, the second is tested where the pair has one, and
+// hit_b is parallelogram.cu:33's, "only when the first missed".
+// SHARED true (a pair round: a ray read from LDS beside the lane's own, and no registers for both records at once):
+// the records' third read fetches the words that are used and no more; the second record is read when the first test's
+// t is formed (asm volatile statements keep their order, and a record's address passes through one); the second test
+// runs without a branch on whatever an absent record holds, and the flag then drops its verdict; and hit_b is the
+// second's own verdict, because a pair round needs both to know the ordered kind.  So the two forms' hit_b are NOT the
+// same boolean: with SHARED the caller must not read it as "the pair is hit at tb" before it has looked at hit_a.
+// (A macro, not a __forceinline__ function: the function is simplified on its own before it is inlined, which commutes
+// operands of the own-first test in every kernel that has one -- the same arithmetic, but no longer the text the kernels
+// had, and "compiles to what it was" is checked by text: tools/kernel_diff.py.)
+#define RTMI_PAIR_TEST(rec_, o_, d_, t_to_, SHARED)                                                                             \
+  V3 p0, e1, e2, p1, e1b, e2b;                                                                                                  \
+  (void)load_tri_pts<M, true, SHARED>(sc, s_tris, (rec_), 0, p0, e1, e2);                                                       \
+  bool second = false;                                                                                                          \
+  if (!(SHARED)) second = load_tri_pts<M, true, SHARED>(sc, s_tris, (rec_) + 1, 1, p1, e1b, e2b);                               \
+  float ta = 0.f, ua = 0.f, va = 0.f, tb = 0.f, ub = 0.f, vb = 0.f;                                                             \
+  const bool hit_a = tri_test_flat<T, VOTE>(p0, e1, e2, cross3(d_, e2), o_, d_, t_to_, ta, ua, va, det_safe);                   \
+  bool hit_b = false;                                                                                                           \
+  if (SHARED) {                                                                                                                 \
+    asm volatile("" : "+v"(ta));                                                                                                \
+    second = load_tri_pts<M, true, SHARED>(sc, s_tris, (rec_) + 1, 1, p1, e1b, e2b);                                            \
+    hit_b = tri_test_flat<T, VOTE>(p1, e1b, e2b, cross3(d_, e2b), o_, d_, t_to_, tb, ub, vb, det_safe) && second;               \
+  } else if (second) {                                                                                                          \
+    hit_b = tri_test_flat<T, VOTE>(p1, e1b, e2b, cross3(d_, e2b), o_, d_, t_to_, tb, ub, vb, det_safe) && !hit_a;               \
+  }
+
+#if defined(RTMI_CHECK_MARGINS) && !defined(RTMI_STATS)
+// (the rounds of a flush's step (b), counted by the check build of the kernels that have pair rounds: kernels.h)
+#define RTMI_COUNT_ROUND(word) \
+  if (PAIRS && ln == 0) atomicAdd(overflow + ((word) - 2), 1ull);
+// (and the tasks of the ordered kind that a pair round met, one by one)
+#define RTMI_COUNT_PAIR_FLAG(cond) \
+  if (cond) atomicAdd(overflow + (kPairFlagsWord - 2), 1ull);
+#else
+#define RTMI_COUNT_ROUND(word)
+#define RTMI_COUNT_PAIR_FLAG(cond)
+#endif
 
 // ================================================================== closest hit
 // HitableList::Hit (hitable_list.cu:7-25) over the flattened world.  A nested
@@ -147,6 +197,8 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
   constexpr bool SLAB = culls_by_slab(M);  // (kernels.h) the pair test in centre / half-extent form
   constexpr bool MINF = folds_by_min(M);   // (kernels.h) a flush of shared tests folds by one LDS minimum per ray
   constexpr bool VOTE = trims_votes(M);    // (kernels.h) wave votes on a compare take the compare's own lane mask
+  constexpr bool PAIRS = pairs_full_rounds(M) && kPairRoundMin < kListTasks(F);  // (kernels.h) full rounds of a flush test a pair per lane
+  static_assert(!PAIRS || MINF, "a pair round posts keys");
   static_assert(!MINF || (!OCC && !DT && !(F & F_TEX)), "a key holds a binary32 t and the triangle's place, nothing else");
   const bool cull_list = (F & F_TRIS) && ((M & PIN_LDS_TABLES) || (ll != nullptr && sc.n_pairs >= kCullMinPairs));  // (wave-uniform)
   V3 cull_inv = splat(0.f), cull_klo = splat(0.f), cull_khi = splat(0.f);
@@ -274,13 +326,7 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             const int bit = __builtin_ctz(mask);
             mask &= mask - 1u;
             const int rec = 2 * (pair0 + c0 + bit);  // the pair's two records: edges formed on the host (scene.hip: push_pair)
-            V3 p0, e1, e2, p1, e1b, e2b;
-            (void)load_tri_pts<M, true>(sc, s_tris, rec, 0, p0, e1, e2);
-            const bool second = load_tri_pts<M, true>(sc, s_tris, rec + 1, 1, p1, e1b, e2b);
-            float ta = 0.f, ua = 0.f, va = 0.f, tb = 0.f, ub = 0.f, vb = 0.f;
-            const bool hit_a = tri_test_flat<T, VOTE>(p0, e1, e2, cross3(d, e2), o, d, t_to, ta, ua, va, det_safe);
-            bool hit_b = false;
-            if (second) hit_b = tri_test_flat<T, VOTE>(p1, e1b, e2b, cross3(d, e2b), o, d, t_to, tb, ub, vb, det_safe) && !hit_a;  // parallelogram.cu:33
+            RTMI_PAIR_TEST(rec, o, d, t_to, false)
             const float t = hit_a ? ta : tb;
             const bool acc = (hit_a || hit_b) && (!ok || (T)t < t_to);
             ok = ok || acc;
@@ -356,7 +402,43 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             // below, which read the same tasks and ray records and overwrite the keys with their result words.
             if (MINF) {
               bool flagged = false;
-              for (int t0 = 0; t0 < 2 * n_now; t0 += 64) {  // (b)
+              // (PAIRS) rounds that would run more than kPairRoundMin / 64 full test a PAIR per lane (pair_rounds.h): lane
+              // ln takes task done + ln, reads its ray record once and both records of its pair through one address
+              // product, and knows both verdicts itself -- the booleans the two lanes of a triangle round form by their
+              // exchange, from the same tests against the same bound, so the keys and the flagged flushes are the same.
+              // (`flagged` is a flag per lane, and word 16 counts lanes: a task sits in another lane here than in a
+              // triangle round, so two flagged tasks of one flush may share a lane in one schedule and not in the other.)
+              // What is left, at most kPairRoundMin tasks, goes to the triangle rounds below from triangle 2 * done on.
+              int done = 0;
+              if (PAIRS) {
+                for (; pair_round_due(n_now, done, kPairRoundMin); done += 64) {
+                  RTMI_COUNT_ROUND(kPairRoundsWord)
+                  const int ti = done + ln;
+                  if (ti < n_now) {
+                    const int w0 = tasks[ti];
+                    const int *orr = ll + (w0 >> 5) * 8;
+                    const float4 r0 = *reinterpret_cast<const float4 *>(orr), r1 = *reinterpret_cast<const float4 *>(orr + 4);
+                    const V3 ro = mk(r0.x, r0.y, r0.z), rd = mk(r1.x, r1.y, r1.z);
+                    RTMI_PAIR_TEST(2 * (pair0 + c0 + (w0 & 31)), ro, rd, (T)r0.w, true)
+                    const bool second_nearer = hit_a && hit_b && tb < ta;  // the ordered kind: posts nothing
+                    flagged = flagged || second_nearer;
+                    RTMI_COUNT_PAIR_FLAG(second_nearer)
+                    if ((hit_a || hit_b) && !second_nearer) {  // the first where it passed, else the second
+                      // (the task word once more, through an index the compiler cannot match with the first read's:
+                      // a register less through the two tests, for a read on the way to the LDS minimum)
+                      int tj = ti;
+                      asm volatile("" : "+v"(tj));
+                      const int w = tasks[tj];
+                      const unsigned long long key = ((unsigned long long)(uint32_t)__float_as_int(hit_a ? ta : tb) << 32) |
+                                                     (uint32_t)(2 * (w & 31) + (hit_a ? 0 : 1));
+                      (void)__hip_atomic_fetch_min(reinterpret_cast<unsigned long long *>(results + 2 * (w >> 5)), key,
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    }
+                  }
+                }
+              }
+              for (int t0 = 2 * done; t0 < 2 * n_now; t0 += 64) {  // (b)
+                RTMI_COUNT_ROUND(kTriRoundsWord)
                 const int ti = t0 + ln;
                 if (ti < 2 * n_now) {  // (2 n_now is even: the two lanes of a task are both here or both not)
                   const int w = tasks[ti >> 1], which = ti & 1;
@@ -448,6 +530,9 @@ __device__ __forceinline__ Hit closest_hit(const SceneDev &sc, const BvhNode *s_
             RTMI_STAT2(st.cyc[7] += stat_now() - tc2;)
           }
 #undef RTMI_TODO_LANES
+#undef RTMI_PAIR_TEST
+#undef RTMI_COUNT_ROUND
+#undef RTMI_COUNT_PAIR_FLAG
         }
         RTMI_STAT2(st.cyc[6] += stat_now() - tc1;)  // (a) + (b) + (c); [7] is (c) alone
       }

@@ -93,6 +93,17 @@ constexpr bool culls_by_slab(uint32_t m) { return (m & kFastCommon) == kFastComm
 // binary32, untextured and never the occlusion engine, which is what a key of t and place alone takes for granted.
 // Every other kernel keeps the result words and the fold, and compiles to what it was.
 constexpr bool folds_by_min(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+// The same kernels test a flush's tasks a PAIR per lane while a round of pairs runs more than kPairRoundMin / 64 full, and
+// only the short rest a triangle per lane (pair_rounds.h has the schedule and why; closest_hit.h, step (b)): a pair round
+// reads the ray record once, forms one address product and needs no exchange between lanes, and posts the keys the
+// triangle rounds would.  -DRTMI_PAIR_ROUND_MIN=<more than kListTasks> compiles the pair rounds away: every kernel is then
+// what it was before them, instruction for instruction.  Every other kernel is that anyway.
+#ifndef RTMI_PAIR_ROUND_MIN
+#define RTMI_PAIR_ROUND_MIN 32
+#endif
+constexpr int kPairRoundMin = RTMI_PAIR_ROUND_MIN;
+constexpr bool pairs_full_rounds(uint32_t m) { return (m & kFastCommon) == kFastCommon; }
+#include "pair_rounds.h"
 // Three trims of the same kernels' instruction text that leave the arithmetic on every value as it is (NOTES.md, "Fast
 // list kernels: votes, 24-bit addresses, fold colours").  RTMI_TRIM is a bit per trim so that each can be built and
 // censused alone (tools/loop_census.py --extra -DRTMI_TRIM=1); the product has all three.
@@ -136,6 +147,10 @@ constexpr int kFoldRgbBytes = 256;  // 16 rows of r, g, b, pad
 // The tasks that sent their flush through the ordered steps are counted in counters[kOrderedTasksWord], a word only
 // -DRTMI_STATS builds of mesh kernels used (rtmi_debug_counters).  closest_hit sees the words from [2] on.
 constexpr int kOrderedTasksWord = 16;
+// -DRTMI_CHECK_MARGINS builds without -DRTMI_STATS count the pair rounds and the triangle rounds of those kernels' flushes
+// in two words that otherwise only a stats build writes (rtmi_debug_counters), and in a third the tasks of the ordered kind
+// that a pair round met (tasks, one by one: word 16 counts the lanes that flagged).  The product counts none of them.
+constexpr int kPairRoundsWord = 37, kTriRoundsWord = 38, kPairFlagsWord = 39;
 // Everything the fast kernels take for granted, as the call's plan knows it (capi.hip: plan_render).  One predicate for
 // the plan, which the launch and rtmi_render_mode both read, and for the tests (rtmi_fast_path_kernel).
 struct FastPathFacts {
