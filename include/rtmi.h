@@ -924,6 +924,60 @@ int rtmi_direct_sample_mis(const rtmi_scene *s, const rtmi_direct_sample_mis_arg
 #define RTMI_LIGHTS_SPHERES 2u
 int rtmi_scene_light_kinds(rtmi_scene *s, uint32_t kinds);
 
+/* rtmi_trace_direct.  rtmi_trace with next-event estimation inside the kernel: the radiance of the loop of rtmi_bounce_list,
+ * rtmi_direct_sample_mis, rtmi_occluded_list and the compactions, in ONE launch, a path's vertex, hit record, flag and
+ * carry never leaving its lane.  Added without a version change: a caller detects it by the symbol rtmi_trace_direct.  Only
+ * the MIS estimator is offered.  rtmi_trace and every other entry are what they were.
+ *
+ * args: size (sizeof of the caller's struct), reserved (0); n, d_origins, d_dirs, max_depth, d_states, d_radiance,
+ * d_ray_counts (nullable) and d_work with rtmi_trace's meaning, shape and layout; d_light_states in d_states' layout
+ * (uint32[6][n], stride n): RNG states of their own, as rtmi_direct_sample's; d_counts (nullable): three words that are
+ * ADDED to.  d_work[0] holds the abandoned mesh searches, those of shadow queries included; d_work[1] the paths'
+ * closest-hit queries (shadow queries are not counted there).
+ *
+ * The rule, by the entries that define it.  For every good ray i, vertex by vertex, what the loop does to path i:
+ *   - vertex k is one rtmi_bounce iteration with rtmi_trace's ray handling (a bad scattered ray is followed as rtmi_trace
+ *     follows it, where the step skips it: the one difference);
+ *   - then rtmi_direct_sample_mis's rule with step = k, sample = (k + 1 < max_depth), the path the only candidate, its flag
+ *     (0 at the start) and carry private to it, the hit the rtmi_hit record rtmi_bounce would write; on a scene that opted
+ *     into RTMI_LIGHTS_SPHERES the sphere rules of rtmi_scene_light_kinds (SAMPLE in the cone, WEIGH from outside only);
+ *   - then the shadow ray (x, wi, t_max) gets exactly rtmi_occluded's answer: Ray's one normalisation of wi, and
+ *     (float)t <= t_max on HitableList::Hit(.., 1e-3, inf); a ray rtmi_occluded leaves out is clear;
+ *   - the path state advances as in rtmi_trace; d_light_states[i] advances by exactly the loop's draws (three per flat
+ *     sample, 2 + 2 * trips per sphere sample, none at a vertex that does not sample);
+ *   - a bad ray is left out: radiance 0, count 0, both states untouched.
+ * Radiance.  With the loop's final stacks E (the WEIGHed terminal emission in place), A, D (what SAMPLE wrote per layer),
+ * occ (the shadow answers) and c the path's step count:
+ *     r_path = rtmi_path_fold(dirs, steps, E, A);
+ *     acc = +0.0f, P = (1, 1, 1);  for k = 0 .. c - 1, ascending, per channel, every operation rounded on its own:
+ *         V = occ[k] ? +0.0f : D[k];   acc = acc + (P * V);   P = P * A[k];
+ *     d_radiance[i] = r_path + acc.
+ * A layer whose V is a zero may be skipped (acc began at +0.0f), and with an empty light table the result is rtmi_trace's
+ * with -0.0f turned into +0.0f.  The sum runs FORWARD where rtmi_path_fold_direct folds backward: the samples and the
+ * estimator are the same -- in exact arithmetic r_path + acc is rtmi_path_fold_direct's value -- and only the rounding
+ * order of the sum differs; the forward form needs six registers and no stack of float[layers][n][3].
+ * d_ray_counts[i] = rtmi_trace's count (steps + alive);  d_counts[0] += vertices sampled, [1] += emissions weighed,
+ * [2] += shadow rays answered occluded: the loop's counts[0], counts[1] and the sum of its occlusion stack.
+ *
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: a null scene or args, a wrong args->size, a non-zero
+ * args->reserved, every case of rtmi_trace, a null d_light_states with n > 0, and d_light_states == d_states (an aliasing
+ * the loop tolerates and one kernel that holds the path state in registers does not); RTMI_ERR_DEPTH for max_depth outside
+ * [0, RTMI_MAX_DEPTH]; then RTMI_ERR_INVALID when the current device is not the scene's.  n == 0 launches nothing. */
+typedef struct rtmi_trace_direct_args {
+  int32_t size;      /* sizeof(rtmi_trace_direct_args) of the caller: must match the library's */
+  int32_t reserved;  /* 0 */
+  int64_t n;
+  const float *d_origins, *d_dirs;
+  int32_t max_depth;
+  void *d_states;
+  void *d_light_states;
+  float *d_radiance;                  /* float[n][3] */
+  uint32_t *d_ray_counts;             /* nullable */
+  unsigned long long *d_counts;       /* nullable: three words, added to */
+  unsigned long long *d_work;         /* RTMI_TRACE_WORK_WORDS words */
+} rtmi_trace_direct_args;
+int rtmi_trace_direct(const rtmi_scene *s, const rtmi_trace_direct_args *args, void *stream);
+
 /* rtmi_occluded_list.  rtmi_occluded for the candidates of (d_list, n_list, d_count) only: the visibility query of a loop
  * whose other steps take a live-path list, and of any caller who shoots shadow or ambient-occlusion rays from the vertices
  * rtmi_bounce_list leaves behind.  Added without a version change: a caller detects it by the symbol rtmi_occluded_list.

@@ -1499,6 +1499,33 @@ int rtmi_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ radiance of caller rays with direct light
+int rtmi_trace_direct(const rtmi_scene *sp, const rtmi_trace_direct_args *p, void *stream) {
+  static_assert(sizeof(rtmi_trace_direct_args) == 88, "rtmi_trace_direct_args is 88 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!p) return fail(RTMI_ERR_INVALID, "null rtmi_trace_direct_args");
+  if (p->size != (int32_t)sizeof(rtmi_trace_direct_args) || p->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_trace_direct_args.size does not match this library, or reserved is not 0");
+  if (p->n > 0 && !p->d_light_states) return fail(RTMI_ERR_INVALID, "null light state array");
+  if (p->d_light_states && p->d_light_states == p->d_states)
+    return fail(RTMI_ERR_INVALID, "d_light_states must not be d_states: a path's draws and its light draws are two streams");
+  const Scene *s;
+  int n_cu;
+  int max_depth = p->max_depth;
+  const int rc = batch_prologue(sp, p->n, p->d_origins && p->d_dirs && p->d_states && p->d_radiance && p->d_work,
+                                "null ray, state, radiance or work array", &max_depth, &s, &n_cu);
+  if (rc || p->n == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(p->d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
+  TraceDirectBufs dx{};
+  dx.ld = s->ldev, dx.qd = s->qdev;
+  dx.light_states = reinterpret_cast<uint32_t *>(p->d_light_states), dx.counts = p->d_counts;
+  HIP_TRY(launch_trace_direct(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, s->sphere_lights, n_cu, p->n,
+                              max_depth, p->d_origins, p->d_dirs, reinterpret_cast<uint32_t *>(p->d_states), dx, p->d_radiance,
+                              p->d_ray_counts, p->d_work, st));
+  return RTMI_OK;
+}
+
 // ------------------------------------------------------------------ any-hit queries for the paths of a list
 // rtmi_occluded for rtmi_bounce_list's candidates.  The arguments first, without a HIP call, then the scene's device.
 static int occluded_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,

@@ -57,6 +57,14 @@ struct LightDev : LightTable {
   int32_t n_entries;         // 1 + the largest entry of a table light (0: no table light)
 };
 
+// What rtmi_trace_direct's kernels are told behind the trace kernel's block (trace_direct.hip; render_body.h: DIRECT).
+struct TraceDirectBufs {
+  LightDev ld;
+  QueryDev qd;                 // the recording order's names of a hit: the map is looked up by them
+  uint32_t *light_states;      // rtmi_trace's layout, stride n: read where a vertex draws, stored back after its draws
+  unsigned long long *counts;  // nullable: {vertices sampled, emissions weighed, shadow rays answered occluded}
+};
+
 constexpr int kLdsLights = 1024;  // at most this many cdf entries are staged in LDS (4 KiB); longer tables search global memory
 constexpr int kDirectThreads = 256;
 constexpr int kDirectBlocksPerCu = 8;  // the grid's cap: longer lists are walked in strides of the grid's lanes
@@ -167,51 +175,24 @@ __device__ __forceinline__ void direct_body(const Args &a, float *s_cdf) {
         const int32_t mat = h1.z, kind = h1.w;
         const bool mat_ok = mat >= 0 && mat < lt.n_mats;
         if constexpr (MIS) {
-          // WEIGH: the light of the hit by its entry (and face), every index checked before it addresses anything
           const int4 h2 = hp[2];  // entry element reserved
           const int32_t entry = h2.x, face = h2.y;
-          int32_t col = -1;
-          if (kind == QHIT_PARALLELEPIPED) col = face >= 0 && face < kHitLightAny ? face : -1;
-          else if (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM) col = kHitLightAny;
-          if constexpr (SPH)
-            if (kind == QHIT_SPHERE) col = kHitLightAny;
-          int32_t j = -1;
-          if (was && col >= 0 && entry >= 0 && entry < a.n_entries) j = a.hit_light[(int64_t)entry * kHitLightCols + col];
-          bool flat = true;
-          if constexpr (SPH) {
-            if (kind == QHIT_SPHERE) {
-              flat = false;
-              if (j >= 0 && j < lt.n_lights && reinterpret_cast<const int4 *>(lt.recs + j)[4].x == 2) {
-                const float4 *lp = reinterpret_cast<const float4 *>(lt.recs + j);
-                const float4 l0 = lp[0], l1 = lp[1], l3 = lp[3];  // c R | R2 .. | emission scale
-                const SphereCone k = sphere_cone(mk(l0.x, l0.y, l0.z), l1.x, mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2]));
-                if (k.outside) {
-                  const float av = (reinterpret_cast<const float4 *>(a.carry)[i].w * k.om) * l3.w;
-                  const float sum = av + 1.f;
-                  const bool div = av > 0.f && sum < INFINITY;
-                  const float w = av / sum;
-                  const V3 e = mk(a.emitted[i3 + 0], a.emitted[i3 + 1], a.emitted[i3 + 2]);
-                  a.emitted[i3 + 0] = div ? e.x * w : 0.f, a.emitted[i3 + 1] = div ? e.y * w : 0.f, a.emitted[i3 + 2] = div ? e.z * w : 0.f;
-                  dropped = true;
-                }
-              }
-            }
-          }
-          if (flat && j >= 0 && j < lt.n_lights) {
-            const float4 c = reinterpret_cast<const float4 *>(a.carry)[i];
-            const float4 *lp = reinterpret_cast<const float4 *>(lt.recs + j);
-            const float4 l2 = lp[2], l3 = lp[3];  // e2.z n | emission scale
-            const float cl = fabsf(dot3(mk(l2.y, l2.z, l2.w), mk(c.x, c.y, c.z)));
-            const float t = __int_as_float(h0.x);
-            const float d2 = t * t;
-            const float av = (c.w * cl) * l3.w;
-            const float sum = av + d2;
-            const bool div = av > 0.f && d2 > 0.f && sum < INFINITY;
-            const float w = av / sum;
-            const V3 e = mk(a.emitted[i3 + 0], a.emitted[i3 + 1], a.emitted[i3 + 2]);
-            a.emitted[i3 + 0] = div ? e.x * w : 0.f, a.emitted[i3 + 1] = div ? e.y * w : 0.f, a.emitted[i3 + 2] = div ? e.z * w : 0.f;
-            dropped = true;
-          }
+          // WEIGH (direct_weigh.inc: the rule's one text, rtmi_trace_direct's too), on this step's arrays
+#define RTMI_DS_HIT_LIGHT a.hit_light
+#define RTMI_DS_N_ENTRIES a.n_entries
+#define RTMI_DS_HIT_T __int_as_float(h0.x)
+#define RTMI_DS_ORIGIN mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2])
+#define RTMI_DS_CARRY reinterpret_cast<const float4 *>(a.carry)[i]
+#define RTMI_DS_EMITTED mk(a.emitted[i3 + 0], a.emitted[i3 + 1], a.emitted[i3 + 2])
+#define RTMI_DS_EMITTED_SET(ex, ey, ez) a.emitted[i3 + 0] = ex, a.emitted[i3 + 1] = ey, a.emitted[i3 + 2] = ez
+#include "direct_weigh.inc"
+#undef RTMI_DS_HIT_LIGHT
+#undef RTMI_DS_N_ENTRIES
+#undef RTMI_DS_HIT_T
+#undef RTMI_DS_ORIGIN
+#undef RTMI_DS_CARRY
+#undef RTMI_DS_EMITTED
+#undef RTMI_DS_EMITTED_SET
         } else if (was && mat_ok && (kind == QHIT_TRIANGLE || kind == QHIT_PARALLELOGRAM || kind == QHIT_PARALLELEPIPED) &&
             lt.light_mats != nullptr && ((lt.light_mats[mat >> 5] >> (mat & 31)) & 1u)) {
           a.emitted[i3 + 0] = 0.f, a.emitted[i3 + 1] = 0.f, a.emitted[i3 + 2] = 0.f;
@@ -237,109 +218,16 @@ __device__ __forceinline__ void direct_body(const Args &a, float *s_cdf) {
         if (a.sample != 0u && lt.n_lights > 0 && scattered && mat_ok && a.mats[mat].kind == MAT_LAMBERTIAN) {
           sampled = true;
           flag |= 1u;
-          Rng rng;
-          rng.d = a.light_states[0 * (int64_t)a.n + i], rng.v0 = a.light_states[1 * (int64_t)a.n + i];
-          rng.v1 = a.light_states[2 * (int64_t)a.n + i], rng.v2 = a.light_states[3 * (int64_t)a.n + i];
-          rng.v3 = a.light_states[4 * (int64_t)a.n + i], rng.v4 = a.light_states[5 * (int64_t)a.n + i];
-          const float r0 = rng_range(0.f, 1.f, rng);
-          float r1 = rng_range(0.f, 1.f, rng);
-          float r2 = 0.f;
-          if constexpr (!SPH) {
-            r2 = rng_range(0.f, 1.f, rng);
-            a.light_states[0 * (int64_t)a.n + i] = rng.d, a.light_states[1 * (int64_t)a.n + i] = rng.v0;
-            a.light_states[2 * (int64_t)a.n + i] = rng.v1, a.light_states[3 * (int64_t)a.n + i] = rng.v2;
-            a.light_states[4 * (int64_t)a.n + i] = rng.v3, a.light_states[5 * (int64_t)a.n + i] = rng.v4;
-          }
-          const int j = staged ? light_pick(s_cdf, lt.n_lights, r0) : light_pick(lt.cdf, lt.n_lights, r0);
-          const float4 *lp = reinterpret_cast<const float4 *>(lt.recs + j);
-          const float4 l0 = lp[0], l1 = lp[1], l2 = lp[2], l3 = lp[3];  // p0 e1.x | e1.yz e2.xy | e2.z n | emission scale
-          const int4 l4 = reinterpret_cast<const int4 *>(lt.recs + j)[4];
-          const V3 N = mk(__int_as_float(h0.w), __int_as_float(h1.x), __int_as_float(h1.y));
-          bool sph = false;
-          if constexpr (SPH) {
-            // a sphere light takes r1 and a point of the unit disc by rejection (the Lambertian ball sampler's kind of loop:
-            // no trip cap), every draw before any validity test; a flat light takes r2 as ever
-            sph = l4.x == 2;
-            float cp = 0.f, sp = 0.f;
-            if (sph) {
-              float da, db, s2d;
-              do {
-                da = rng_range(-1.f, 1.f, rng);
-                db = rng_range(-1.f, 1.f, rng);
-                s2d = da * da + db * db;
-              } while (!(s2d > 0.f && s2d <= 1.f));
-              const float ls = sqrtf(s2d);
-              cp = da / ls, sp = db / ls;
-            } else {
-              r2 = rng_range(0.f, 1.f, rng);
-            }
-            a.light_states[0 * (int64_t)a.n + i] = rng.d, a.light_states[1 * (int64_t)a.n + i] = rng.v0;
-            a.light_states[2 * (int64_t)a.n + i] = rng.v1, a.light_states[3 * (int64_t)a.n + i] = rng.v2;
-            a.light_states[4 * (int64_t)a.n + i] = rng.v3, a.light_states[5 * (int64_t)a.n + i] = rng.v4;
-            if (sph) {
-              x = mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2]);
-              const float R2 = l1.x;
-              const SphereCone k = sphere_cone(mk(l0.x, l0.y, l0.z), R2, x);
-              const float dc = sqrtf(k.d2c);
-              const float h = r1 * k.om;
-              const float ct = 1.f - h;
-              const float st2 = h * (2.f - h);
-              const float st = sqrtf(st2);
-              // the cone's axis and Duff et al.'s branch-free frame around it
-              const V3 w = k.wc / dc;
-              const float sg = w.z >= 0.f ? 1.f : -1.f;
-              const float ka = -1.f / (sg + w.z);
-              const float kb = (w.x * w.y) * ka;
-              const V3 u = mk(1.f + (sg * (w.x * w.x)) * ka, sg * kb, (-sg) * w.x);
-              const V3 v = mk(kb, sg + (w.y * w.y) * ka, -w.y);
-              const float sc = st * cp, ss = st * sp;
-              wi = (ct * w + sc * u) + ss * v;
-              // the near intersection of that direction with the sphere
-              const float tc = dc * ct;
-              float q = R2 - k.d2c * st2;
-              q = q > 0.f ? q : 0.f;
-              const float t = tc - sqrtf(q);
-              const float cs = dot3(N, wi);
-              valid = k.outside && cs > 0.f && t > 0.f && t < INFINITY;
-              if (valid) {
-                const float av = (cs * k.om) * l3.w;
-                float g = av;
-                if constexpr (MIS) g = av / (av + 1.f);
-                const V3 att = mk(a.attenuation[i3 + 0], a.attenuation[i3 + 1], a.attenuation[i3 + 2]);
-                dir = (att * mk(l3.x, l3.y, l3.z)) * g;
-                t_max = t * 0.999f;
-              } else {
-                wi = splat(0.f);
-              }
-            }
-          }
-          if (!sph) {
-            if (l4.x == 1 && r1 + r2 > 1.f) r1 = 1.f - r1, r2 = 1.f - r2;
-            const V3 p0 = mk(l0.x, l0.y, l0.z), e1 = mk(l0.w, l1.x, l1.y), e2 = mk(l1.z, l1.w, l2.x), ln = mk(l2.y, l2.z, l2.w);
-            const V3 q = (p0 + r1 * e1) + r2 * e2;
-            x = mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2]);
-            const V3 w = q - x;
-            const float d2 = dot3(w, w);
-            const float dist = sqrtf(d2);
-            wi = w / dist;
-            const float cs = dot3(N, wi);
-            const float cl = fabsf(dot3(ln, wi));
-            valid = d2 > 0.f && cs > 0.f && cl > 0.f && dist < INFINITY;
-            if (valid) {
-              float g;
-              if constexpr (MIS) {
-                const float av = (cs * cl) * l3.w;
-                g = av / (av + d2);
-              } else {
-                g = ((cs * cl) / d2) * l3.w;
-              }
-              const V3 att = mk(a.attenuation[i3 + 0], a.attenuation[i3 + 1], a.attenuation[i3 + 2]);
-              dir = (att * mk(l3.x, l3.y, l3.z)) * g;
-              t_max = dist * 0.999f;
-            } else {
-              wi = splat(0.f);
-            }
-          }
+          // SAMPLE (direct_sample.inc: the rule's one text, rtmi_trace_direct's too), on this step's arrays
+#define RTMI_DS_STATE(k) a.light_states[k * (int64_t)a.n + i]
+#define RTMI_DS_ORIGIN mk(a.origins[i3 + 0], a.origins[i3 + 1], a.origins[i3 + 2])
+#define RTMI_DS_HIT_N mk(__int_as_float(h0.w), __int_as_float(h1.x), __int_as_float(h1.y))
+#define RTMI_DS_ATTENUATION mk(a.attenuation[i3 + 0], a.attenuation[i3 + 1], a.attenuation[i3 + 2])
+#include "direct_sample.inc"
+#undef RTMI_DS_STATE
+#undef RTMI_DS_ORIGIN
+#undef RTMI_DS_HIT_N
+#undef RTMI_DS_ATTENUATION
           if constexpr (MIS) reinterpret_cast<float4 *>(a.carry)[i] = make_float4(d.x, d.y, d.z, dot3(N, d));
         }
       }

@@ -302,6 +302,13 @@ hipError_t launch_direct_sample_sph(const DirectMisArgs &a, bool mis, int n_cu, 
 hipError_t launch_path_fold_direct(int64_t n, int layers, const float *d_dirs, const uint32_t *d_steps, const float *d_emitted,
                                    const float *d_attenuation, const float *d_direct, const uint8_t *d_occluded,
                                    float *d_radiance, hipStream_t stream);
+// rtmi_trace with next-event estimation inside (rtmi_trace_direct; trace_direct.hip: trace_direct_kernel<F, SPH>, render_body.h
+// in its DIRECT mode): launch_trace's arguments, and dx (direct_body.h) -- the light table with the hit -> light map, the
+// names of a hit, the light states and the three counters.  sphere_lights: the table holds a sphere light (the SPH twins).
+struct TraceDirectBufs;
+hipError_t launch_trace_direct(uint32_t variant, const SceneDev &sc, bool tex_layers, bool sphere_lights, int n_cu, int64_t n,
+                               int max_depth, const float *d_o, const float *d_d, uint32_t *d_states, const TraceDirectBufs &dx,
+                               float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
 // Per-pixel sample budgets (rtmi_render_budget; calls.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).

@@ -11,6 +11,10 @@
 // resolution, Emit and Scatter, this same copy of them -- whose results are written out instead of stacked and folded:
 // no depth, no layer stack, no fold.  LIST (with STEP) is rtmi_bounce_list (bounce_list_kernel): the same step, its items
 // the entries of a list of path indices, handed to the waves by index instead of drawn from the queue.
+// DIRECT (with RAYS, without STEP) is rtmi_trace_direct (trace_direct.hip: trace_direct_kernel): rtmi_trace with next-event
+// estimation inside -- after a Lambertian vertex the lane takes one turn of this same loop with its shadow ray, the path's
+// own ray parked, and the visible light is summed forward beside the layer stack (DirectLane below).  SPH: the twin for a
+// table with sphere lights.  The vertex rule is rtmi_direct_sample_mis's own text (direct_weigh.inc, direct_sample.inc).
 // What each mode is told: RenderParams and CallExtras below.
 #pragma once
 
@@ -206,6 +210,22 @@ __device__ __forceinline__ const P &in_constant(const P *p) {
   return *(const P *)(const RT_CONSTANT P *)(uintptr_t)p;
 }
 
+// (DIRECT) What a lane carries beside its path: the forward sum of include/rtmi.h "rtmi_trace_direct" -- thr, the product
+// of the attenuations of the layers so far, and sum, the visible direct light of those layers under it --, the carry and
+// the flag of rtmi_direct_sample_mis, private to the path, and, while the lane's query is its shadow ray (shadow), the
+// path's own direction (the origin is the shadow ray's), thr x D of the layer and the shadow ray's t_max.  The three
+// counters are the lane's share of d_counts.  No other mode has any of it.
+template <bool ON>
+struct DirectLane {};
+template <>
+struct DirectLane<true> {
+  V3 thr, sum, park_d, pend;
+  float cx, cy, cz, cw;  // the carry: the once-normalised scattered direction and its N . d
+  float t_max;
+  bool flag, shadow;
+  uint32_t n_sampled, n_weighed, n_occluded;
+};
+
 // The loop on the block's fields: the kernels hand each over themselves (kernels.hip), the fields of other modes left
 // out.  The buffers are parameters of their own because only a parameter can say that nothing else points into what it
 // points to, and the compiler uses it: with the buffers as locals loaded from the block 44 of the 45 kernels compile to
@@ -214,8 +234,10 @@ __device__ __forceinline__ const P &in_constant(const P *p) {
 // (NOTES.md 11).
 // M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
 // the front end folds: with M == 0 every line below is the run-time test it was.
+// DX: DIRECT's own block (direct_body.h: TraceDirectBufs), a template parameter so that the units without a light table
+// need not know the type.
 template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0, bool STEP = false,
-          bool LIST = false>
+          bool LIST = false, bool DIRECT = false, bool SPH = false, class DX = void>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -225,8 +247,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const uint32_t *__restrict__ budget = nullptr,
                                             float *__restrict__ sq = nullptr, uint32_t *__restrict__ samples = nullptr,
                                             const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr,
-                                            const PathList *list = nullptr) {
+                                            const PathList *list = nullptr, const DX *dx = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
+  static_assert(!DIRECT || (RAYS && !STEP && M == 0), "direct light is a mode of the caller's rays, traced whole");
+  static_assert(!SPH || DIRECT, "the sphere lights' twin is a direct one");
   static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
   static_assert(!LIST || STEP, "the list is where a step's items come from");
   static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
@@ -343,6 +367,13 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   // per-lane path state
   V3 o = splat(0.f), d = splat(0.f);
   int depth = 0;
+  [[maybe_unused]] DirectLane<DIRECT> dl;
+  if constexpr (DIRECT) {
+    dl.thr = dl.sum = dl.park_d = dl.pend = splat(0.f);
+    dl.cx = dl.cy = dl.cz = dl.cw = dl.t_max = 0.f;
+    dl.flag = dl.shadow = false;
+    dl.n_sampled = dl.n_weighed = dl.n_occluded = 0u;
+  }
   // Bit 31 of depth: d is the raw vector of a new camera ray or of a Lambertian bounce, and normalize(normalize(d)) is
   // due at the top of the next iteration, which clears the bit before anything reads depth (a mark of its own, a lane
   // mask or a flag, costs more instructions in every fast kernel: NOTES.md, "Deferred normalisation")
@@ -723,6 +754,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         k++;
         depth = 0;
         active = true;
+        if constexpr (DIRECT) dl.thr = splat(1.f), dl.sum = splat(0.f), dl.flag = false;
       } else if (has_px) {
         // ray_tracing.cu:68-74 + camera.cu:57-70
         float r1 = rng_01(rng);
@@ -839,11 +871,26 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                            , st
 #endif
         );
+      // (DIRECT) The query was the lane's shadow ray: rtmi_occluded's answer is the closest hit under its filter.  What is
+      // visible joins the forward sum, the path's own ray comes back, and nothing below shades, draws or counts: the
+      // record is spent (h.ok) and the path has not ended.
+      [[maybe_unused]] bool shadow_turn = false;
+      if constexpr (DIRECT) {
+        if (dl.shadow) {
+          if (h.ok && h.t <= dl.t_max) dl.n_occluded++;
+          else dl.sum = dl.sum + dl.pend;
+          d = dl.park_d;
+          dl.shadow = false, shadow_turn = true;
+          h.ok = false;
+        }
+      }
       rays++;
+      if constexpr (DIRECT) rays -= shadow_turn ? 1u : 0u;  // (path turns only)
       if ((F & F_BVH) && lc.visit_counts != nullptr) work_px += (uint32_t)h.work;
 
       V3 result = splat(0.f);
       bool ended = true;
+      if constexpr (DIRECT) ended = !shadow_turn;
       V3 step_att = splat(0.f), step_o = o, step_d = splat(0.f);  // (STEP) Scatter's attenuation and the vector it hands to Ray
       [[maybe_unused]] bool restart = false;  // (DIFF_RESTARTS) the path ends here and the lane has started its pixel's next sample
       if constexpr (DIFF) {
@@ -1027,6 +1074,33 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
           if (m.kind == MAT_LIGHT) {
             result = rgb;  // diffuse_light.cu:5-13
+#ifdef RTMI_TRACE_DIRECT  // (the unit has direct_body.h: trace_direct.hip)
+            if constexpr (DIRECT) {
+              // WEIGH: the emission a scattered ray finds on a table light, when the vertex it left sampled the lights.  The
+              // hit as rtmi_hit names it; the vertex is this ray's origin (a light does not scatter).
+              const auto r = resolve_hit<F>(sc, dx->qd, h, o, d);
+              const int32_t kind = r.kind, entry = r.entry, face = r.element;
+              const bool was = dl.flag;
+              const LightTable &lt = dx->ld;
+              bool dropped = false;
+#define RTMI_DS_HIT_LIGHT dx->ld.hit_light
+#define RTMI_DS_N_ENTRIES dx->ld.n_entries
+#define RTMI_DS_HIT_T r.t
+#define RTMI_DS_ORIGIN o
+#define RTMI_DS_CARRY make_float4(dl.cx, dl.cy, dl.cz, dl.cw)
+#define RTMI_DS_EMITTED result
+#define RTMI_DS_EMITTED_SET(ex, ey, ez) result = mk(ex, ey, ez)
+#include "direct_weigh.inc"
+#undef RTMI_DS_HIT_LIGHT
+#undef RTMI_DS_N_ENTRIES
+#undef RTMI_DS_HIT_T
+#undef RTMI_DS_ORIGIN
+#undef RTMI_DS_CARRY
+#undef RTMI_DS_EMITTED
+#undef RTMI_DS_EMITTED_SET
+              dl.n_weighed += dropped ? 1u : 0u;
+            }
+#endif
           } else {
             const float dn = dot3(d, nrm);
             V3 nd = splat(0.f);
@@ -1039,6 +1113,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 // normalize(S + n), then Ray's constructor (lambertian.cu:41-42) (DEFER: at the top of the loop)
                 // (STEP: normalize(S + n) alone -- the next step's Ray normalises again)
                 nd = STEP ? unit3_rn(s + nrm) : DEFER ? s + nrm : unit3_rn_twice<VOTE>(s + nrm);
+                if constexpr (DIRECT) {  // the same two normalisations, the first kept: the carry's direction, as a step leaves it
+                  const V3 once = unit3_rn(s + nrm);
+                  dl.cx = once.x, dl.cy = once.y, dl.cz = once.z;
+                  nd = unit3_rn(once);
+                }
                 scattered = true;
               }
             } else if (m.kind == MAT_METAL) {  // metal.cu:12-25
@@ -1064,6 +1143,51 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               scattered = !(zero || nan);
               if (!STEP && scattered) nd = unit3_rn<VOTE>(nd);  // Ray's constructor (STEP: the next step's)
             }
+#ifdef RTMI_TRACE_DIRECT
+            if constexpr (DIRECT) {
+              // SAMPLE, with step = depth and sample = (depth + 1 < max_depth): the path is the rule's only candidate.  o, d
+              // still hold the ray that came in, p is the vertex, layer_att the layer A[depth] as the fold reads it.
+              dl.flag = false;  // (a Metal or Dielectric vertex, or one that does not sample, clears it)
+              if (scattered) {
+                const V3 layer_att = ((F & F_TEX) && (layer >> 31)) ? texel_rgb(layer) : rgb;
+                const LightTable &lt = dx->ld;
+                if (m.kind == MAT_LAMBERTIAN && depth + 1 < fr.max_depth && lt.n_lights > 0 &&
+                    (dl.cx != 0.f || dl.cy != 0.f || dl.cz != 0.f)) {
+                  constexpr bool MIS = true, staged = false;  // (the cdf is searched where it lies: the LDS layout is the trace kernel's)
+                  const float *s_cdf = nullptr;
+                  const auto r = resolve_hit<F>(sc, dx->qd, h, o, d);
+                  const int64_t ls_n = n_items, ls_q = (int64_t)q32;
+                  V3 wi = splat(0.f), dir = splat(0.f), x = splat(0.f);
+                  float t_max = 0.f;
+                  bool valid = false;
+#define RTMI_DS_STATE(k) dx->light_states[k * ls_n + ls_q]
+#define RTMI_DS_ORIGIN p
+#define RTMI_DS_HIT_N r.n
+#define RTMI_DS_ATTENUATION layer_att
+#include "direct_sample.inc"
+#undef RTMI_DS_STATE
+#undef RTMI_DS_ORIGIN
+#undef RTMI_DS_HIT_N
+#undef RTMI_DS_ATTENUATION
+                  dl.cw = dot3(r.n, mk(dl.cx, dl.cy, dl.cz));
+                  dl.flag = true;
+                  dl.n_sampled++;
+                  if (valid) {
+                    // the shadow ray (x, wi, t_max) as rtmi_occluded takes it: Ray's one normalisation, and a ray it would
+                    // leave out is clear.  The lane's next query is this ray; the path's own direction waits in park_d.
+                    const V3 sd = unit3_rn(wi);
+                    dl.pend = mk(dl.thr.x * dir.x, dl.thr.y * dir.y, dl.thr.z * dir.z);
+                    if (finite3(x) && finite3(wi) && finite3(sd) && (sd.x != 0.f || sd.y != 0.f || sd.z != 0.f) && t_max == t_max) {
+                      dl.shadow = true, dl.t_max = t_max, dl.park_d = sd;  // (swapped with nd below)
+                    } else {
+                      dl.sum = dl.sum + dl.pend;
+                    }
+                  }
+                }
+                dl.thr = mk(dl.thr.x * layer_att.x, dl.thr.y * layer_att.y, dl.thr.z * layer_att.z);
+              }
+            }
+#endif
             if constexpr (STEP) {  // the layer itself instead of its place on the stack: what the fold would read of it
               if (scattered) {
                 step_att = ((F & F_TEX) && (layer >> 31)) ? texel_rgb(layer) : rgb;
@@ -1088,6 +1212,9 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
               o = p;
               d = nd;  // (normalised by Ray's constructor in its material's branch above; DEFER, Lambertian: owed)
               ended = false;
+              if constexpr (DIRECT) {
+                if (dl.shadow) d = dl.park_d, dl.park_d = nd;  // the shadow ray first, from the same origin
+              }
             }
           }
         }
@@ -1229,6 +1356,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
           }
         }
         color = color + result;
+        if constexpr (DIRECT) color = color + dl.sum;  // r_path + the forward sum: one addition per channel
         if constexpr (BUDGET)  // the product and the sum rounded separately, so that a binary32 restatement is exact
           moment = mk(__fadd_rn(moment.x, __fmul_rn(result.x, result.x)), __fadd_rn(moment.y, __fmul_rn(result.y, result.y)),
                       __fadd_rn(moment.z, __fmul_rn(result.z, result.z)));
@@ -1243,6 +1371,14 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   if (RTMI_PRIO) wave_priority_leave(lc.prio_tab);
 #undef RTMI_CHAINS
 #undef RTMI_PRIO
+  if constexpr (DIRECT) {  // d_counts: vertices sampled, emissions weighed, shadow rays answered occluded -- a wave reduce each
+    const uint32_t v[3] = {dl.n_sampled, dl.n_weighed, dl.n_occluded};
+    for (int c = 0; c < 3; c++) {
+      unsigned long long total = v[c];
+      for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off);
+      if ((threadIdx.x & 63) == 0 && total && dx->counts) atomicAdd(&dx->counts[c], total);
+    }
+  }
   {  // total closest-hit queries: wave reduce, one atomic per wave
     unsigned long long ray_total = ray_acc;
     for (int off = 32; off > 0; off >>= 1) ray_total += __shfl_down(ray_total, off);

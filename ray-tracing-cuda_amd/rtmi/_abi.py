@@ -131,6 +131,13 @@ class DirectSampleMisArgs(C.Structure):
                 ("d_direct", C.c_void_p), ("d_carry", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
+class TraceDirectArgs(C.Structure):
+    """rtmi_trace_direct_args of include/rtmi.h (the arrays of one rtmi_trace_direct call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("d_origins", C.c_void_p), ("d_dirs", C.c_void_p),
+                ("max_depth", C.c_int32), ("d_states", C.c_void_p), ("d_light_states", C.c_void_p), ("d_radiance", C.c_void_p),
+                ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p), ("d_work", C.c_void_p)]
+
+
 class DenoiseOpts(C.Structure):
     """rtmi_denoise_opts of include/rtmi.h."""
     _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
@@ -275,6 +282,7 @@ SYMBOLS = [
     ("rtmi_scene_light_kinds", C.c_int, [C.c_void_p, C.c_uint32]),
     ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
     ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
+    ("rtmi_trace_direct", C.c_int, [C.c_void_p, C.POINTER(TraceDirectArgs), C.c_void_p]),
 ]
 
 # RTMI_LIGHTS_* of include/rtmi.h (rtmi_scene_light_kinds)

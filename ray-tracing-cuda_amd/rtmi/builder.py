@@ -5,10 +5,10 @@ import numpy as np
 
 from . import _abi
 from ._abi import (HIT_WORDS, LIGHT_DTYPE, MAX_DEPTH, STATE_WORDS, TRACE_WORK_WORDS, TRANSFORM_FN, DirectSampleMisArgs, RtmiError,
-                   _addr, _camera21, _check, _f, _fp, _u32p, lib)
+                   TraceDirectArgs, _addr, _camera21, _check, _f, _fp, _u32p, lib)
 from ._tensors import _check_batch, _need, _new, _out_buffer, _ptr, _ptrs, _stream, _torch
-from .wavefront import (Bounce, DirectSample, Hits, Occlusion, Steps, Trace, _list_args, _new_paths, _path_compact, path_fold,
-                        path_fold_direct)
+from .wavefront import (Bounce, DirectSample, Hits, Occlusion, Steps, Trace, TraceDirect, _list_args, _new_paths, _path_compact,
+                        path_fold, path_fold_direct)
 
 
 class _CommitOptions:
@@ -24,7 +24,42 @@ class _CommitOptions:
         return self
 
 
-class SceneBuilder(_CommitOptions):
+class _FusedTraces:
+    """The entries that run a whole loop of steps in one kernel.  A base of ``SceneBuilder``: they are the builder's methods."""
+
+    def trace_direct(self, origins, directions, states, light_states, max_depth, count_rays=False, out=None):
+        """``trace`` with next-event estimation inside the kernel (rtmi_trace_direct), enqueued on torch's current stream:
+        per path the samples, weights and shadow answers of ``trace_steps(compact=True, direct="mis")`` in one launch, the
+        visible light summed forward along the path (include/rtmi.h states the sum; it differs from that loop's fold by the
+        rounding order only).
+
+        ``origins`` / ``directions`` / ``states`` / ``max_depth`` / ``count_rays`` / ``out`` as for ``trace``;
+        ``light_states``: a contiguous (6, N) int32 CUDA tensor of RNG states of their own (``rng_states`` with
+        ``first=N``), advanced in place by exactly the loop's draws, and not ``states`` itself.  Returns ``TraceDirect``;
+        call ``.check()`` on it before trusting the answers of a mesh scene."""
+        torch = _torch()
+        n, dev, _ = _check_batch("rtmi_trace_direct", origins, directions)
+        _need(states, "states", (STATE_WORDS, n), dev, torch.int32, words="(6, N)")
+        _need(light_states, "light_states", (STATE_WORDS, n), dev, torch.int32, words="(6, N)")
+        max_depth = int(max_depth)
+        if not 0 <= max_depth <= MAX_DEPTH:
+            raise RtmiError("max_depth %d outside [0, %d]" % (max_depth, MAX_DEPTH))
+        out = _out_buffer(out, "(N, 3)", (n, 3), dev, torch.float32)
+        stream = self._stream(dev)
+        origins, directions = origins.contiguous(), directions.contiguous()
+        rays = _new(dev, (n,), torch.int32) if count_rays else None
+        work = _new(dev, (TRACE_WORK_WORDS,), torch.int64, zero=True)  # (n == 0 leaves it untouched)
+        counts = _new(dev, (3,), torch.int64, zero=True)
+        a = TraceDirectArgs()
+        a.size, a.reserved, a.n, a.max_depth = C.sizeof(TraceDirectArgs), 0, n, max_depth
+        a.d_origins, a.d_dirs, a.d_states, a.d_light_states = _addr(origins), _addr(directions), _addr(states), _addr(light_states)
+        a.d_radiance, a.d_ray_counts, a.d_counts, a.d_work = _addr(out), _addr(rays), _addr(counts), _addr(work)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_trace_direct(self.h, C.byref(a), stream), "rtmi_trace_direct")
+        return TraceDirect(out, rays, work, counts, (origins, directions, states, light_states))
+
+
+class SceneBuilder(_CommitOptions, _FusedTraces):
     """Builder protocol of rtmi/scenes.py over the C ABI's scene recorder.
 
     ``seed`` seeds the host copy of pixel 0's RNG stream that scene programs may draw

@@ -202,7 +202,9 @@ class Renderer:
         paths with next-event estimation, the same expectation and less variance where small lights light the scene; the
         sums are then not ``render_budget``'s.  Its light states are seeded from the renderer's seed with first = items on
         the first such call and carried on.  ``direct="mis"`` is passed through to ``trace_steps`` in the same way
-        (multiple importance sampling); ``self.carry`` is then the last sample's carry tensor, else None."""
+        (multiple importance sampling); ``self.carry`` is then the last sample's carry tensor, else None.
+        ``direct="fused"`` traces every sample with one ``SceneBuilder.trace_direct`` on the same light states: the
+        ``"mis"`` loop's samples in one kernel per sample, its sums up to the rounding order of the direct light's sum."""
         torch = self.torch
         self._unposted("render_rays")
         self._budget_arg(budget)
@@ -218,6 +220,15 @@ class Renderer:
                 self.camera_rays(sample, budget, projection, out=(origins, dirs))
                 if each is not None:
                     each(sample, origins, dirs)
+                if isinstance(direct, str) and direct == "fused":
+                    if self.light_states is None:
+                        self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
+                    t = self.scene.trace_direct(origins, dirs, self.states, self.light_states, int(self.frame.max_depth),
+                                                count_rays=count_rays, out=radiance)
+                    self.budget_abandoned += t.work[0]
+                    self.rays_total += t.work[1]
+                    self.sample_add(sample, radiance, t.rays, budget)
+                    continue
                 if direct:
                     if self.light_states is None:
                         self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)

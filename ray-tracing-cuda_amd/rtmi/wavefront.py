@@ -71,6 +71,20 @@ class Trace:
         return int(self.work[1].item())
 
 
+class TraceDirect(Trace):
+    """What ``SceneBuilder.trace_direct`` returns: a ``Trace`` (``rgb``, ``rays``, ``work``, ``check()``, ``total_rays()`` --
+    the paths' closest-hit queries, shadow queries not among them) and ``counts`` (3,) int64: vertices sampled, emissions
+    weighed, shadow rays answered occluded."""
+
+    def __init__(self, rgb, rays, work, counts, keep):
+        Trace.__init__(self, rgb, rays, work, keep)
+        self.counts = counts
+
+    def check(self):
+        _complete(self.work[0], "rtmi_trace_direct")
+        return self
+
+
 class Bounce:
     """What ``SceneBuilder.bounce`` returns: ``emitted`` and ``attenuation`` (N, 3) float32; ``hits`` the step's ``Hits``
     (views into an (N, 12) int32 buffer, ``hits.raw``) or None when they were not asked for; ``steps`` (N,) int32, each
