@@ -1207,6 +1207,58 @@ int rtmi_render_features(const rtmi_scene *s, const rtmi_frame *f, const uint32_
 int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const uint32_t *d_samples,
                           const rtmi_features *out, void *stream);
 
+/* ---------------------------------------------------------- render direct --
+ * rtmi_render_direct.  rtmi_render_budget / rtmi_render_features whose every sample is traced with next-event estimation
+ * inside the kernel (rtmi_trace_direct's estimator): per-pixel budgets in; sums, second moments, sample and ray counts
+ * and the optional first-hit features out, in ONE launch, so that rtmi_budget_plan, rtmi_resolve, rtmi_resolve_variance,
+ * rtmi_resolve_features, rtmi_denoise and rtmi_accumulate follow unchanged.  Added without a version change: a caller
+ * detects it by the symbol rtmi_render_direct.  rtmi_render_budget, rtmi_render_features and every other entry are what
+ * they were.
+ *
+ * args: size (sizeof of the caller's struct), reserved (0); d_budget, d_states, d_sum, d_sq (nullable), d_samples,
+ * d_ray_counts (nullable) with rtmi_render_budget's meaning, nullability and accumulation; d_light_states in d_states'
+ * layout (uint32[6][items], stride items = rtmi_frame_work_items(f)): RNG states of their own, as rtmi_trace_direct's,
+ * carried across calls; features (nullable) with rtmi_render_features' meaning; d_counts (nullable): three words that are
+ * ADDED to; d_work (RTMI_BUDGET_WORK_WORDS words): afterwards [0] holds the abandoned mesh searches, those of shadow
+ * queries included, [1] the paths' closest-hit queries (shadow queries are not counted there).
+ *
+ * The rule, by the entries that define it.  For every work item q of the shard that is a pixel, with
+ * b = min(d_budget[q], f->spp), and for sample index k = 0 .. b - 1 in order:
+ *   - the ray is the one rtmi_camera_rays (kind RTMI_PROJ_CAMERA) makes for the item's next sample from d_states[q]: the
+ *     same jitter and lens draws, the direction normalised once;
+ *   - the radiance x, both state advances, the query count and the three counters are rtmi_trace_direct's for that one ray,
+ *     with d_states[q] and d_light_states[q] as the path's two streams: x = r_path + acc, ONE binary32 addition per channel;
+ *   - the fold is rtmi_sample_add's: d_sum[q][c] += x, d_sq[q][c] += x * x (the product and the sum each rounded on its
+ *     own, no fused multiply-add), d_samples[q] += 1, d_ray_counts[q] += the path's closest-hit queries (a shadow query
+ *     is not counted);
+ *   - with features, the feature sums are rtmi_render_features' for those same samples: a shadow query is not a primary
+ *     hit, and the primary hits do not depend on direct light.
+ * An item with b == 0, and a padding item: nothing of it is read or written, its light state included.  With an empty
+ * light table no light state moves and the sums are rtmi_render_budget's for buffers that hold no -0.0f (a sample's -0.0f
+ * is added as +0.0f).
+ * So the call is bit for bit the loop "for k: rtmi_camera_rays, rtmi_trace_direct, rtmi_sample_add" on the same buffers,
+ * without the rays, radiances and counts crossing memory and without the host knowing the largest budget.
+ *
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: a null scene or args, a wrong args->size, a non-zero
+ * args->reserved, every case of rtmi_render_budget and rtmi_render_features, a null d_light_states (with items > 0), and
+ * d_light_states == d_states; RTMI_ERR_DEPTH for max_depth outside [0, RTMI_MAX_DEPTH] (and for max_depth == 0 with a
+ * feature buffer); then RTMI_ERR_INVALID when the current device is not the scene's. */
+typedef struct rtmi_render_direct_args {
+  int32_t size;      /* sizeof(rtmi_render_direct_args) of the caller: must match the library's */
+  int32_t reserved;  /* 0 */
+  const uint32_t *d_budget;           /* uint32[items] */
+  void *d_states;
+  void *d_light_states;
+  float *d_sum;                       /* float[items][3]; accumulates */
+  float *d_sq;                        /* nullable; accumulates */
+  uint32_t *d_samples;                /* uint32[items]; accumulates */
+  uint32_t *d_ray_counts;             /* nullable; accumulates */
+  const rtmi_features *features;      /* nullable */
+  unsigned long long *d_counts;       /* nullable: three words, added to */
+  unsigned long long *d_work;         /* RTMI_BUDGET_WORK_WORDS words */
+} rtmi_render_direct_args;
+int rtmi_render_direct(const rtmi_scene *s, const rtmi_frame *f, const rtmi_render_direct_args *args, void *stream);
+
 /* ---------------------------------------------------------------- denoise --
  * A variance- and feature-guided a-trous filter (edge-avoiding wavelets) for frames of a few samples per pixel, on what
  * rtmi_render_budget and rtmi_render_features leave behind.  Added without a version change: a caller detects it by the

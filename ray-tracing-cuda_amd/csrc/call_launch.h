@@ -1,5 +1,6 @@
 // The one launcher of the entries that own their device state (calls.hip: rtmi_trace, rtmi_render_budget,
-// rtmi_render_features, rtmi_bounce, rtmi_bounce_list; trace_direct.hip: rtmi_trace_direct).  Host templates only.
+// rtmi_render_features, rtmi_bounce, rtmi_bounce_list; trace_direct.hip: rtmi_trace_direct; render_direct.hip:
+// rtmi_render_direct).  Host templates only.
 #pragma once
 // (included inside namespace rtmi, after render_body.h and launch_cfg.h)
 

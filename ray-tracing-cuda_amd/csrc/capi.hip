@@ -1580,9 +1580,12 @@ static bool feature_bufs(const rtmi_features *feat, FeatureBufs *fb) {
 }
 static const char *const kBadFeatures = "rtmi_features.size does not match this library, or reserved is not 0";
 
-int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
+// rtmi_render_features, and with `direct` rtmi_render_direct: the same checks in the same order -- the light states' own
+// among the arguments', before the scene is looked at -- and the DIRECT twins of the two kernels.
+static int render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
                          float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, const rtmi_features *feat,
-                         unsigned long long *d_work, void *stream) {
+                         unsigned long long *d_work, void *stream, bool direct, void *d_light_states,
+                         unsigned long long *d_counts) {
   if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
   FeatureBufs fb;
   if (!feature_bufs(feat, &fb)) return fail(RTMI_ERR_INVALID, kBadFeatures);
@@ -1591,6 +1594,9 @@ int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32
   int rc = budget_frame(f, d_budget && d_states && d_sum && d_samples && d_work,
                         "null budget, state, sum, sample-count or work array", &d);
   if (rc) return rc;
+  if (direct && d.items > 0 && !d_light_states) return fail(RTMI_ERR_INVALID, "null light state array");
+  if (direct && d_light_states && d_light_states == d_states)
+    return fail(RTMI_ERR_INVALID, "d_light_states must not be d_states: a path's draws and its light draws are two streams");
   // (before the scene is looked at: max_depth is the frame's, and at depth 0 Trace never looks at the primary record)
   if (features && d.max_depth == 0)
     return fail(RTMI_ERR_DEPTH, "max_depth must be at least 1 with a feature buffer: at depth 0 Trace never looks at the primary hit");
@@ -1606,14 +1612,40 @@ int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32
   // the counter words start from zero; the argument block behind them is written by launch_budget
   HIP_TRY(hipMemsetAsync(d_work, 0, kCallParamsOffset, st));
   if (d.spp == 0) return RTMI_OK;  // (every budget is capped at 0: nothing to render)
+  if (direct) {
+    TraceDirectBufs dx{};
+    dx.ld = s->ldev, dx.qd = s->qdev;
+    dx.light_states = reinterpret_cast<uint32_t *>(d_light_states), dx.counts = d_counts;
+    HIP_TRY(launch_budget_direct(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, s->sphere_lights, n_cu, d,
+                                 d_budget, reinterpret_cast<uint32_t *>(d_states), dx, d_sum, d_sq, d_samples, d_ray_counts, &fb,
+                                 d_work, st));
+    return RTMI_OK;
+  }
   HIP_TRY(launch_budget(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, d, d_budget,
                         reinterpret_cast<uint32_t *>(d_states), d_sum, d_sq, d_samples, d_ray_counts, &fb, d_work, st));
   return RTMI_OK;
 }
 
+int rtmi_render_features(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
+                         float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, const rtmi_features *feat,
+                         unsigned long long *d_work, void *stream) {
+  return render_budget(sp, f, d_budget, d_states, d_sum, d_sq, d_samples, d_ray_counts, feat, d_work, stream, false, nullptr, nullptr);
+}
+
 int rtmi_render_budget(const rtmi_scene *sp, const rtmi_frame *f, const uint32_t *d_budget, void *d_states, float *d_sum,
                        float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, unsigned long long *d_work, void *stream) {
   return rtmi_render_features(sp, f, d_budget, d_states, d_sum, d_sq, d_samples, d_ray_counts, nullptr, d_work, stream);
+}
+
+// ------------------------------------------------------------------ the budget render with direct light
+int rtmi_render_direct(const rtmi_scene *sp, const rtmi_frame *f, const rtmi_render_direct_args *p, void *stream) {
+  static_assert(sizeof(rtmi_render_direct_args) == 88, "rtmi_render_direct_args is 88 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!p) return fail(RTMI_ERR_INVALID, "null rtmi_render_direct_args");
+  if (p->size != (int32_t)sizeof(rtmi_render_direct_args) || p->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_render_direct_args.size does not match this library, or reserved is not 0");
+  return render_budget(sp, f, p->d_budget, p->d_states, p->d_sum, p->d_sq, p->d_samples, p->d_ray_counts, p->features, p->d_work,
+                       stream, true, p->d_light_states, p->d_counts);
 }
 
 int rtmi_resolve_features(const rtmi_frame *f, const rtmi_features *sums, const uint32_t *d_samples,

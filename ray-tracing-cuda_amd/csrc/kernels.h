@@ -320,6 +320,13 @@ hipError_t launch_budget(uint32_t variant, const SceneDev &sc, bool tex_layers, 
 // Per-item means of those sums (rtmi_resolve_features): null buffers of `out` are skipped.
 hipError_t launch_resolve_features(const FrameDev &fr, const FeatureBufs &sums, const uint32_t *d_samples,
                                    const FeatureBufs &out, hipStream_t stream);
+// launch_budget with next-event estimation inside (rtmi_render_direct; render_direct.hip: budget_direct_kernel<F, SPH> and
+// feature_direct_kernel<F, SPH>, render_body.h in its DIRECT mode with BUDGET): dx as launch_trace_direct's, its light states
+// uint32[6][fr.items].
+hipError_t launch_budget_direct(uint32_t variant, const SceneDev &sc, bool tex_layers, bool sphere_lights, int n_cu,
+                                const FrameDev &fr, const uint32_t *d_budget, uint32_t *d_states, const TraceDirectBufs &dx,
+                                float *d_sum, float *d_sq, uint32_t *d_samples, uint32_t *d_ray_counts, const FeatureBufs *feat,
+                                unsigned long long *d_work, hipStream_t stream);
 // The next pass's budget per work item by the stopping rule of include/rtmi.h; d_totals[2] = {items with a budget, sum of
 // budgets}, zeroed on the stream first.
 hipError_t launch_budget_plan(const FrameDev &fr, int min_samples, int max_samples, int step, float tolerance, float floor,

@@ -15,6 +15,9 @@
 // estimation inside -- after a Lambertian vertex the lane takes one turn of this same loop with its shadow ray, the path's
 // own ray parked, and the visible light is summed forward beside the layer stack (DirectLane below).  SPH: the twin for a
 // table with sphere lights.  The vertex rule is rtmi_direct_sample_mis's own text (direct_weigh.inc, direct_sample.inc).
+// DIRECT with BUDGET (with or without FEATURES) is rtmi_render_direct (render_direct.hip: budget_direct_kernel,
+// feature_direct_kernel): the budget render whose every sample is traced that way -- the lane's forward sum restarts with
+// each sample, the light state is the work item's, and a sample's value is its path's radiance + its forward sum.
 // What each mode is told: RenderParams and CallExtras below.
 #pragma once
 
@@ -249,7 +252,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                                             const FeatureBufs *feat = nullptr, const StepBufs *step = nullptr,
                                             const PathList *list = nullptr, const DX *dx = nullptr) {
   static_assert(!(RAYS && BUDGET), "one work-item source at a time");
-  static_assert(!DIRECT || (RAYS && !STEP && M == 0), "direct light is a mode of the caller's rays, traced whole");
+  static_assert(!DIRECT || ((RAYS || BUDGET) && !STEP && !LIST && M == 0),
+                "direct light is a mode of the caller's rays or of the budget's samples, traced whole");
   static_assert(!SPH || DIRECT, "the sphere lights' twin is a direct one");
   static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
   static_assert(!LIST || STEP, "the list is where a step's items come from");
@@ -800,6 +804,10 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         }
         depth = DEFER && !DIFF ? kOwesBit : 0;  // (DEFER: depth 0, normalisation owed; DIFF: every active lane owes)
         active = true;
+        if constexpr (DIRECT) {  // (BUDGET) every sample is a path of its own: the forward sum, the flag and the carry restart
+          dl.thr = splat(1.f), dl.sum = splat(0.f), dl.flag = false;
+          dl.cx = dl.cy = dl.cz = dl.cw = 0.f;
+        }
       }
     }
     // The one site of normalize(normalize(v)): the camera rays formed just above and the Lambertian directions the
@@ -1355,8 +1363,11 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
             result = mk(0.f + a.x * result.x, 0.f + a.y * result.y, 0.f + a.z * result.z);
           }
         }
+        // (DIRECT with BUDGET) the sample's value is r_path + the forward sum, one addition per channel, and it is that
+        // value the sum and the moment take
+        if constexpr (DIRECT && BUDGET) result = result + dl.sum;
         color = color + result;
-        if constexpr (DIRECT) color = color + dl.sum;  // r_path + the forward sum: one addition per channel
+        if constexpr (DIRECT && !BUDGET) color = color + dl.sum;  // r_path + the forward sum: one addition per channel
         if constexpr (BUDGET)  // the product and the sum rounded separately, so that a binary32 restatement is exact
           moment = mk(__fadd_rn(moment.x, __fmul_rn(result.x, result.x)), __fadd_rn(moment.y, __fmul_rn(result.y, result.y)),
                       __fadd_rn(moment.z, __fmul_rn(result.z, result.z)));

@@ -138,6 +138,13 @@ class TraceDirectArgs(C.Structure):
                 ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p), ("d_work", C.c_void_p)]
 
 
+class RenderDirectArgs(C.Structure):
+    """rtmi_render_direct_args of include/rtmi.h (the arrays of one rtmi_render_direct call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("d_budget", C.c_void_p), ("d_states", C.c_void_p),
+                ("d_light_states", C.c_void_p), ("d_sum", C.c_void_p), ("d_sq", C.c_void_p), ("d_samples", C.c_void_p),
+                ("d_ray_counts", C.c_void_p), ("features", C.POINTER(Features)), ("d_counts", C.c_void_p), ("d_work", C.c_void_p)]
+
+
 class DenoiseOpts(C.Structure):
     """rtmi_denoise_opts of include/rtmi.h."""
     _fields_ = [("size", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("demodulate", C.c_int32),
@@ -283,6 +290,7 @@ SYMBOLS = [
     ("rtmi_occluded_list", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
     ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
     ("rtmi_trace_direct", C.c_int, [C.c_void_p, C.POINTER(TraceDirectArgs), C.c_void_p]),
+    ("rtmi_render_direct", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderDirectArgs), C.c_void_p]),
 ]
 
 # RTMI_LIGHTS_* of include/rtmi.h (rtmi_scene_light_kinds)

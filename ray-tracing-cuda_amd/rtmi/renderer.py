@@ -5,8 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (BUDGET_WORK_WORDS, MAX_DEPTH, MODE_FIELDS, STATE_WORDS, TRACE_WORK_WORDS, Projection, PathAdvanceArgs, RtmiError,
-                   _addr, _check, _u32p, adaptive_opts, feature_bufs, lib, make_frame, work_items)
+from ._abi import (BUDGET_WORK_WORDS, MAX_DEPTH, MODE_FIELDS, STATE_WORDS, TRACE_WORK_WORDS, Projection, PathAdvanceArgs,
+                   RenderDirectArgs, RtmiError, _addr, _check, _u32p, adaptive_opts, feature_bufs, lib, make_frame, work_items)
 from ._tensors import _need, _new, _out_buffer, _ptr, _stream
 from .filters import denoise
 from .wavefront import _list_args, _new_paths, rng_states
@@ -24,7 +24,45 @@ is not renormalised), ``depth`` (items,) float32 (the mean over the samples that
 ``alpha`` (items,) float32 (the share of the samples that hit a surface)."""
 
 
-class Renderer:
+class _DirectRenders:
+    """The budget renders with next-event estimation inside the kernel.  A base of ``Renderer``: they are the renderer's
+    methods."""
+
+    def render_direct(self, budget, count_rays=True, features=False):
+        """``render_budget(budget, count_rays, features)`` with every sample traced with next-event estimation inside the
+        kernel (rtmi_render_direct), enqueued on torch's current stream: one launch for what
+        ``render_rays(budget, direct="fused")`` composes of three per sample index, bit for bit its sums, moments, counts
+        and states, in the buffers of ``render_budget`` -- so ``plan``, ``resolve``, ``resolve_variance``, ``denoise`` and
+        ``accumulate`` follow unchanged.  The light states are ``render_rays``' own -- seeded from the scene's seed with
+        first = items on first use, kept in ``light_states`` -- so the two interleave; the three counters (vertices
+        sampled, emissions weighed, shadow rays answered occluded) add up in ``direct_counts``, a (3,) int64 tensor zeroed
+        on first use."""
+        self._need(budget, "budget", (), self.torch.int32)
+        self._budget_buffers()
+        with self.torch.cuda.device(self.device):
+            if self.direct_counts is None:
+                self.direct_counts = self._new((3,), self.torch.int64, zero=True)
+            a = RenderDirectArgs()
+            a.size, a.reserved = C.sizeof(RenderDirectArgs), 0
+            a.d_budget, a.d_states, a.d_light_states = _addr(budget), _addr(self.states), _addr(self._light_states())
+            a.d_sum, a.d_sq, a.d_samples = _addr(self.sum), _addr(self.sq), _addr(self.samples)
+            a.d_ray_counts = _addr(self.budget_rays) if count_rays else None
+            a.d_counts, a.d_work = _addr(self.direct_counts), _addr(self.d_work)
+            feat = None
+            if features:
+                self._feature_buffers()
+                feat = feature_bufs(self.albedo, self.normal, self.depth, self.coverage)
+                a.features = C.pointer(feat)
+            _check(self.L.rtmi_render_direct(self.scene.h, C.byref(self.frame), C.byref(a), self._stream()), "rtmi_render_direct")
+            self.budget_abandoned += self.d_work[0]  # (stream-ordered: the next call resets d_work)
+        return self
+
+    def render_adaptive_direct(self, min_spp, max_spp, step, tolerance, floor=0.01, post=True, features=False):
+        """``render_adaptive`` whose every pass is ``render_direct``: the same plan, stopping rule and result."""
+        return self._adaptive(self.render_direct, min_spp, max_spp, step, tolerance, floor, post, features)
+
+
+class Renderer(_DirectRenders):
     """One rank's share of a frame: device buffers (torch), RNG init, render, untile.
 
     Mirrors what the reference's ``Main``/``DistributedMain`` do around the kernel
@@ -51,6 +89,7 @@ class Renderer:
         self.albedo = self.normal = self.depth = self.coverage = None
         # ... and what render_rays and render_wavefront keep between calls; the scratch of the last render(opts)
         self.rays_total = self.wavefront_counts = self.light_states = self.carry = self._last_scratch = None
+        self.direct_counts = None  # render_direct: (3,) int64, vertices sampled, emissions weighed, shadow rays occluded
 
     def _stream(self):
         return _stream(self.device)
@@ -127,6 +166,13 @@ class Renderer:
         if not self.items:
             return 0
         return min(spp, int((budget.to(self.torch.int64) & 0xffffffff).max().item()))  # (uint32 words: a negative int32 is a large one)
+
+    def _light_states(self):
+        """The light states of the direct renders (``render_rays(direct=...)``, ``render_direct``): seeded from
+        the scene's seed with first = items on first use and carried on, so the ways to direct light interleave."""
+        if self.light_states is None:
+            self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
+        return self.light_states
 
     def render_budget(self, budget, count_rays=True, features=False):
         """``budget[q]`` more samples (at most the frame's spp per call) of every pixel q of this shard
@@ -221,19 +267,15 @@ class Renderer:
                 if each is not None:
                     each(sample, origins, dirs)
                 if isinstance(direct, str) and direct == "fused":
-                    if self.light_states is None:
-                        self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
-                    t = self.scene.trace_direct(origins, dirs, self.states, self.light_states, int(self.frame.max_depth),
+                    t = self.scene.trace_direct(origins, dirs, self.states, self._light_states(), int(self.frame.max_depth),
                                                 count_rays=count_rays, out=radiance)
                     self.budget_abandoned += t.work[0]
                     self.rays_total += t.work[1]
                     self.sample_add(sample, radiance, t.rays, budget)
                     continue
                 if direct:
-                    if self.light_states is None:
-                        self.light_states = rng_states(self.scene.seed, self.items, first=self.items, device=self.device)
                     st = self.scene.trace_steps(origins, dirs, self.states, int(self.frame.max_depth), compact=True, direct=direct,
-                                                light_states=self.light_states)
+                                                light_states=self._light_states())
                     self.carry = st.carry
                     for w in st.works:
                         self.budget_abandoned += w[0]
@@ -495,6 +537,10 @@ class Renderer:
         more per pass until it meets the stopping rule or has ``max_spp``.  One host read of the plan's totals per
         pass is the only synchronisation.  The frame's spp must be at least max(min_spp, step).  ``features``: every
         pass also adds to the first-hit feature buffers, and the result's ``features`` holds them resolved."""
+        return self._adaptive(self.render_budget, min_spp, max_spp, step, tolerance, floor, post, features)
+
+    def _adaptive(self, render, min_spp, max_spp, step, tolerance, floor, post, features):
+        """The loop of ``render_adaptive``, its passes rendered by ``render`` (``render_budget`` or ``render_direct``)."""
         if self.frame.spp < max(int(min_spp), int(step)):
             raise RtmiError("the frame's spp (%d) caps one pass: it must be at least max(min_spp, step)" % self.frame.spp)
         passes = total = 0
@@ -502,7 +548,7 @@ class Renderer:
             budget, active, pass_total = self.plan(min_spp, max_spp, step, tolerance, floor)
             if active == 0:
                 break
-            self.render_budget(budget, features=features)
+            render(budget, features=features)
             passes, total = passes + 1, total + pass_total
         self.check()
         return Adaptive(self.resolve(post), self.samples, passes, total, self.resolve_features() if features else None)
