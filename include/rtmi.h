@@ -978,6 +978,105 @@ typedef struct rtmi_trace_direct_args {
 } rtmi_trace_direct_args;
 int rtmi_trace_direct(const rtmi_scene *s, const rtmi_trace_direct_args *args, void *stream);
 
+/* rtmi_path_roulette.  Russian roulette as a wavefront step: the termination rule a loop of rtmi_bounce / rtmi_bounce_list
+ * steps may play after each step, with the survivors' compensation written where the folds read it.  Added without a
+ * version change: a caller detects it by the symbol rtmi_path_roulette.  The call needs no scene.
+ *
+ * It runs after step `step` of the loop, on that step's outputs; in a loop with direct sampling after
+ * rtmi_direct_sample[_mis] of that step, whose D[k] is formed from the unscaled A[k].  The candidates are
+ * rtmi_bounce_list's (d_list, n_list, d_count): a null list is the identity, entries >= n are dropped, entries are distinct.
+ * d_states: the PATHS' states in rtmi_trace's layout (uint32[6][n], stride n).  d_attenuation: layer `step` of the fold's
+ * stack.  d_throughput: float[n][3] that the caller fills with 1.0f once, before the first call of a loop.
+ *
+ * The rule per candidate i.  Binary32, every operation rounded on its own, no fused multiply-add, IEEE division; a NaN
+ * makes a comparison false.
+ *   - d_steps[i] != step + 1 (not stepped), or d_dirs[i] the zero vector, -0.0f included (ended): every word is kept.
+ *   - Else, with a = d_attenuation[i], P = d_throughput[i]:
+ *       t = P * a per channel;   q = t.x; if (t.y > q) q = t.y; if (t.z > q) q = t.z;
+ *       play = step >= first_step && q < 1;
+ *     not play: d_throughput[i] = t; no draw, nothing else changes.
+ *     play: p = q > p_min ? q : p_min;  u = CudaRandomFloat(0, 1) from the path's own state, which advances by exactly
+ *     one draw;  d_counts[0] += 1;
+ *       u <= p (survives): inv = 1 / p;  a' = a * inv per channel;  d_attenuation[i] = a';  d_throughput[i] = P * a' per
+ *         channel -- not t * inv: the throughput is by construction the forward product of the stack as it now stands;
+ *       else (killed): d_attenuation[i], d_dirs[i] and d_throughput[i] become three +0.0f each, and d_counts[1] += 1.
+ *   - A path that is not a candidate keeps every word.
+ * A killed path is an ended path for everything that exists: rtmi_path_compact drops it, later steps skip it, and
+ * rtmi_path_fold and rtmi_path_fold_direct fold it as a path that ended at a vertex emitting E[step], unchanged.  A
+ * survivor's continuation is scaled through A[step], so both folds stay correct as they are.
+ *
+ * The floor p_min.  u lies on a grid of 2^-32 rounded to binary32, so P(u <= p) differs from p by at most 2^-24 absolute
+ * (tests/test_roulette_host.py counts the draws): the floor bounds the relative bias of a weight by 2^-24 / p_min, and one
+ * compensation factor by 1 / p_min.
+ *
+ * One lane per candidate, the list taken 64 entries at a time by wave number; no cursor, no atomic in the distribution;
+ * each counter by one atomic per wave.  Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: null args, a wrong
+ * args->size, a non-zero reserved or reserved2, n or n_list negative or above 2^31 - 1, a null d_list with n_list > n, a null
+ * d_steps, d_dirs, d_attenuation, d_states or d_throughput with n_list > 0, step >= RTMI_MAX_DEPTH, p_min not in (0, 1]
+ * (NaN included).  n == 0 or n_list == 0 launches nothing. */
+typedef struct rtmi_path_roulette_args {
+  int32_t size;                      /* sizeof(rtmi_path_roulette_args) of the caller: must match the library's */
+  int32_t reserved;                  /* 0 */
+  int64_t n;
+  const uint32_t *d_list;            /* nullable: the identity */
+  int64_t n_list;
+  const uint32_t *d_count;           /* nullable */
+  uint32_t step;                     /* the step just made, 0-based */
+  uint32_t first_step;               /* no roulette at steps below this */
+  float p_min;                       /* floor of the survival probability, in (0, 1] */
+  int32_t reserved2;                 /* 0 */
+  const uint32_t *d_steps;           /* uint32[n] */
+  float *d_dirs;                     /* float[n][3]: the scattered rays */
+  float *d_attenuation;              /* float[n][3]: layer `step` of the fold's stack */
+  void *d_states;                    /* the PATHS' states, rtmi_trace's layout, stride n */
+  float *d_throughput;               /* float[n][3]; the caller fills it with 1.0f once */
+  unsigned long long *d_counts;      /* nullable, two words, added to */
+} rtmi_path_roulette_args;
+int rtmi_path_roulette(const rtmi_path_roulette_args *args, void *stream);
+
+/* rtmi_trace_roulette.  rtmi_trace with rtmi_path_roulette's rule played in the lane: what the loop of rtmi_bounce_list,
+ * rtmi_path_roulette and rtmi_path_compact does to a path, in ONE launch.  Added without a version change: a caller detects
+ * it by the symbol rtmi_trace_roulette.  rtmi_trace and every other entry are what they were.
+ *
+ * args: size, reserved (0); n, d_origins, d_dirs, max_depth, d_states, d_radiance, d_ray_counts (nullable) and d_work with
+ * rtmi_trace's meaning, shape and layout; first_step, p_min as rtmi_path_roulette's; d_counts (nullable): two words that are
+ * ADDED to, roulettes played and paths killed.
+ *
+ * The rule, by the entries that define it.  For every good ray i:
+ *   - vertex k is one rtmi_bounce iteration with rtmi_trace's ray handling (a bad scattered ray is followed as rtmi_trace
+ *     follows it, where the step skips it: the one difference);
+ *   - where vertex k scattered and k + 1 < max_depth, rtmi_path_roulette's rule with step = k, the path the only candidate,
+ *     its throughput (1, 1, 1) at the start; at k + 1 == max_depth nothing is played (Trace's last query only counts);
+ *   - the state advances by Trace's draws plus one per roulette played;
+ *   - d_ray_counts[i] = steps + (alive ? 1 : 0); a killed path is not alive;
+ *   - a bad ray is left out: radiance 0, count 0, state untouched.
+ * Radiance, summed FORWARD.  With the loop's final stacks E and A' (the survivors' layers scaled) and c the step count:
+ *     the path ended by its own hit (not killed, not cut):  P = (1, 1, 1);  P = P * A'[k] for k = 0 .. c - 2, ascending;
+ *         d_radiance[i] = E[c - 1] * P  per channel, every operation rounded on its own;
+ *     the path was killed or cut, or c == 0:  three +0.0f.
+ * E[k] is +0.0f on every layer that scattered (no material both emits and scatters), so in exact arithmetic this is
+ * rtmi_path_fold of those stacks; only the rounding order of one product differs, as with rtmi_trace_direct's forward sum.
+ * P is the throughput the rule carries anyway: no layer stack is written and no fold runs.
+ *
+ * Asynchronous on `stream`.  RTMI_ERR_INVALID before any HIP call: a null scene or args, a wrong args->size, a non-zero
+ * args->reserved, p_min not in (0, 1] (NaN included), every case of rtmi_trace; RTMI_ERR_DEPTH for max_depth outside
+ * [0, RTMI_MAX_DEPTH]; then RTMI_ERR_INVALID when the current device is not the scene's.  n == 0 launches nothing. */
+typedef struct rtmi_trace_roulette_args {
+  int32_t size;      /* sizeof(rtmi_trace_roulette_args) of the caller: must match the library's */
+  int32_t reserved;  /* 0 */
+  int64_t n;
+  const float *d_origins, *d_dirs;
+  int32_t max_depth;
+  uint32_t first_step;
+  float p_min;
+  void *d_states;
+  float *d_radiance;                  /* float[n][3] */
+  uint32_t *d_ray_counts;             /* nullable */
+  unsigned long long *d_counts;       /* nullable: two words, added to */
+  unsigned long long *d_work;         /* RTMI_TRACE_WORK_WORDS words */
+} rtmi_trace_roulette_args;
+int rtmi_trace_roulette(const rtmi_scene *s, const rtmi_trace_roulette_args *args, void *stream);
+
 /* rtmi_occluded_list.  rtmi_occluded for the candidates of (d_list, n_list, d_count) only: the visibility query of a loop
  * whose other steps take a live-path list, and of any caller who shoots shadow or ambient-occlusion rays from the vertices
  * rtmi_bounce_list leaves behind.  Added without a version change: a caller detects it by the symbol rtmi_occluded_list.

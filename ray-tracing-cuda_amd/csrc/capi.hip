@@ -1526,6 +1526,49 @@ int rtmi_trace_direct(const rtmi_scene *sp, const rtmi_trace_direct_args *p, voi
   return RTMI_OK;
 }
 
+// ------------------------------------------------------------------ Russian roulette
+static bool roulette_floor(float p_min) { return p_min > 0.f && p_min <= 1.f; }  // (a NaN is neither)
+
+int rtmi_path_roulette(const rtmi_path_roulette_args *p, void *stream) {
+  static_assert(sizeof(rtmi_path_roulette_args) == 104, "rtmi_path_roulette_args is 104 bytes");
+  if (!p) return fail(RTMI_ERR_INVALID, "null rtmi_path_roulette_args");
+  if (p->size != (int32_t)sizeof(rtmi_path_roulette_args) || p->reserved != 0 || p->reserved2 != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_path_roulette_args.size does not match this library, or reserved or reserved2 is not 0");
+  if (const int rc = list_args(p->n, "negative path count", "more than 2^31 - 1 paths", p->d_list, p->n_list)) return rc;
+  if (p->n_list > 0 && !(p->d_steps && p->d_dirs && p->d_attenuation && p->d_states && p->d_throughput))
+    return fail(RTMI_ERR_INVALID, "null step, direction, attenuation, state or throughput array");
+  if (p->step >= (uint32_t)RTMI_MAX_DEPTH) return fail(RTMI_ERR_INVALID, "step outside 0..RTMI_MAX_DEPTH - 1");
+  if (!roulette_floor(p->p_min)) return fail(RTMI_ERR_INVALID, "p_min outside (0, 1]");
+  RouletteArgs a{};
+  a.list = p->d_list, a.count = p->d_count;
+  a.n = (uint32_t)p->n, a.n_list = (uint32_t)p->n_list, a.step = p->step, a.first_step = p->first_step, a.p_min = p->p_min;
+  a.steps = p->d_steps, a.dirs = p->d_dirs, a.attenuation = p->d_attenuation, a.throughput = p->d_throughput;
+  a.states = reinterpret_cast<uint32_t *>(p->d_states), a.counts = p->d_counts;
+  HIP_TRY(launch_path_roulette(a, (hipStream_t)stream));
+  return RTMI_OK;
+}
+
+int rtmi_trace_roulette(const rtmi_scene *sp, const rtmi_trace_roulette_args *p, void *stream) {
+  static_assert(sizeof(rtmi_trace_roulette_args) == 88, "rtmi_trace_roulette_args is 88 bytes");
+  if (!sp) return fail(RTMI_ERR_INVALID, "null scene");
+  if (!p) return fail(RTMI_ERR_INVALID, "null rtmi_trace_roulette_args");
+  if (p->size != (int32_t)sizeof(rtmi_trace_roulette_args) || p->reserved != 0)
+    return fail(RTMI_ERR_INVALID, "rtmi_trace_roulette_args.size does not match this library, or reserved is not 0");
+  if (!roulette_floor(p->p_min)) return fail(RTMI_ERR_INVALID, "p_min outside (0, 1]");
+  const Scene *s;
+  int n_cu;
+  int max_depth = p->max_depth;
+  const int rc = batch_prologue(sp, p->n, p->d_origins && p->d_dirs && p->d_states && p->d_radiance && p->d_work,
+                                "null ray, state, radiance or work array", &max_depth, &s, &n_cu);
+  if (rc || p->n == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(p->d_work, 0, kCallParamsOffset, st));  // (as rtmi_trace)
+  HIP_TRY(launch_trace_roulette(pick_query_variant(s->features), s->dev, (s->features & F_TEX) != 0, n_cu, p->n, max_depth,
+                                p->first_step, p->p_min, p->d_origins, p->d_dirs, reinterpret_cast<uint32_t *>(p->d_states),
+                                p->d_radiance, p->d_ray_counts, p->d_counts, p->d_work, st));
+  return RTMI_OK;
+}
+
 // ------------------------------------------------------------------ any-hit queries for the paths of a list
 // rtmi_occluded for rtmi_bounce_list's candidates.  The arguments first, without a HIP call, then the scene's device.
 static int occluded_list(const rtmi_scene *sp, int64_t n, const uint32_t *d_list, int64_t n_list, const uint32_t *d_count,

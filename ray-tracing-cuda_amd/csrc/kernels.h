@@ -309,6 +309,24 @@ struct TraceDirectBufs;
 hipError_t launch_trace_direct(uint32_t variant, const SceneDev &sc, bool tex_layers, bool sphere_lights, int n_cu, int64_t n,
                                int max_depth, const float *d_o, const float *d_d, uint32_t *d_states, const TraceDirectBufs &dx,
                                float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_work, hipStream_t stream);
+// Russian roulette after a step (rtmi_path_roulette; paths.hip: path_roulette_kernel): the caller's arrays as include/rtmi.h
+// names them, every pointer checked by capi.hip.  n == 0 or n_list == 0 launches nothing.
+struct RouletteArgs {
+  const uint32_t *list, *count;  // the candidates (path_list.h), both nullable
+  uint32_t n, n_list, step, first_step;
+  float p_min;
+  const uint32_t *steps;
+  float *dirs, *attenuation, *throughput;
+  uint32_t *states;
+  unsigned long long *counts;  // nullable: {played, killed}, added to
+};
+hipError_t launch_path_roulette(const RouletteArgs &a, hipStream_t stream);
+// rtmi_trace with that rule played in the lane (rtmi_trace_roulette; trace_roulette.hip: trace_roulette_kernel<F>, render_body.h
+// in its ROULETTE mode): launch_trace's arguments, the rule's two parameters and its two counters (nullable).
+hipError_t launch_trace_roulette(uint32_t variant, const SceneDev &sc, bool tex_layers, int n_cu, int64_t n, int max_depth,
+                                 uint32_t first_step, float p_min, const float *d_o, const float *d_d, uint32_t *d_states,
+                                 float *d_radiance, uint32_t *d_ray_counts, unsigned long long *d_counts,
+                                 unsigned long long *d_work, hipStream_t stream);
 // Per-pixel sample budgets (rtmi_render_budget; calls.hip: budget_kernel), on the query variants with F_DEFOCUS added.
 // fr: the shard's frame, fr.spp = the cap on one call's samples per pixel.  d_sum, d_sq (nullable), d_samples,
 // d_ray_counts (nullable) accumulate; d_work as launch_trace's (RTMI_BUDGET_WORK_WORDS words, the same layout).

@@ -160,4 +160,65 @@ hipError_t launch_path_fold(int64_t n, int layers, const float *d_dirs, const ui
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ Russian roulette as a step (rtmi_path_roulette)
+// include/rtmi.h states the rule; tests/roulettelib.py restates it.  One lane per candidate: wave w of the grid takes
+// entries 64w .. 64w + 63 of the list (path_list.h), so the grid is sized by the host's bound and a wave past the device's
+// count leaves at once -- no cursor, no atomic in the distribution.  The lanes that play and those that kill are counted by
+// a ballot each and one atomic per wave.  Every binary32 * and / below is one operation (no contraction in this unit).
+constexpr int kRouletteThreads = 256;
+__global__ __launch_bounds__(kRouletteThreads) void path_roulette_kernel(RouletteArgs a) {
+  const PathList pl{a.list, a.count, a.n_list};
+  const uint32_t end = list_end(pl);
+  const uint32_t e = blockIdx.x * (uint32_t)kRouletteThreads + threadIdx.x;  // (below 2^31 + 256: n_list <= 2^31 - 1)
+  bool played = false, killed = false;
+  if (e < end) {
+    const uint32_t i = list_entry(pl, e);
+    // (not a path: dropped before anything is addressed with it; not stepped, or ended: every word is kept)
+    if (i < a.n && a.steps[i] == a.step + 1u) {
+      float *d = a.dirs + (int64_t)i * 3, *at = a.attenuation + (int64_t)i * 3, *th = a.throughput + (int64_t)i * 3;
+      if (!(d[0] == 0.f && d[1] == 0.f && d[2] == 0.f)) {
+        const V3 att = mk(at[0], at[1], at[2]), P = mk(th[0], th[1], th[2]);
+        const V3 t = mk(__fmul_rn(P.x, att.x), __fmul_rn(P.y, att.y), __fmul_rn(P.z, att.z));
+        float q = t.x;
+        if (t.y > q) q = t.y;
+        if (t.z > q) q = t.z;
+        played = a.step >= a.first_step && q < 1.f;
+        if (!played) {
+          th[0] = t.x, th[1] = t.y, th[2] = t.z;
+        } else {
+          const float p = q > a.p_min ? q : a.p_min;
+          Rng rng;
+          rng.d = a.states[0 * (int64_t)a.n + i], rng.v0 = a.states[1 * (int64_t)a.n + i], rng.v1 = a.states[2 * (int64_t)a.n + i];
+          rng.v2 = a.states[3 * (int64_t)a.n + i], rng.v3 = a.states[4 * (int64_t)a.n + i], rng.v4 = a.states[5 * (int64_t)a.n + i];
+          const float u = rng_01(rng);
+          a.states[0 * (int64_t)a.n + i] = rng.d, a.states[1 * (int64_t)a.n + i] = rng.v0, a.states[2 * (int64_t)a.n + i] = rng.v1;
+          a.states[3 * (int64_t)a.n + i] = rng.v2, a.states[4 * (int64_t)a.n + i] = rng.v3, a.states[5 * (int64_t)a.n + i] = rng.v4;
+          if (u <= p) {
+            const float inv = 1.0f / p;
+            const V3 s = mk(__fmul_rn(att.x, inv), __fmul_rn(att.y, inv), __fmul_rn(att.z, inv));
+            at[0] = s.x, at[1] = s.y, at[2] = s.z;
+            th[0] = __fmul_rn(P.x, s.x), th[1] = __fmul_rn(P.y, s.y), th[2] = __fmul_rn(P.z, s.z);
+          } else {
+            killed = true;
+            at[0] = 0.f, at[1] = 0.f, at[2] = 0.f;
+            d[0] = 0.f, d[1] = 0.f, d[2] = 0.f;
+            th[0] = 0.f, th[1] = 0.f, th[2] = 0.f;
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long np = __builtin_amdgcn_ballot_w64(played), nk = __builtin_amdgcn_ballot_w64(killed);
+  if ((threadIdx.x & 63u) == 0u && a.counts) {
+    if (np) atomicAdd(&a.counts[0], (unsigned long long)__popcll(np));
+    if (nk) atomicAdd(&a.counts[1], (unsigned long long)__popcll(nk));
+  }
+}
+hipError_t launch_path_roulette(const RouletteArgs &a, hipStream_t stream) {
+  if (a.n == 0 || a.n_list == 0) return hipSuccess;
+  hipLaunchKernelGGL(path_roulette_kernel, dim3((unsigned)cdiv((int64_t)a.n_list, (int64_t)kRouletteThreads)),
+                     dim3(kRouletteThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
 }  // namespace rtmi

@@ -18,6 +18,10 @@
 // DIRECT with BUDGET (with or without FEATURES) is rtmi_render_direct (render_direct.hip: budget_direct_kernel,
 // feature_direct_kernel): the budget render whose every sample is traced that way -- the lane's forward sum restarts with
 // each sample, the light state is the work item's, and a sample's value is its path's radiance + its forward sum.
+// ROULETTE (with RAYS alone) is rtmi_trace_roulette (trace_roulette.hip: trace_roulette_kernel): rtmi_trace with
+// rtmi_path_roulette's rule played in the lane after every vertex that scatters but the last -- the path's throughput is
+// carried forward (RouletteLane below), no layer is stacked and no fold runs: a path that ends by its own hit gets its
+// emission times that throughput, a killed or cut one nothing.
 // What each mode is told: RenderParams and CallExtras below.
 #pragma once
 
@@ -229,6 +233,21 @@ struct DirectLane<true> {
   uint32_t n_sampled, n_weighed, n_occluded;
 };
 
+// (ROULETTE) What the mode is told besides rtmi_trace's block, and what a lane carries beside its path: thr, the forward
+// product of the layers as the rule leaves them (include/rtmi.h "rtmi_trace_roulette": P), and the lane's share of d_counts.
+struct RouletteBufs {
+  uint32_t first_step;
+  float p_min;
+  unsigned long long *counts;  // nullable: {played, killed}, added to
+};
+template <bool ON>
+struct RouletteLane {};
+template <>
+struct RouletteLane<true> {
+  V3 thr;
+  uint32_t n_played, n_killed;
+};
+
 // The loop on the block's fields: the kernels hand each over themselves (kernels.hip), the fields of other modes left
 // out.  The buffers are parameters of their own because only a parameter can say that nothing else points into what it
 // points to, and the compiler uses it: with the buffers as locals loaded from the block 44 of the 45 kernels compile to
@@ -238,9 +257,9 @@ struct DirectLane<true> {
 // M (kernels.h): the mode word.  A pinned decision reads `(M & PIN_X) || run-time test` (or `!(M & PIN_X) && ...`), which
 // the front end folds: with M == 0 every line below is the run-time test it was.
 // DX: DIRECT's own block (direct_body.h: TraceDirectBufs), a template parameter so that the units without a light table
-// need not know the type.
+// need not know the type; ROULETTE's is RouletteBufs, through the same parameter.
 template <uint32_t F, bool RAYS = false, bool BUDGET = false, bool FEATURES = false, uint32_t M = 0, bool STEP = false,
-          bool LIST = false, bool DIRECT = false, bool SPH = false, class DX = void>
+          bool LIST = false, bool DIRECT = false, bool SPH = false, class DX = void, bool ROULETTE = false>
 __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &fr, const LaunchCfg &lc,
                                             uint32_t *__restrict__ states, float *__restrict__ out,
                                             uint32_t *__restrict__ ray_counts,
@@ -255,6 +274,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   static_assert(!DIRECT || ((RAYS || BUDGET) && !STEP && !LIST && M == 0),
                 "direct light is a mode of the caller's rays or of the budget's samples, traced whole");
   static_assert(!SPH || DIRECT, "the sphere lights' twin is a direct one");
+  static_assert(!ROULETTE || (RAYS && !STEP && !LIST && !BUDGET && !DIRECT && M == 0),
+                "the roulette is a mode of the caller's rays, traced whole, without direct light");
   static_assert(!STEP || (RAYS && M == 0), "the step is a mode of the caller's rays");
   static_assert(!LIST || STEP, "the list is where a step's items come from");
   static_assert(!FEATURES || BUDGET, "the feature buffers belong to the budget mode");
@@ -378,6 +399,8 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
     dl.flag = dl.shadow = false;
     dl.n_sampled = dl.n_weighed = dl.n_occluded = 0u;
   }
+  [[maybe_unused]] RouletteLane<ROULETTE> rl;
+  if constexpr (ROULETTE) rl.thr = splat(1.f), rl.n_played = rl.n_killed = 0u;
   // Bit 31 of depth: d is the raw vector of a new camera ray or of a Lambertian bounce, and normalize(normalize(d)) is
   // due at the top of the next iteration, which clears the bit before anything reads depth (a mark of its own, a lane
   // mask or a flag, costs more instructions in every fast kernel: NOTES.md, "Deferred normalisation")
@@ -759,6 +782,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         depth = 0;
         active = true;
         if constexpr (DIRECT) dl.thr = splat(1.f), dl.sum = splat(0.f), dl.flag = false;
+        if constexpr (ROULETTE) rl.thr = splat(1.f);
       } else if (has_px) {
         // ray_tracing.cu:68-74 + camera.cu:57-70
         float r1 = rng_01(rng);
@@ -1203,8 +1227,39 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
                 ended = false;
               }
             }
+            if constexpr (ROULETTE) {
+              // rtmi_path_roulette's rule with step = depth, the path its only candidate: layer_att is the layer A[depth]
+              // as the step writes it; nothing is played behind the last vertex a path may have.
+              if (scattered && depth + 1 < fr.max_depth) {
+                const V3 layer_att = ((F & F_TEX) && (layer >> 31)) ? texel_rgb(layer) : rgb;
+                const V3 t = mk(__fmul_rn(rl.thr.x, layer_att.x), __fmul_rn(rl.thr.y, layer_att.y), __fmul_rn(rl.thr.z, layer_att.z));
+                float q = t.x;
+                if (t.y > q) q = t.y;
+                if (t.z > q) q = t.z;
+                if ((uint32_t)depth >= dx->first_step && q < 1.f) {
+                  const float p = q > dx->p_min ? q : dx->p_min;
+                  const float u = rng_01(rng);
+                  rl.n_played++;
+                  if (u <= p) {
+                    const float inv = 1.0f / p;
+                    const V3 s = mk(__fmul_rn(layer_att.x, inv), __fmul_rn(layer_att.y, inv), __fmul_rn(layer_att.z, inv));
+                    rl.thr = mk(__fmul_rn(rl.thr.x, s.x), __fmul_rn(rl.thr.y, s.y), __fmul_rn(rl.thr.z, s.z));
+                  } else {
+                    // killed: the vertex does not scatter after all -- `ended` stays set and result is +0.0f, which the
+                    // zeroed throughput keeps in the terminal product
+                    scattered = false;
+                    rl.thr = splat(0.f);
+                    rl.n_killed++;
+                  }
+                } else {
+                  rl.thr = t;
+                }
+              }
+            }
             if (!STEP && scattered) {
-              if (tex32) {
+              if constexpr (ROULETTE) {
+                // (no layer is stacked: the throughput above is all the terminal branch needs)
+              } else if (tex32) {
                 *reinterpret_cast<uint32_t *>(smem + tex_layer_offset(depth)) = layer;
               } else if (nibble_ids) {
                 const uint32_t at = ids_offset(depth >> 1);  // this lane's own byte: no other lane writes it
@@ -1264,6 +1319,13 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         // attenuation * result, deepest layer first.  The addition only matters for a product of -0,
         // which needs a colour with its sign bit set (sc.unsigned_colours).
         int i = depth - 1;
+        if constexpr (ROULETTE) {
+          // No stack, no fold.  The path ended by its own hit -- not cut -- and its emission meets the throughput:
+          // E[c-1] * P (a killed path: +0.0f * +0.0f)
+          i = -1;
+          if (depth < fr.max_depth)
+            result = mk(__fmul_rn(result.x, rl.thr.x), __fmul_rn(result.y, rl.thr.y), __fmul_rn(result.z, rl.thr.z));
+        }
         if (!tex32 && fast_fold) {
           // common case (byte ids, material table in LDS, no signed colours) without the per-layer
           // uniform branches: four layers at a time, ids first, then colours, then the products.
@@ -1367,6 +1429,7 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
         // value the sum and the moment take
         if constexpr (DIRECT && BUDGET) result = result + dl.sum;
         color = color + result;
+        if constexpr (ROULETTE) color = result;  // (one path per item: the product itself, its zero's sign kept)
         if constexpr (DIRECT && !BUDGET) color = color + dl.sum;  // r_path + the forward sum: one addition per channel
         if constexpr (BUDGET)  // the product and the sum rounded separately, so that a binary32 restatement is exact
           moment = mk(__fadd_rn(moment.x, __fmul_rn(result.x, result.x)), __fadd_rn(moment.y, __fmul_rn(result.y, result.y)),
@@ -1385,6 +1448,14 @@ __device__ __forceinline__ void render_body(const SceneDev &sc, const FrameDev &
   if constexpr (DIRECT) {  // d_counts: vertices sampled, emissions weighed, shadow rays answered occluded -- a wave reduce each
     const uint32_t v[3] = {dl.n_sampled, dl.n_weighed, dl.n_occluded};
     for (int c = 0; c < 3; c++) {
+      unsigned long long total = v[c];
+      for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off);
+      if ((threadIdx.x & 63) == 0 && total && dx->counts) atomicAdd(&dx->counts[c], total);
+    }
+  }
+  if constexpr (ROULETTE) {  // d_counts: roulettes played, paths killed -- a wave reduce each
+    const uint32_t v[2] = {rl.n_played, rl.n_killed};
+    for (int c = 0; c < 2; c++) {
       unsigned long long total = v[c];
       for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off);
       if ((threadIdx.x & 63) == 0 && total && dx->counts) atomicAdd(&dx->counts[c], total);

@@ -138,6 +138,21 @@ class TraceDirectArgs(C.Structure):
                 ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p), ("d_work", C.c_void_p)]
 
 
+class PathRouletteArgs(C.Structure):
+    """rtmi_path_roulette_args of include/rtmi.h (the arrays of one rtmi_path_roulette call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("d_list", C.c_void_p), ("n_list", C.c_int64),
+                ("d_count", C.c_void_p), ("step", C.c_uint32), ("first_step", C.c_uint32), ("p_min", C.c_float),
+                ("reserved2", C.c_int32), ("d_steps", C.c_void_p), ("d_dirs", C.c_void_p), ("d_attenuation", C.c_void_p),
+                ("d_states", C.c_void_p), ("d_throughput", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+class TraceRouletteArgs(C.Structure):
+    """rtmi_trace_roulette_args of include/rtmi.h (the arrays of one rtmi_trace_roulette call)."""
+    _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("d_origins", C.c_void_p), ("d_dirs", C.c_void_p),
+                ("max_depth", C.c_int32), ("first_step", C.c_uint32), ("p_min", C.c_float), ("d_states", C.c_void_p),
+                ("d_radiance", C.c_void_p), ("d_ray_counts", C.c_void_p), ("d_counts", C.c_void_p), ("d_work", C.c_void_p)]
+
+
 class RenderDirectArgs(C.Structure):
     """rtmi_render_direct_args of include/rtmi.h (the arrays of one rtmi_render_direct call)."""
     _fields_ = [("size", C.c_int32), ("reserved", C.c_int32), ("d_budget", C.c_void_p), ("d_states", C.c_void_p),
@@ -291,6 +306,8 @@ SYMBOLS = [
     ("rtmi_path_advance", C.c_int, [C.c_void_p, _frp, C.POINTER(PathAdvanceArgs), C.c_void_p]),
     ("rtmi_trace_direct", C.c_int, [C.c_void_p, C.POINTER(TraceDirectArgs), C.c_void_p]),
     ("rtmi_render_direct", C.c_int, [C.c_void_p, _frp, C.POINTER(RenderDirectArgs), C.c_void_p]),
+    ("rtmi_path_roulette", C.c_int, [C.POINTER(PathRouletteArgs), C.c_void_p]),
+    ("rtmi_trace_roulette", C.c_int, [C.c_void_p, C.POINTER(TraceRouletteArgs), C.c_void_p]),
 ]
 
 # RTMI_LIGHTS_* of include/rtmi.h (rtmi_scene_light_kinds)

@@ -5,10 +5,10 @@ import numpy as np
 
 from . import _abi
 from ._abi import (HIT_WORDS, LIGHT_DTYPE, MAX_DEPTH, STATE_WORDS, TRACE_WORK_WORDS, TRANSFORM_FN, DirectSampleMisArgs, RtmiError,
-                   TraceDirectArgs, _addr, _camera21, _check, _f, _fp, _u32p, lib)
+                   TraceDirectArgs, TraceRouletteArgs, _addr, _camera21, _check, _f, _fp, _u32p, lib)
 from ._tensors import _check_batch, _need, _new, _out_buffer, _ptr, _ptrs, _stream, _torch
-from .wavefront import (Bounce, DirectSample, Hits, Occlusion, Steps, Trace, TraceDirect, _list_args, _new_paths, _path_compact,
-                        path_fold, path_fold_direct)
+from .wavefront import (Bounce, DirectSample, Hits, Occlusion, Roulette, Steps, Trace, TraceDirect, TraceRoulette, _list_args,
+                        _new_paths, _path_compact, path_fold, path_fold_direct, path_roulette)
 
 
 class _CommitOptions:
@@ -25,7 +25,9 @@ class _CommitOptions:
 
 
 class _FusedTraces:
-    """The entries that run a whole loop of steps in one kernel.  A base of ``SceneBuilder``: they are the builder's methods."""
+    """The entries that run a whole loop of steps in one kernel, and the loop that a fused rule is held to where
+    ``trace_steps`` itself cannot take it (its parameter list is recorded).  A base of ``SceneBuilder``: they are the
+    builder's methods."""
 
     def trace_direct(self, origins, directions, states, light_states, max_depth, count_rays=False, out=None):
         """``trace`` with next-event estimation inside the kernel (rtmi_trace_direct), enqueued on torch's current stream:
@@ -57,6 +59,50 @@ class _FusedTraces:
         with torch.cuda.device(dev):
             _check(self.L.rtmi_trace_direct(self.h, C.byref(a), stream), "rtmi_trace_direct")
         return TraceDirect(out, rays, work, counts, (origins, directions, states, light_states))
+
+    def trace_roulette(self, origins, directions, states, max_depth, first_step=3, p_min=0.05, count_rays=False, out=None):
+        """``trace`` with Russian roulette played inside the kernel (rtmi_trace_roulette), enqueued on torch's current stream:
+        per path the steps, draws and kills of ``trace_steps_roulette(compact=True)`` in one launch, the radiance summed
+        forward along the path (include/rtmi.h states the product; it differs from that loop's fold by the rounding order
+        only).  The expectation is ``trace``'s.
+
+        ``origins`` / ``directions`` / ``states`` / ``max_depth`` / ``count_rays`` / ``out`` as for ``trace``; ``first_step``,
+        ``p_min`` as ``Roulette``'s.  Returns ``TraceRoulette``; call ``.check()`` on it before trusting the answers of a mesh
+        scene."""
+        torch = _torch()
+        n, dev, _ = _check_batch("rtmi_trace_roulette", origins, directions)
+        _need(states, "states", (STATE_WORDS, n), dev, torch.int32, words="(6, N)")
+        max_depth = int(max_depth)
+        if not 0 <= max_depth <= MAX_DEPTH:
+            raise RtmiError("max_depth %d outside [0, %d]" % (max_depth, MAX_DEPTH))
+        rule = Roulette(first_step, p_min)  # (its checks)
+        out = _out_buffer(out, "(N, 3)", (n, 3), dev, torch.float32)
+        stream = self._stream(dev)
+        origins, directions = origins.contiguous(), directions.contiguous()
+        rays = _new(dev, (n,), torch.int32) if count_rays else None
+        work = _new(dev, (TRACE_WORK_WORDS,), torch.int64, zero=True)  # (n == 0 leaves it untouched)
+        counts = _new(dev, (2,), torch.int64, zero=True)
+        a = TraceRouletteArgs()
+        a.size, a.reserved, a.n, a.max_depth = C.sizeof(TraceRouletteArgs), 0, n, max_depth
+        a.first_step, a.p_min = rule.first_step, rule.p_min
+        a.d_origins, a.d_dirs, a.d_states = _addr(origins), _addr(directions), _addr(states)
+        a.d_radiance, a.d_ray_counts, a.d_counts, a.d_work = _addr(out), _addr(rays), _addr(counts), _addr(work)
+        with torch.cuda.device(dev):
+            _check(self.L.rtmi_trace_roulette(self.h, C.byref(a), stream), "rtmi_trace_roulette")
+        return TraceRoulette(out, rays, work, counts, (origins, directions, states))
+
+    def trace_steps_roulette(self, origins, directions, states, max_depth, roulette, each=None, hits=None, compact=False,
+                             direct=False, light_states=None, shadow=None):
+        """``trace_steps`` with Russian roulette: the same loop, every argument with ``trace_steps``' meaning, and after every
+        step but the last ``path_roulette(k, result, states, roulette)`` on the step's candidates -- with ``direct`` behind
+        that step's ``direct_sample`` and shadow query, and before ``each``.  With ``compact`` the compaction that follows
+        drops the killed paths.  ``roulette``: a ``Roulette``, reset here; afterwards its ``throughput`` and ``counts`` are the
+        loop's.  ``states`` advance by one more draw per roulette played; the radiance has ``trace``'s expectation.  Returns
+        ``Steps``, exactly its fields."""
+        if not isinstance(roulette, Roulette):
+            raise RtmiError("roulette must be an rtmi.wavefront.Roulette")
+        roulette.reset()
+        return self._steps_loop(origins, directions, states, max_depth, each, hits, compact, direct, light_states, shadow, roulette)
 
 
 class SceneBuilder(_CommitOptions, _FusedTraces):
@@ -455,7 +501,8 @@ class SceneBuilder(_CommitOptions, _FusedTraces):
         radiance while ``each`` changes nothing.  ``states`` advance in place, as in ``trace``.  ``each(step, result)``
         is called after every step is enqueued, with the step's ``Bounce`` (``result.origins`` / ``.directions`` are the
         loop's own ray tensors): the place for shadow rays from ``result.hits``, or a termination rule -- zeroing a path's
-        direction ends it, and the fold then takes its last layer's emitted as the path's end.  ``hits``: whether the
+        direction ends it, and the fold then takes its last layer's emitted as the path's end (Russian roulette is built:
+        ``trace_steps_roulette``).  ``hits``: whether the
         steps record hits (default: when ``each`` is given).  Returns ``Steps``.
 
         ``compact``: False (the default) steps all N paths every time (``bounce``).  True steps the live paths only: every
@@ -487,6 +534,10 @@ class SceneBuilder(_CommitOptions, _FusedTraces):
         did not sample.  (The one path outside this argument is ``bounce``'s documented bad scattered ray, a non-zero
         direction that does not normalise: it may sample, leaves the list alive, and ``"all"`` answers its stale shadow
         ray again in the layers after its last, which no fold reads.)"""
+        return self._steps_loop(origins, directions, states, max_depth, each, hits, compact, direct, light_states, shadow, None)
+
+    def _steps_loop(self, origins, directions, states, max_depth, each, hits, compact, direct, light_states, shadow, roulette):
+        """The loop of ``trace_steps`` and, with a ``Roulette``, of ``trace_steps_roulette``."""
         torch = _torch()
         if not (direct is False or direct is True or direct == "mis"):
             raise RtmiError("direct must be False, True or \"mis\"")
@@ -539,6 +590,8 @@ class SceneBuilder(_CommitOptions, _FusedTraces):
                 else:
                     q = self.occluded(rays[0], rays[1], rays[2], out=occ[k])
                 r.work[0] += q.counts[0]  # (abandoned searches: check())
+            if roulette is not None and k + 1 < max_depth:  # (behind the step's direct light: D[k] is formed from the unscaled A[k])
+                path_roulette(k, r, states, roulette)
             if each is not None:
                 each(k, r)
             if compact and k + 1 < max_depth:  # the next step's list: the live ones of this step's (or of all N)

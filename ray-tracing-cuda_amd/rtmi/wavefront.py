@@ -1,9 +1,10 @@
 """The value types of the ray queries and of a wavefront of paths, and the free functions over path arrays: the folds,
-the compaction and the RNG states (rtmi_path_fold, rtmi_path_fold_direct, rtmi_path_compact, rtmi_rng_init_n)."""
+the compaction, Russian roulette and the RNG states (rtmi_path_fold, rtmi_path_fold_direct, rtmi_path_compact,
+rtmi_path_roulette, rtmi_rng_init_n)."""
 import collections
 import ctypes as C
 
-from ._abi import MAX_DEPTH, STATE_WORDS, RtmiError, _check, lib
+from ._abi import MAX_DEPTH, STATE_WORDS, PathRouletteArgs, RtmiError, _addr, _check, lib
 from ._tensors import _check_batch, _lead, _need, _new, _out_buffer, _ptr, _ptrs, _stream, _torch
 
 
@@ -83,6 +84,81 @@ class TraceDirect(Trace):
     def check(self):
         _complete(self.work[0], "rtmi_trace_direct")
         return self
+
+
+class TraceRoulette(Trace):
+    """What ``SceneBuilder.trace_roulette`` returns: a ``Trace`` (``rgb``, ``rays``, ``work``, ``check()``, ``total_rays()``) and
+    ``counts`` (2,) int64: roulettes played, paths killed."""
+
+    def __init__(self, rgb, rays, work, counts, keep):
+        Trace.__init__(self, rgb, rays, work, keep)
+        self.counts = counts
+
+    def check(self):
+        _complete(self.work[0], "rtmi_trace_roulette")
+        return self
+
+
+class Roulette:
+    """Russian roulette for a loop of steps (rtmi_path_roulette): no roulette at steps below ``first_step``, and ``p_min`` in
+    (0, 1], the floor of the survival probability.  A small holder: after a call it carries ``throughput`` (N, 3) float32,
+    each path's forward product of the attenuation layers as the rule left them, and ``counts`` (2,) int64 on the device:
+    roulettes played, paths killed.  ``reset()`` forgets both, for the next loop."""
+
+    def __init__(self, first_step=3, p_min=0.05):
+        first_step, p_min = int(first_step), float(p_min)
+        if not 0 <= first_step < 1 << 32:
+            raise RtmiError("first_step must be in [0, 2^32)")
+        if not 0.0 < p_min <= 1.0:
+            raise RtmiError("p_min must be in (0, 1]")
+        self.first_step, self.p_min = first_step, p_min
+        self.throughput = self.counts = None
+
+    def reset(self):
+        self.throughput = self.counts = None
+        return self
+
+
+def path_roulette(step, result, states, roulette, paths=None):
+    """Russian roulette after step number ``step`` of a loop (rtmi_path_roulette), enqueued on torch's current stream.
+
+    ``result``: the ``Bounce`` of that step, made with ``steps`` and the layer tensor ``attenuation`` of the fold's stack;
+    ``states``: the paths' own (6, N) int32 RNG states, advanced by one draw per roulette played; ``roulette``: the loop's
+    ``Roulette``, whose ``throughput`` (ones at a loop's start) and ``counts`` are made here when None and updated;
+    ``paths``: the candidates, a ``Paths`` with distinct entries (None: the step's own, ``result.paths``, or all N).  A
+    survivor's ``result.attenuation`` is divided by its survival probability; a killed path gets a zero attenuation and a
+    zero direction, and is an ended path for the compaction, the later steps and both folds.  In a loop with direct
+    sampling call it after that step's ``direct_sample``.  Returns ``roulette``."""
+    torch = _torch()
+    if not isinstance(result, Bounce) or result.steps is None:
+        raise RtmiError("result must be the Bounce of a step made with steps")
+    if not isinstance(roulette, Roulette):
+        raise RtmiError("roulette must be an rtmi.wavefront.Roulette")
+    d = result.directions
+    _lead(d, "result.directions", "rtmi_path_roulette", 2, "(N, 3)", True)
+    n, dev = int(d.shape[0]), d.device
+    step = int(step)
+    if not 0 <= step < MAX_DEPTH:
+        raise RtmiError("step %d outside [0, %d)" % (step, MAX_DEPTH))
+    idx, n_list, cnt = _list_args(result.paths if paths is None else paths, n, dev)
+    _need(states, "states", (STATE_WORDS, n), dev, torch.int32, words="(6, N)")
+    _need(result.attenuation, "result.attenuation", (n, 3), dev, torch.float32, words="(N, 3)")
+    _need(result.steps, "result.steps", (n,), dev, torch.int32, words="(N,)")
+    if roulette.throughput is None:
+        roulette.throughput = torch.ones((n, 3), dtype=torch.float32, device=dev)
+    if roulette.counts is None:
+        roulette.counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+    _need(roulette.throughput, "roulette.throughput", (n, 3), dev, torch.float32, words="(N, 3)")
+    _need(roulette.counts, "roulette.counts", (2,), dev, torch.int64, words="(2,)")
+    a = PathRouletteArgs()
+    a.size, a.reserved, a.reserved2, a.n, a.n_list = C.sizeof(PathRouletteArgs), 0, 0, n, n_list
+    a.step, a.first_step, a.p_min = step, roulette.first_step, roulette.p_min
+    a.d_list, a.d_count, a.d_steps, a.d_dirs = _addr(idx), _addr(cnt), _addr(result.steps), _addr(d)
+    a.d_attenuation, a.d_states = _addr(result.attenuation), _addr(states)
+    a.d_throughput, a.d_counts = _addr(roulette.throughput), _addr(roulette.counts)
+    with torch.cuda.device(dev):
+        _check(lib().rtmi_path_roulette(C.byref(a), _stream(dev)), "rtmi_path_roulette")
+    return roulette
 
 
 class Bounce:
